@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the MI355X-native ST-GCN / CoST-GCN forward path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload clip|step] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload clip|step] [--batch B] [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch of synthetic input already resident in HBM:
   clip : full 10-block ST-GCN clip forward (input norm -> 10 blocks -> pool+fc), batch 256 clips per GPU,
@@ -15,6 +15,11 @@ fixed), the only exchange is one RCCL all-gather of logits per step.  Rank 0 pri
 70 % of the path's FLOPs): algorithmic FLOPs of its launches (SURVEY 8d accounting) / their duration measured
 live with HIP events on the launch stream, against the dense fp32 MFMA peak (157.3 TFLOP/s).
 `cpu_baseline` times the CPU oracle (a port of the reference's op sequence, see oracle/) on the host cores.
+
+A plain run measures the headline workload alone: set up, warm up, time --steps steps, print the line.  --full adds
+every other leg (CPU baselines, the bf16x3 precision mode, clip and online latency, the configs[4] shard, the online
+workload beside the clip headline with its kernel-level timing pass, configs[3]).  --dump-outputs DIR writes the
+logits of the last timed step as DIR/logits.npy (float32); inputs and weights are seeded, identical from run to run.
 """
 import argparse
 import gc
@@ -169,10 +174,12 @@ def cpu_baseline_clip(seed, threads, budget_s=30.0, adaptive=False):
                        f"(batch 8 and batch 1 at {threads} threads, batch 1 at 1 thread) after warm-up; value = best of the {threads}-thread runs")
 
 
-def run_step_workload(pkg, dev, streams, cycles, warm_cycles, rank, world, parallel, dist, shards=1, native_plan=True, fpl=4, use_dist=None):
+def run_step_workload(pkg, dev, streams, cycles, warm_cycles, rank, world, parallel, dist, shards=1, native_plan=True, fpl=4, use_dist=None,
+                      outputs=None):
     """CoST-GCN online inference: `streams` concurrent streams per GPU, persistent ring-buffer state; one
     cycle = 4 consecutive frames (the stack's stride pattern) = one prediction per stream.  With shards > 1 the
-    stream axis is split into independent shards advanced on separate HIP streams (parallel.StreamShards)."""
+    stream axis is split into independent shards advanced on separate HIP streams (parallel.StreamShards).
+    `outputs` (a dict): receives the logits of the last timed cycle under "logits"."""
     use_dist = world > 1 if use_dist is None else use_dist
 
     def make():
@@ -211,6 +218,8 @@ def run_step_workload(pkg, dev, streams, cycles, warm_cycles, rank, world, paral
         lt.enabled = False
         tcn_ms, n_launch = lt.total_ms(), len(lt.records)
     assert out is not None and out.shape == (streams * world, NTU["classes"]) and bool(torch.isfinite(out).all())
+    if outputs is not None:
+        outputs["logits"] = out.float().cpu()
     return dt, tcn_ms, n_launch, (eng.state_bytes(), eng.scratch_bytes())
 
 
@@ -490,6 +499,21 @@ def load_traffic(name="traffic_tcn_stage.json", batch=None, streams=None):
     return d
 
 
+def dump_outputs(out_dir, arrays, budget_bytes=64 << 20):
+    """Write each tensor of `arrays` as out_dir/<name>.npy in float32.  Past `budget_bytes` in all, every array keeps a fixed
+    seeded sample of its rows (the same rows on every run of the same shape)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(t.numel() * 4 for t in arrays.values())
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if total > budget_bytes and a.shape[0] > 1:
+            keep = max(1, int(a.shape[0] * budget_bytes / total))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))
+            a = a[rows]
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def self_launch(n):
     """`python bench.py --gpus N` (N > 1) started WITHOUT a launcher: this process becomes the parent of N fresh rank
     processes (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <same arguments>`, one rank per
@@ -576,6 +600,11 @@ def main():
     ap.add_argument("--clip-latency-forwards", type=int, default=200, help="forwards timed per batch size and mode by the clip latency leg")
     ap.add_argument("--cpu-budget", type=float, default=50.0, help="seconds of CPU work the configs[1]/[2] cpu_baseline legs may take in all")
     ap.add_argument("--cpu-budget-config4", type=float, default=14.0, help="seconds of CPU work for the two configs[3] cpu_baseline legs")
+    ap.add_argument("--full", action="store_true",
+                    help="run every leg beside the headline (CPU baselines, bf16x3, latency, configs[4] shard, online workload "
+                         "with --workload both, configs[3]); a plain run times the headline workload only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the logits of the headline's last timed step to DIR/logits.npy (float32)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -609,9 +638,11 @@ def main():
     pkg = _bootstrap.load()
     from continual_skeletons_amd import parallel
 
-    do_clip, do_step = args.workload in ("both", "clip"), args.workload in ("both", "step")
+    # the headline is the clip workload ('both', 'clip') or the online one ('step'); 'both' adds the online leg with --full only
+    do_clip = args.workload in ("both", "clip")
+    do_step = args.workload == "step" or (args.workload == "both" and args.full)
     cpu = cpu_step = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         host_threads = host_cpu_threads()                   # one thread count for both legs
         if do_clip:
             cpu = cpu_baseline_clip(seed=0, threads=host_threads, budget_s=0.6 * args.cpu_budget)
@@ -654,6 +685,7 @@ def main():
         return len({r["device_uuid"] for r in rows})
 
     line = None
+    outputs = None               # the headline's last timed step: {"logits": tensor}
     B = args.batch
 
     def clip_leg(batch, steps, warmup, seed0=100, precision="f32", info=None):
@@ -693,6 +725,7 @@ def main():
         assert out.shape == (batch * world, NTU["classes"]) and bool(torch.isfinite(out).all())
         if info is not None:
             info["local_ms_per_step"] = dt / steps * 1e3           # this rank's own clock (per_rank table)
+            info["logits"] = out.float().cpu()                     # what the last timed step returned (all ranks' clips)
         dt = max_over_ranks(dt)
         if info is not None and precision != "f32":
             got = net(x)
@@ -742,7 +775,8 @@ def main():
             "cpu_baseline": cpu,
             "ranks_seen": ranks_seen(per_rank), "per_rank": per_rank, "collective_backend": backend if use_dist else None,
         }
-        if not args.no_split_leg:
+        outputs = {"logits": inf1["logits"]}
+        if args.full and not args.no_split_leg:
             # OPT-IN precision mode "bf16x3" (csrc/tcn_split.hip): the same workload with the temporal conv on the bf16 matrix
             # pipe (fp32 operands split into 3 bf16 pieces, 6 piece products, fp32 accumulation).  NOT the headline and NOT
             # fp32: its own key, its own dtype, priced both ways.
@@ -762,9 +796,9 @@ def main():
                               "note": "6 bf16 MFMA products per fp32 product: executed FLOPs = 6 x the fp32-equivalent; peak 2.5 PFLOP/s dense bf16"},
                 "fp32_path_tcn_stage_avg_launch_ms": round(avg_launch_s * 1e3, 4),
                 "scope": "clip kernels only (csk_tcn_stage_bf16x3, csk_gcn_stage_bf16x3); the continual step kernels stay exact fp32 (DESIGN.md)"}
-        if world == 1 and not args.no_clip_latency_leg:
+        if args.full and world == 1 and not args.no_clip_latency_leg:
             line["clip_latency"] = run_clip_latency(pkg, dev, cpu, forwards=args.clip_latency_forwards)
-        if use_dist or not args.no_config5_leg:
+        if args.full and (use_dist or not args.no_config5_leg):
             # BASELINE.json configs[4]: batch 8192 over 8 GPUs = 1024 clips per GPU + the RCCL logit all-gather.  Reported
             # beside the 256 / GPU weak-scaling headline (which stays comparable with the N = 1 line); at N = 8 this IS
             # configs[4], at other N the same per-GPU shard (N = 1: one rank's shard, no collective).
@@ -791,25 +825,43 @@ def main():
                 "roofline_config": workmodel.roofline_config(f5a * world, f5y * world, dt5 / steps5, f5e * world, n_gpus=world)}
 
     if do_step:
-        sdt, stcn_ms, sn, sbytes = run_step_workload(pkg, dev, args.streams, args.step_cycles, 2, rank, world, parallel, dist, args.stream_shards, fpl=args.frames_per_launch, use_dist=use_dist)
+        step_out = {}
+        sdt, stcn_ms, sn, sbytes = run_step_workload(pkg, dev, args.streams, args.step_cycles, 2, rank, world, parallel, dist, args.stream_shards, fpl=args.frames_per_launch, use_dist=use_dist,
+                                                     outputs=step_out)
+        if line is None:          # --workload step: the online leg is the headline, its logits are the outputs
+            outputs = step_out
         sdt_local = sdt
         sdt = max_over_ranks(sdt)
-        # kernel-level timing: launches must not overlap and must go through the Python hook -> short single-shard pass
-        gc.collect()                 # engines hold reference cycles (state-dict hooks); free their slabs now
-        torch.cuda.empty_cache()
-        kcycles = max(1, args.kernel_cycles)
-        _, stcn_ms, sn, _ = run_step_workload(pkg, dev, args.streams, kcycles, 1, rank, world, parallel, dist, 1, native_plan=False, use_dist=use_dist)
-        # the timed launches are the tcn_step_kernel launches of a cycle: blocks 5-10 (blocks 1-4, C_out = 64, advance with
-        # the fused csk_co_block_step_f32 launch, which does not go through the hook)
-        step_layers = [l for l in workmodel.step_layers(4) if l["co"] > 64]
-        tfl = 2.0 * args.streams * NTU["M"] * sum(l["tcn_macs"] for l in step_layers)
-        assert sn == kcycles * len(step_layers), (sn, len(step_layers))
         fps = args.frames_per_launch * args.streams * world * args.step_cycles / sdt
-        ach = tfl * kcycles / (stcn_ms / 1e3) / 1e12 if stcn_ms > 0 else 0.0
-        straffic = load_traffic("traffic_tcn_step.json", streams=args.streams)
         sfa, sfe, sby = workmodel.step_totals(args.streams * NTU["M"], args.frames_per_launch)   # per rank and cycle
+        step_roofline = None
+        if args.full:
+            # kernel-level timing: launches must not overlap and must go through the Python hook -> short single-shard pass
+            gc.collect()                 # engines hold reference cycles (state-dict hooks); free their slabs now
+            torch.cuda.empty_cache()
+            kcycles = max(1, args.kernel_cycles)
+            _, stcn_ms, sn, _ = run_step_workload(pkg, dev, args.streams, kcycles, 1, rank, world, parallel, dist, 1, native_plan=False, use_dist=use_dist)
+            # the timed launches are the tcn_step_kernel launches of a cycle: blocks 5-10 (blocks 1-4, C_out = 64, advance with
+            # the fused csk_co_block_step_f32 launch, which does not go through the hook)
+            step_layers = [l for l in workmodel.step_layers(4) if l["co"] > 64]
+            tfl = 2.0 * args.streams * NTU["M"] * sum(l["tcn_macs"] for l in step_layers)
+            assert sn == kcycles * len(step_layers), (sn, len(step_layers))
+            ach = tfl * kcycles / (stcn_ms / 1e3) / 1e12 if stcn_ms > 0 else 0.0
+            straffic = load_traffic("traffic_tcn_step.json", streams=args.streams)
+            step_roofline = {"bound": "mfma", "kernel": "tcn_step16_kernel", "achieved": round(ach, 2), "peak": PEAK_F32_MFMA_TFLOPS,
+                             "unit": "TFLOP/s", "frac": round(ach / PEAK_F32_MFMA_TFLOPS, 6), "launches_timed": sn,
+                             "avg_launch_ms": round(stcn_ms / max(1, sn), 4),
+                             "flops_per_launch": tfl / len(step_layers),
+                             "timing": "single stream shard, launches driven from Python with HIP events around every "
+                                       f"csk_tcn_step_f32 launch (tcn_step16_kernel; blocks 5-10 -- blocks 1-4 advance through the fused block / "
+                                       f"stack entry points) of {kcycles} cycles of "
+                                       "4 frames: the launch shape of tools/online_pass.py --shards 1, whose rocprofv3 per-layer "
+                                       "table is profiles/r06_online_1shard.md (rows L5-L10 tcn_step)",
+                             "traffic": straffic["hbm_bytes_per_launch"] if straffic else None,
+                             "traffic_source": (f"{straffic.get('source')} (committed PMC passes, not collected by this run)")
+                             if straffic else "no committed PMC pass at this stream count"}
         thr = None
-        if args.frames_per_launch != 8:      # throughput mode: two stride cycles per launch (adds 4 frames of latency)
+        if args.full and args.frames_per_launch != 8:      # throughput mode: two stride cycles per launch (adds 4 frames of latency)
             gc.collect()
             torch.cuda.empty_cache()
             tdt, _, _, _ = run_step_workload(pkg, dev, args.streams, args.step_cycles, 2, rank, world, parallel, dist,
@@ -823,21 +875,10 @@ def main():
                      "unit": "frames/s", "streams_per_gpu": args.streams, "stream_shards": args.stream_shards, "frames_per_launch": args.frames_per_launch, "ms_per_frame_step": round(sdt / args.step_cycles / args.frames_per_launch * 1e3, 4),
                      "predictions_per_s": round(fps / 4, 1), "state_slab_GB_per_gpu": round(sbytes[0] / 1e9, 3),
                      "split_k_scratch_GB_per_gpu": round(sbytes[1] / 1e9, 3),
-                     "roofline": {"bound": "mfma", "kernel": "tcn_step16_kernel", "achieved": round(ach, 2), "peak": PEAK_F32_MFMA_TFLOPS,
-                                  "unit": "TFLOP/s", "frac": round(ach / PEAK_F32_MFMA_TFLOPS, 6), "launches_timed": sn,
-                                  "avg_launch_ms": round(stcn_ms / max(1, sn), 4),
-                                  "flops_per_launch": tfl / len(step_layers),
-                                  "timing": "single stream shard, launches driven from Python with HIP events around every "
-                                            f"csk_tcn_step_f32 launch (tcn_step16_kernel; blocks 5-10 -- blocks 1-4 advance through the fused block / "
-                                            f"stack entry points) of {kcycles} cycles of "
-                                            "4 frames: the launch shape of tools/online_pass.py --shards 1, whose rocprofv3 per-layer "
-                                            "table is profiles/r06_online_1shard.md (rows L5-L10 tcn_step)",
-                                  "traffic": straffic["hbm_bytes_per_launch"] if straffic else None,
-                                  "traffic_source": (f"{straffic.get('source')} (committed PMC passes, not collected by this run)")
-                                  if straffic else "no committed PMC pass at this stream count"},
+                     "roofline": step_roofline,
                      "roofline_config": workmodel.roofline_config(sfa * world, sby * world, sdt / args.step_cycles, sfe * world, n_gpus=world),
                      "throughput_mode": thr, "cpu_baseline": cpu_step, "config": "BASELINE.json configs[2]"}
-        if world == 1 and not args.no_latency_leg:
+        if args.full and world == 1 and not args.no_latency_leg:
             gc.collect()
             torch.cuda.empty_cache()
             step_info["latency"] = run_latency(pkg, dev, cpu_step, frames=args.latency_frames)
@@ -851,7 +892,7 @@ def main():
                     "latency": step_info.get("latency")}
         else:
             line["costgcn_online"] = step_info
-    if do_clip and do_step and world == 1:          # BASELINE.json configs[3] beside the headline numbers (per GPU)
+    if args.full and do_clip and do_step and world == 1:          # BASELINE.json configs[3] beside the headline numbers (per GPU)
         gc.collect()
         torch.cuda.empty_cache()
         line["agcn_kinetics"] = run_config4(pkg, dev, parallel, batch=args.config4_batch, streams=args.config4_streams,
@@ -867,6 +908,8 @@ def main():
     bad = use_dist and backend == "nccl" and line["ranks_seen"] != world
     if bad:
         line["error"] = f"ranks_seen {line['ranks_seen']} != n_gpus {world}: ranks share a device; this line is INVALID"
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, outputs)
     if rank == 0:
         print(json.dumps(line))
     if use_dist:

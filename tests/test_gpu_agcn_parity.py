@@ -131,6 +131,9 @@ def test_agcn_block_clip_and_continual(graph, c):
     (per-frame attention) against the oracle's continual block built on adaptive_graph_conv.  (c = 64: the fused embedding +
     attention launch on the Kinetics graph; the NTU graph keeps the two-launch route and gcn_stage_dense2_kernel<.., 25>.)"""
     A_KIN = pkg.kinetics_graph().A if graph == "kinetics" else pkg.ntu_graph().A
+    # _randomise leaves the conv weights at the constructor's init: seed the global RNG that draws them, so that the fixture does not
+    # depend on the tests that ran before (unseeded, |want| reached 32.3 > REF_CAP on one run)
+    torch.manual_seed(3)
     blk = pkg.SpatioTemporalBlock(c, c, A_KIN, GraphConv=pkg.AdaptiveGraphConvolution).eval()
     _randomise(blk, 3)
     sd = {k: v.clone() for k, v in blk.state_dict().items()}

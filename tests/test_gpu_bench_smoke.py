@@ -1,10 +1,12 @@
 """bench.py end to end at toy sizes: one JSON line with the contract's keys (metric, value, unit, n_gpus, steps,
-warmup, ms_per_step, higher_is_better, scaling, vs_baseline, dtype, data, config.workload, roofline, cpu_baseline)."""
+warmup, ms_per_step, higher_is_better, scaling, vs_baseline, dtype, data, config.workload, roofline, cpu_baseline); every
+leg with --full, the headline alone in a plain run, whose --dump-outputs logits repeat bit for bit."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -22,7 +24,7 @@ def _run(*args):
 
 @pytest.mark.parametrize("workload", ["clip", "step", "both"])
 def test_bench_line_contract(workload):
-    d = _run("--workload", workload, "--batch", "4", "--streams", "8", "--steps", "2", "--warmup", "1", "--step-cycles", "2",
+    d = _run("--full", "--workload", workload, "--batch", "4", "--streams", "8", "--steps", "2", "--warmup", "1", "--step-cycles", "2",
              "--stream-shards", "2", "--cpu-budget", "6", "--config4-batch", "2", "--config4-streams", "6",
              "--cpu-budget-config4", "4", "--latency-frames", "12", "--config5-batch", "6", "--clip-latency-forwards", "6",
              "--kernel-cycles", "2")
@@ -70,3 +72,33 @@ def test_bench_line_contract(workload):
         for e in lat["per_stream_count"]:
             assert 0 < e["ms_per_frame_p50"] <= e["ms_per_frame_p99"] and e["launches_per_frame"] > 10 and e["predictions"] == 3
         assert lat["cpu_oracle_ms_per_frame_one_stream"] > 0
+
+
+FULL_ONLY = ("clip_bf16x3", "clip_latency", "config5", "costgcn_online", "agcn_kinetics")
+
+
+def test_plain_run_times_the_headline_only_and_dumps_its_logits(tmp_path):
+    """A plain run: --steps timed clip forwards and nothing else (no CPU baseline, no side legs); --dump-outputs writes the
+    logits of the last timed step, and a second run with the same arguments writes the same array bit for bit."""
+    dumps = []
+    for run in range(2):
+        out_dir = tmp_path / f"run{run}"
+        d = _run("--batch", "4", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out_dir))
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+        assert d["unit"] == "clips/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert abs(d["value"] - 4 * 1e3 / d["ms_per_step"]) <= 1e-2 * d["value"]
+        assert d["cpu_baseline"] is None and not any(k in d for k in FULL_ONLY), sorted(d)
+        assert sorted(os.listdir(out_dir)) == ["logits.npy"]
+        a = np.load(out_dir / "logits.npy")
+        assert a.dtype == np.float32 and a.shape == (4, 60) and np.isfinite(a).all()
+        dumps.append(a)
+    assert np.array_equal(dumps[0], dumps[1])
+
+
+def test_plain_step_workload_dumps_the_online_logits(tmp_path):
+    """--workload step: the online leg is the headline; a plain run skips its kernel-timing, throughput and latency passes."""
+    d = _run("--workload", "step", "--streams", "6", "--step-cycles", "2", "--dump-outputs", str(tmp_path))
+    assert d["steps"] == 2 and d["unit"] == "frames/s" and d["value"] > 0 and d["ms_per_step"] > 0
+    assert d["roofline"] is None and d["latency"] is None and d["cpu_baseline"] is None
+    a = np.load(tmp_path / "logits.npy")
+    assert a.dtype == np.float32 and a.shape == (6, 60) and np.isfinite(a).all()

@@ -133,7 +133,7 @@ def test_errors_are_loud():
         m.to(DEV)(torch.rand(1, 4, 20, 25, device=DEV).double())
 
 
-def test_general_gcn_kernel_matches_sparse_fast_path():
+def test_general_gcn_kernel_matches_sparse_fast_path(tmp_path):
     """The dense-capable GCN kernel (used for A-GCN / arbitrary adjacencies) and the sparse-graph fast path must
     agree on a skeleton graph; run the general one in a subprocess (diagnostic switch is read at library load)."""
     import os
@@ -147,7 +147,7 @@ def test_general_gcn_kernel_matches_sparse_fast_path():
     ) % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     outs = []
     for general in (False, True):
-        path = f"/tmp/gcn_{int(general)}.pt"
+        path = str(tmp_path / f"gcn_{int(general)}.pt")
         env = dict(os.environ)
         env.pop("CSK_DIAG", None)
         if general:
@@ -157,7 +157,7 @@ def test_general_gcn_kernel_matches_sparse_fast_path():
     check_parity(outs[0], outs[1], tol=1e-5, note="general vs sparse GCN kernel")
 
 
-def test_tile_families_are_bitwise_interchangeable():
+def test_tile_families_are_bitwise_interchangeable(tmp_path):
     """The 16x16x4 tile family (csrc/tcn16.hip, csrc/step16.hip:gcn16_kernel) stands in for the 32x32x2 kernels where a launch
     shape favours it, on the claim that both walk the K loop in the same (chunk, tap / subset, channel) order and that
     v_mfma_f32_16x16x4_f32 is the same fmaf chain: stride-1 blocks (identity and conv residual, 64 and 128 channels) and a
@@ -178,7 +178,7 @@ def test_tile_families_are_bitwise_interchangeable():
     ) % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     res = []
     for mode in ("2", "1"):
-        path = f"/tmp/tile16_{mode}.pt"
+        path = str(tmp_path / f"tile16_{mode}.pt")
         env = dict(os.environ, CSK_DIAG="1", CSK_TCN16=mode, CSK_GCN16=mode)
         subprocess.check_call([sys.executable, "-c", code, path], env=env)
         res.append(torch.load(path))

@@ -151,7 +151,7 @@ def test_costgcn_logits_vs_oracle_and_forward_modes():
 
 
 def test_costgcn_top3_equals_stgcn_default_init_default_pool():
-    """Mirror of the reference's one model-level pin, /root/reference/tests/test_cost_gcn.py:329-362: StGcn and CoStGcn
+    """Mirror of the reference's one model-level pin, its tests/test_cost_gcn.py:329-362: StGcn and CoStGcn
     with the constructors' DEFAULT initialisation (gcn.bn.weight = 1e-6, base.py:257) and the DEFAULT pool (75 / 19),
     weights transferred with ``co.load_state_dict(co.map_state_dict(reg.state_dict()))``; on a dummy_ntu sample
     (torch.rand, datasets/datasets.py:301) the top-3 classes of ``reg(sample)``, ``co.forward(sample)`` and

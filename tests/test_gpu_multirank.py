@@ -98,7 +98,7 @@ def test_two_ranks_share_the_gpu_sharded_equals_unsharded(tmp_path):
 def test_bench_two_ranks_toy_sizes():
     env = dict(os.environ, CSK_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "3", "--streams", "6",
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--batch", "3", "--streams", "6",
            "--steps", "2", "--warmup", "1", "--step-cycles", "2", "--stream-shards", "2", "--no-cpu-baseline",
            "--config5-batch", "4"]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
@@ -131,7 +131,7 @@ def test_bench_self_launch_two_ranks_toy_sizes():
     env = dict(os.environ, CSK_BENCH_BACKEND="gloo")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "4", "--streams", "6", "--steps", "2",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--batch", "4", "--streams", "6", "--steps", "2",
            "--warmup", "1", "--step-cycles", "2", "--stream-shards", "2", "--no-cpu-baseline", "--config5-batch", "3",
            "--no-split-leg"]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
@@ -153,7 +153,7 @@ def test_bench_self_launch_eight_ranks_toy_sizes():
     env = dict(os.environ, CSK_BENCH_BACKEND="gloo")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--batch", "2", "--streams", "4", "--steps", "2",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "8", "--batch", "2", "--streams", "4", "--steps", "2",
            "--warmup", "1", "--step-cycles", "2", "--stream-shards", "1", "--no-cpu-baseline", "--config5-batch", "2",
            "--no-split-leg"]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
@@ -235,7 +235,7 @@ def test_bench_one_rank_rccl_toy_sizes():
     max-over-ranks all_reduce, logit all-gather, config5 leg) on one rank."""
     env = dict(os.environ, CSK_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--batch", "3", "--streams", "6",
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--batch", "3", "--streams", "6",
            "--steps", "2", "--warmup", "1", "--step-cycles", "2", "--stream-shards", "2", "--no-cpu-baseline",
            "--config5-batch", "4"]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
@@ -254,7 +254,7 @@ def test_bench_fails_the_line_when_rccl_ranks_share_a_device():
     2-GPU line may come out of a 1-GPU box."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", CSK_BENCH_SAME_DEVICE="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "2", "--streams", "4",
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--batch", "2", "--streams", "4",
            "--steps", "1", "--warmup", "1", "--step-cycles", "1", "--no-cpu-baseline", "--workload", "clip", "--no-split-leg",
            "--config5-batch", "2"]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)

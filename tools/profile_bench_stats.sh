@@ -1,6 +1,6 @@
 #!/usr/bin/env bash
-# Run ON THE GPU BOX (via gpurun): `rocprofv3 --kernel-trace --stats` of the DEFAULT bench command (python3 bench.py, CPU baseline
-# legs skipped) -> profiles-ready markdown gpurun_out/prof_<tag>/bench_stats.md: rocprofv3's own per-kernel summary next to the
+# Run on a GPU machine: `rocprofv3 --kernel-trace --stats` of the whole bench run (python3 bench.py --full, CPU baseline
+# legs skipped) -> profiles-ready markdown prof_<tag>/bench_stats.md in the output folder below: rocprofv3's own per-kernel summary next to the
 # JSON line the same run printed (whose roofline.avg_launch_ms must agree with the tcn_stage_kernel rows).
 # usage: bash tools/profile_bench_stats.sh <tag>
 set -uo pipefail
@@ -9,7 +9,7 @@ R="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 out="$R/gpurun_out/prof_$tag"
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$out/bench" -- python3 "$R/bench.py" --no-cpu-baseline > "$out/bench.log" 2> "$out/bench.err"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$out/bench" -- python3 "$R/bench.py" --full --no-cpu-baseline > "$out/bench.log" 2> "$out/bench.err"
 python3 - "$out" "$tag" <<'PY'
 import csv, glob, json, sys
 out = sys.argv[1]
@@ -17,7 +17,7 @@ f = sorted(glob.glob(f"{out}/bench/**/*kernel_stats.csv", recursive=True))[-1]
 rows = list(csv.DictReader(open(f)))
 line = [ln for ln in open(f"{out}/bench.log") if ln.startswith("{")][-1]
 d = json.loads(line)
-L = ["# rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline (whole default run: clip leg, bf16x3 leg, online legs, config 4)", "",
+L = ["# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline (whole run: clip leg, bf16x3 leg, online legs, config 4)", "",
      "| kernel | calls | total ms | average ms | % of GPU time |", "|---|---|---|---|---|"]
 for r in rows[:28]:
     n = r["Name"].replace("(anonymous namespace)::", "")
