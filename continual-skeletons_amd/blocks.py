@@ -341,9 +341,11 @@ class TemporalConvolution(_Folded):
 
 
 def tcn_stage(y, w, bias, c_out, k, stride, pad, relu=True, res_mode=0, x_res=None, w_res=None, res_off=0, out=None,
-              split=False, ksplit=1, scratch=None):
+              split=False, ksplit=1, scratch=None, w_wino=None):
     """csk_tcn_stage_f32, or with split=True csk_tcn_stage_bf16x3 (w / w_res are then the split operand images), or with
-    ksplit > 1 csk_tcn_stage_splitk_f32 (clip latency mode: K loop cut into channel ranges, partial sums in split order)."""
+    ksplit > 1 csk_tcn_stage_splitk_f32 (clip latency mode: K loop cut into channel ranges, partial sums in split order), or
+    with the Winograd image w_wino (fold.pack_conv_weight_wino) csk_tcn_stage_wino_f32 (the Winograd kernel where the layer's
+    shape allows it, csk_tcn_stage_f32 otherwise)."""
     n, c, t_in, v = y.shape
     if t_in + 2 * pad < k:
         raise RuntimeError(f"temporal extent {t_in} (+2*{pad}) shorter than kernel {k}")
@@ -362,6 +364,13 @@ def tcn_stage(y, w, bias, c_out, k, stride, pad, relu=True, res_mode=0, x_res=No
             n, c, c_out, t_in, v, k, stride, pad, res_mode, c_res, t_res, res_off, int(relu), ksplit, native.ptr(part),
             native.stream_of(y))
         native.check(rc, "csk_tcn_stage_splitk_f32")
+        return out
+    if w_wino is not None and not split:
+        rc = native.lib().csk_tcn_stage_wino_f32(
+            native.ptr(y), native.ptr(w), native.ptr(x_res), native.ptr(w_res), native.ptr(bias), native.ptr(out),
+            n, c, c_out, t_in, v, k, stride, pad, res_mode, c_res, t_res, res_off, int(relu), native.ptr(w_wino),
+            native.stream_of(y))
+        native.check(rc, "csk_tcn_stage_wino_f32")
         return out
     fn = native.lib().csk_tcn_stage_bf16x3 if split else native.lib().csk_tcn_stage_f32
     rc = fn(native.ptr(y), native.ptr(w), native.ptr(x_res), native.ptr(w_res), native.ptr(bias), native.ptr(out),
@@ -438,7 +447,7 @@ class SpatioTemporalBlock(_Folded):
         ks = max(1, min(self.clip_split_k, -(-ops["c"] // 8))) if (self.clip_split_k > 1 and ops["k"] == 9 and y.shape[0] <= self.clip_split_max_seq) else 1
         return tcn_stage(y, ops["w"], ops["bias"], ops["c_out"], ops["k"], self.stride, self.tcn.padding, relu=True,
                          res_mode=mode, x_res=xr, w_res=ops["w_res"], res_off=shrink, out=out, ksplit=ks,
-                         scratch=_scratch_of(self) if ks > 1 else None)
+                         scratch=_scratch_of(self) if ks > 1 else None, w_wino=ops["w_wino"] if ks == 1 else None)
 
 
 def _few_channels_fusable(self, x) -> bool:

@@ -1,0 +1,245 @@
+// tcn_wino.hip -- the clip temporal conv of the identity-residual blocks (csk_tcn_stage_wino_f32) by Winograd minimal filtering:
+// the 9 x 1 conv (stride 1, pad 4) as three 3-tap groups, each computed with F(2, 3) -- two output frames from four input frames,
+// interpolation points 0, 1, -1, inf -- and the groups summed in the transformed domain, so that one output transform serves all
+// three.  Per output frame pair and channel the matrix pipe runs 12 K-blocks instead of 18: 1.5x fewer fp32 MFMA FLOPs for the
+// same conv, all arithmetic still fp32 (no reduced-precision operand anywhere).
+//
+//   weights (host, fold.pack_conv_weight_wino):  U[4 g + i][c][co] = (G . w[3 g .. 3 g + 2][c][co])[i], fp64, rounded once
+//            G = [1 0 0; 1/2 1/2 1/2; 1/2 -1/2 1/2; 0 0 1]
+//   input  (per K step, in registers):  d = y[c][2 j + 3 g - 4 .. 2 j + 3 g - 1][v]  ->  (d0 - d2, d1 + d2, d2 - d1, d1 - d3)
+//   GEMMs:  M_i[co][(j, v)] = sum_g sum_c U[4 g + i][c][co] * B_{g,i}[c][(j, v)]          four accumulator sets, i = 0..3
+//   output (epilogue, lane-local):  out(2 j) = M0 + M1 + M2,  out(2 j + 1) = M1 - M2 - M3;  + bias + identity residual, ReLU
+//
+// GEMM view: the columns are (output frame pair j, joint v) flattened, V innermost -- the address arithmetic of a stride-2 conv:
+// column (j, v) reads raw frame 2 j + s - 4 at LDS offset 2 (j - ja) V + v + s V, s = 0..9 (s = 3 g + f, f = 0..3).  One raw
+// activation chunk in LDS serves the 12 (group, point) products; the transform is 4 VALU ops per 8 MFMAs.
+// Tiling: 256 threads = 4 waves, workgroup tile 64 output channels x 128 pair columns; a wave owns all 64 channels x 32 pair
+// columns per point (2 x 1 MFMA 32x32x2 accumulators per point, 8 in all = 128 registers), two workgroups per CU.
+// K loop: 8-channel chunks as in tcn_stage_kernel (tcn.hip), the next chunk's loads trickled in three thirds in front of the
+// three group segments.  The weights stream from the host-transformed image, the staging types are those of mfma_core.h.
+// T odd: the last pair's second frame (t = T) is computed from zero padding and not stored.
+#include "mfma_core.h"
+#include "tcn_params.h"
+
+namespace {
+
+constexpr int WMT = 64;        // output channels per workgroup tile
+constexpr int WNT = 128;       // pair columns per workgroup tile (32 per wave)
+constexpr int WTAPS = 12;      // (group, point) products per channel
+
+// LDS row of one staged channel: the raw frames 2 ja - 4 .. 2 jb + 5 of a tile whose pair columns span pairs ja .. jb
+template <int VT>
+constexpr int wino_ldb() { return ((2 * ((WNT + VT - 2) / VT) + 10) * VT + 3) / 4 * 4; }
+
+// Weight staging of a 12-tap chunk of the 64-row tile: 12 * KC * 16 = 1536 f32x4 = 6 per thread; slot u of a thread is tap
+// 2 u + tid / 128, channel row (tid / 16) % 8, rows 4 (tid % 16) .. -- the offsets of the slots differ by wave-uniform constants
+// (the layout of WStage9x64 in mfma_core.h, all six slots whole)
+struct WStage12x64 {
+    unsigned goff0, loff0, gstride;
+    f32x4 v[6];
+    __device__ __forceinline__ void setup(int Cpad, int Mpad, int tid) {
+        goff0 = (unsigned)(((tid >> 7) * Cpad + ((tid >> 4) & 7)) * Mpad + (tid & 15) * 4);
+        loff0 = (unsigned)(tid * 4);
+        gstride = (unsigned)(2 * Cpad * Mpad);
+    }
+    __device__ __forceinline__ void issue_slot(int u, const float *__restrict__ chunk_base) {
+        v[u] = *reinterpret_cast<const f32x4 *>(chunk_base + (size_t)u * gstride + goff0);
+    }
+    __device__ __forceinline__ void issue(const float *__restrict__ chunk_base) {
+#pragma unroll
+        for (int u = 0; u < 6; ++u) issue_slot(u, chunk_base);
+    }
+    __device__ __forceinline__ void commit(float *__restrict__ Wl) const {
+#pragma unroll
+        for (int u = 0; u < 6; ++u) *reinterpret_cast<f32x4 *>(Wl + u * (NTHREADS * 4) + loff0) = v[u];
+    }
+};
+
+// One group segment of a chunk for one wave: acc[i][mi] += U[4 g + i][kk][rows mi] x B_{g,i}[kk][this lane's column]
+template <int VT, int G>
+__device__ __forceinline__ void wino_group(const float *__restrict__ Wl, const float *__restrict__ Bl, int off, int l31, int kh,
+                                           f32x16 (&acc)[4][2]) {
+    constexpr int LDB = wino_ldb<VT>();
+    const float *br = Bl + kh * LDB + off + 3 * G * VT;
+    const float *wr = Wl + 4 * G * (KC * WMT) + kh * WMT + l31;
+#pragma unroll
+    for (int s = 0; s < KC / 2; ++s) {
+        const float d0 = br[2 * s * LDB], d1 = br[2 * s * LDB + VT], d2 = br[2 * s * LDB + 2 * VT], d3 = br[2 * s * LDB + 3 * VT];
+        const float b[4] = {d0 - d2, d1 + d2, d2 - d1, d1 - d3};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float a0 = wr[i * (KC * WMT) + 2 * s * WMT], a1 = wr[i * (KC * WMT) + 2 * s * WMT + 32];
+            acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b[i], acc[i][0], 0, 0, 0);
+            acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b[i], acc[i][1], 0, 0, 0);
+        }
+    }
+}
+
+}  // namespace
+
+// p.Tout = T (frames in and out), p.nt = pair columns per segment ((T + 1) / 2 * V), p.w = the transformed weight image
+template <int VT>
+__global__ __launch_bounds__(NTHREADS, 2) void tcn_stage_wino_kernel(const TcnParams p) {
+    constexpr int LDB = wino_ldb<VT>();
+    constexpr int NJ = (LDB + 63) / 64;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float *Wl = smem;
+    float *Bl = smem + WTAPS * KC * WMT;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l31 = lane & 31, kh = lane >> 5;
+    // work item -> (m-tile fastest: shares the activation tile; then column tile; then segment)
+    const unsigned wid = xcd_contiguous_id(blockIdx.x, gridDim.x);
+    const int m0 = (int)(wid % p.mtiles) * WMT, q0 = (int)((wid / p.mtiles) % p.qtiles) * WNT;
+    const int seg = (int)(wid / (p.mtiles * p.qtiles));
+    const int T = p.Tout, TV = T * VT, QP = p.nt;
+    const int qend = min(q0 + WNT, QP);
+    const int ja = div_magic(q0, p.vmagic), jb = div_magic(qend - 1, p.vmagic);
+
+    // this lane's pair column (clamped into the tile; lanes past its end compute a copy of the last column and store nothing)
+    const int qc = min(q0 + wave * 32 + l31, qend - 1);
+    const int jc = div_magic(qc, p.vmagic), vc = qc - jc * VT;
+    const int off = 2 * (jc - ja) * VT + vc;
+
+    f32x16 acc[4][2];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+            for (int g = 0; g < 16; ++g) acc[i][mi][g] = 0.f;
+
+    {
+        const int fa = 2 * ja - 4;                                   // first raw frame of the tile (pad 4)
+        const int span = (2 * (jb - ja) + 10) * VT;
+        const int64_t cs = (int64_t)TV;
+        const float *seg_base = p.y + (int64_t)seg * p.C * cs;       // 64-bit segment base; 32-bit offsets inside it
+        const float *wbase = p.w + m0;
+        WStage12x64 ws;
+        ws.setup(p.Cpad, p.Mpad, tid);
+        auto kloop = [&](auto &bx) {
+            ws.issue(wbase);
+            bx.issue(seg_base, p.C, cs, 0, wave);
+            for (int c0 = 0; c0 + KC < p.Cpad; c0 += KC) {
+                __syncthreads();                     // previous chunk's LDS reads are done
+                ws.commit(Wl);
+                bx.commit(Bl, LDB, wave);
+                __syncthreads();
+                const float *wnext = wbase + (size_t)(c0 + KC) * p.Mpad;
+                const int cn = c0 + KC;
+                ws.issue_slot(0, wnext);
+                ws.issue_slot(1, wnext);
+                bx.template issue_third<0>(seg_base, p.C, cs, cn, wave);
+                if (p.prio) __builtin_amdgcn_s_setprio(1);
+                wino_group<VT, 0>(Wl, Bl, off, l31, kh, acc);
+                __builtin_amdgcn_s_setprio(0);
+                ws.issue_slot(2, wnext);
+                ws.issue_slot(3, wnext);
+                bx.template issue_third<1>(seg_base, p.C, cs, cn, wave);
+                if (p.prio) __builtin_amdgcn_s_setprio(1);
+                wino_group<VT, 1>(Wl, Bl, off, l31, kh, acc);
+                __builtin_amdgcn_s_setprio(0);
+                ws.issue_slot(4, wnext);
+                ws.issue_slot(5, wnext);
+                bx.template issue_third<2>(seg_base, p.C, cs, cn, wave);
+                if (p.prio) __builtin_amdgcn_s_setprio(1);
+                wino_group<VT, 2>(Wl, Bl, off, l31, kh, acc);
+                __builtin_amdgcn_s_setprio(0);
+            }
+            __syncthreads();                         // peeled last chunk
+            ws.commit(Wl);
+            bx.commit(Bl, LDB, wave);
+            __syncthreads();
+            wino_group<VT, 0>(Wl, Bl, off, l31, kh, acc);
+            wino_group<VT, 1>(Wl, Bl, off, l31, kh, acc);
+            wino_group<VT, 2>(Wl, Bl, off, l31, kh, acc);
+        };
+        // tiles whose staged span lies inside the sequence: 16-byte staging; the others (zero padding at either end) element-wise
+        const bool interior = p.vec_stage && fa >= 0 && fa * VT + 4 * ((span + 3) / 4) <= TV;     // uniform
+        if (interior) {
+            BStage4<(NJ + 3) / 4> b4;
+            b4.setup(fa * VT, span, lane);
+            kloop(b4);
+        } else {
+            BStage<NJ> bs;
+            bs.setup(fa * VT, span, TV, lane);
+            kloop(bs);
+        }
+    }
+
+    // ---- epilogue: output transform, + bias + identity residual, ReLU.  C/D map: column = lane & 31 (this lane's pair column),
+    // row = (g & 3) + 8 (g >> 2) + 4 (lane >> 5).  Row base pointers are wave-uniform (64-bit); a lane adds one 32-bit byte offset
+    // (4 kh rows + its position; T V < 2^26 keeps it below 2^32).  Every tile has all 64 rows (c_out % 64 == 0, host gate).
+    const bool qv = q0 + wave * 32 + l31 < qend;
+    const bool odd_ok = 2 * jc + 1 < T;                              // the pair's second frame exists (T odd: not the last pair)
+    const unsigned p0 = (unsigned)(2 * jc * VT + vc);
+    const unsigned b0 = 4u * (4u * (unsigned)kh * (unsigned)TV + p0);
+    const unsigned b1 = odd_ok ? b0 + 4u * VT : b0;                  // phantom frame: re-read frame 2 j (value unused)
+    const unsigned kh16 = 16u * (unsigned)kh;
+    const float *rseg = p.xres + (int64_t)seg * p.Cout * TV;
+    float *oseg = p.out + (int64_t)seg * p.Cout * TV;
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi) {
+        const int rb = m0 + mi * 32;
+        float o0[16], o1[16];
+#pragma unroll
+        for (int g = 0; g < 16; ++g) {
+            const int row = rb + (g & 3) + 8 * (g >> 2);
+            const float *rrow = rseg + (int64_t)row * TV;
+            const float bias = ld_lane(p.bias + row, kh16);
+            const float m1 = acc[1][mi][g], m2 = acc[2][mi][g];
+            float v0 = acc[0][mi][g] + m1 + m2 + bias + ld_lane(rrow, b0);
+            float v1 = m1 - m2 - acc[3][mi][g] + bias + ld_lane(rrow, b1);
+            if (p.relu) { v0 = relu_nan(v0); v1 = relu_nan(v1); }
+            o0[g] = v0;
+            o1[g] = v1;
+        }
+        if (qv) {
+#pragma unroll
+            for (int g = 0; g < 16; ++g) {
+                float *orow = oseg + (int64_t)(rb + (g & 3) + 8 * (g >> 2)) * TV;
+                st_lane(orow, b0, o0[g]);
+                if (odd_ok) st_lane(orow, b1, o1[g]);
+            }
+        }
+    }
+}
+
+// -2: the shape is not one the Winograd kernel is built for (the caller runs the direct kernels); 0 / error code otherwise
+static int tcn_stage_wino_launch(const float *y, const float *w_wino, const float *x_res, const float *bias, float *out, int n_seg,
+                                 int c, int c_out, int t_in, int V, int k, int stride, int pad, int res_mode, int c_res, int t_res,
+                                 int res_off, int relu, void *stream) {
+    if (!w_wino || !y || !x_res || !bias || !out) return -2;
+    if (k != 9 || stride != 1 || pad != 4 || res_mode != CSK_RES_IDENTITY || res_off != 0) return -2;
+    if ((V != 25 && V != 18) || c_out % WMT != 0 || c_res != c_out || t_res != t_in || c < 1 || n_seg < 1 || t_in < 1) return -2;
+    if ((int64_t)t_in * V >= (1 << 26)) return -2;                    // 32-bit position / lane byte offsets inside a segment
+    if (csk_diag_flag("CSK_TCN_WINO")) return -2;                     // diagnostic A/B switch: the direct kernels
+    const int qp = (t_in + 1) / 2 * V;
+    const int qtiles = (qp + WNT - 1) / WNT, mtiles = c_out / WMT;
+    if ((int64_t)qtiles * mtiles * n_seg >= (1ll << 31)) return -2;
+    TcnParams p = {};
+    p.y = y; p.w = w_wino; p.xres = x_res; p.wres = nullptr; p.bias = bias; p.out = out;
+    p.C = c; p.Cpad = round_up(c, CSK_CPAD); p.Cout = c_out; p.Mpad = round_up(c_out, CSK_MT);
+    p.Tin = t_in; p.Tout = t_in; p.V = V; p.K = k; p.stride = 1; p.pad = pad;
+    p.res_mode = res_mode; p.Cres = c_res; p.CresPad = round_up(c_res, CSK_CPAD); p.Tres = t_res; p.res_off = 0; p.relu = relu;
+    p.vmagic = vmagic_of(V); p.mtiles = (unsigned)mtiles; p.qtiles = (unsigned)qtiles; p.nt = qp;
+    p.prio = !csk_diag_flag("CSK_NOPRIO");
+    p.vec_stage = !csk_diag_flag("CSK_TCN_NOVEC");
+    void (*kern)(TcnParams) = V == 25 ? tcn_stage_wino_kernel<25> : tcn_stage_wino_kernel<18>;
+    const int ldb = V == 25 ? wino_ldb<25>() : wino_ldb<18>();
+    p.ldb = ldb;
+    const size_t lds = (size_t)(WTAPS * KC * WMT + KC * ldb) * sizeof(float);
+    if (const int e = csk_ensure_lds((const void *)kern, lds)) return e;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(qtiles * mtiles * n_seg)), dim3(NTHREADS), lds, (hipStream_t)stream, p);
+    return (int)hipGetLastError();
+}
+
+extern "C" int csk_tcn_stage_wino_f32(const float *y, const float *w, const float *x_res, const float *w_res, const float *bias,
+                                      float *out, int n_seg, int c, int c_out, int t_in, int V, int k, int stride, int pad,
+                                      int res_mode, int c_res, int t_res, int res_off, int relu, const float *w_wino, void *stream) {
+    const int rc = tcn_stage_wino_launch(y, w_wino, x_res, bias, out, n_seg, c, c_out, t_in, V, k, stride, pad, res_mode, c_res,
+                                         t_res, res_off, relu, stream);
+    if (rc != -2) return rc;
+    return csk_tcn_stage_f32(y, w, x_res, w_res, bias, out, n_seg, c, c_out, t_in, V, k, stride, pad, res_mode, c_res, t_res,
+                             res_off, relu, stream);
+}

@@ -34,6 +34,27 @@ def pack_conv_weight(weight: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
     return out.float().contiguous()
 
 
+# F(2, 3) weight transform (points 0, 1, -1, inf): rows of G
+WINO_G = ((1.0, 0.0, 0.0), (0.5, 0.5, 0.5), (0.5, -0.5, 0.5), (0.0, 0.0, 1.0))
+
+
+def pack_conv_weight_wino(weight: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """(C_out, C_in, 9, 1) conv weight * per-output scale -> the transformed image of csk_tcn_stage_wino_f32 (include/cskel.h),
+    packed [12][C_in_pad][C_out_pad] fp32: element [4 g + i][c][co] = sum_r G[i][r] * W'[co, c, 3 g + r] -- the nine taps as three
+    3-tap groups, each through the F(2, 3) weight transform.  Formed in float64 from the BN-folded weight, rounded to fp32 once."""
+    if weight.dim() == 4:
+        weight = weight[:, :, :, 0]
+    co, ci, k = weight.shape
+    if k != 9:
+        raise ValueError(f"the Winograd image is built for the 9 x 1 temporal conv, got k = {k}")
+    w = weight.double() * scale[:, None, None]                                       # (co, ci, 9)
+    g = torch.tensor(WINO_G, dtype=torch.float64)                                    # (4, 3)
+    u = torch.einsum("ir,ocgr->gico", g, w.view(co, ci, 3, 3)).reshape(12, ci, co)   # [4 g + i][c][co]
+    out = torch.zeros((12, _ceil_to(ci, KC), _ceil_to(co, MT)), dtype=torch.float64)
+    out[:, :ci, :co] = u
+    return out.float().contiguous()
+
+
 SPLIT_KS = 16     # channels per K step of the bf16x3 split kernels (csrc/tcn_split.hip)
 
 
@@ -129,13 +150,15 @@ def fold_graph_conv(sd: Dict[str, torch.Tensor], p: str = "", split: bool = Fals
     return out
 
 
-def fold_temporal_conv(sd: Dict[str, torch.Tensor], p: str = "") -> dict:
-    """Packed weight + bias of a TemporalConvolution (models/base.py:279-304)."""
+def fold_temporal_conv(sd: Dict[str, torch.Tensor], p: str = "", wino: bool = False) -> dict:
+    """Packed weight + bias of a TemporalConvolution (models/base.py:279-304); wino: also the Winograd image ``w_wino``
+    (9-tap convs; None otherwise)."""
     s, t = bn_affine(sd[p + "bn.weight"].cpu(), sd[p + "bn.bias"].cpu(), sd[p + "bn.running_mean"].cpu(),
                      sd[p + "bn.running_var"].cpu())
     wt = sd[p + "t_conv.weight"].detach().cpu()
     bias = s * sd[p + "t_conv.bias"].detach().cpu().double() + t
-    return dict(w=pack_conv_weight(wt, s), bias=bias, c_in=wt.shape[1], c_out=wt.shape[0], k=wt.shape[2])
+    w_wino = pack_conv_weight_wino(wt, s) if wino and wt.shape[2] == 9 else None
+    return dict(w=pack_conv_weight(wt, s), bias=bias, c_in=wt.shape[1], c_out=wt.shape[0], k=wt.shape[2], w_wino=w_wino)
 
 
 def fold_temporal_conv_split(sd: Dict[str, torch.Tensor], p: str = "", stride: int = 1) -> torch.Tensor:
@@ -148,9 +171,11 @@ def fold_temporal_conv_split(sd: Dict[str, torch.Tensor], p: str = "", stride: i
 def fold_block_tail(sd: Dict[str, torch.Tensor], p: str = "", has_conv_residual: Optional[bool] = None,
                     split: bool = False, stride: int = 1) -> dict:
     """Operands of csk_tcn_stage_f32 for a whole SpatioTemporalBlock tail: tcn (+ conv residual).  split: also the
-    bf16x3 operand images ``w_split`` / ``w_res_split`` (precision mode "bf16x3", 9-tap convs only)."""
-    main = fold_temporal_conv(sd, p + "tcn.")
-    out = dict(w=main["w"], k=main["k"], c=main["c_in"], c_out=main["c_out"], w_res=None, c_res=0, w_split=None, w_res_split=None)
+    bf16x3 operand images ``w_split`` / ``w_res_split`` (precision mode "bf16x3", 9-tap convs only).  ``w_wino``: the
+    Winograd image of csk_tcn_stage_wino_f32 for 9-tap stride-1 convs (None otherwise)."""
+    main = fold_temporal_conv(sd, p + "tcn.", wino=stride == 1)
+    out = dict(w=main["w"], k=main["k"], c=main["c_in"], c_out=main["c_out"], w_res=None, c_res=0, w_split=None, w_res_split=None,
+               w_wino=main["w_wino"])
     bias = main["bias"]
     if has_conv_residual is None:
         has_conv_residual = (p + "residual.t_conv.weight") in sd

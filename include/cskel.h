@@ -116,6 +116,23 @@ int csk_tcn_stage_f32(const float *y, const float *w, const float *x_res, const 
                       int res_mode, int c_res, int t_res, int res_off, int relu, void *stream);
 
 /*
+ * csk_tcn_stage_f32 with the 9 x 1 conv evaluated by Winograd minimal filtering where the shape allows (csrc/tcn_wino.hip):
+ * the taps as three 3-tap groups, each an F(2, 3) (two output frames from four input frames, points 0, 1, -1, inf), the groups
+ * summed in the transformed domain -- 12 instead of 18 fp32 MFMA K-blocks per output frame pair.  Exact fp32 arithmetic; the
+ * result differs from csk_tcn_stage_f32 by the rounding of the transformed weights and operands (about 1e-6 relative).
+ * Arguments of csk_tcn_stage_f32 plus
+ *  w_wino   packed [12][c_pad][c_out_pad]: element [4 g + i][c][co] = sum_r G[i][r] * W'[co][c][3 g + r] (g = 0..2, i = 0..3),
+ *           G = {{1, 0, 0}, {1/2, 1/2, 1/2}, {1/2, -1/2, 1/2}, {0, 0, 1}}, formed in fp64 from the BN-folded weight and
+ *           rounded to fp32 once (fold.pack_conv_weight_wino); may be NULL
+ * Taken for k = 9, stride 1, pad 4, an identity residual without shrink (res_off 0, t_res == t_in), V in {25, 18},
+ * c_out % 64 == 0 and w_wino != NULL -- a function of the layer, never of n_seg.  Any other call runs csk_tcn_stage_f32.
+ */
+int csk_tcn_stage_wino_f32(const float *y, const float *w, const float *x_res, const float *w_res,
+                           const float *bias, float *out,
+                           int n_seg, int c, int c_out, int t_in, int V, int k, int stride, int pad,
+                           int res_mode, int c_res, int t_res, int res_off, int relu, const float *w_wino, void *stream);
+
+/*
  * A whole SpatioTemporalBlock with a FEW input channels and no block residual -- layer 1 of the reference's stacks
  * (models/st_gcn/st_gcn.py:30: StGcnBlock(3, 64, A, residual=False); block body models/base.py:376-387) -- in ONE launch:
  *   out = ReLU( tcn( gcn(x) ) ),  gcn(x) = ReLU( sum_k W'_k . (x . A_k) + b' + conv1x1+BN(x) )   (models/base.py:230-270)
