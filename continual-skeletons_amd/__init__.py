@@ -28,6 +28,7 @@ from .continual import (  # noqa: F401
     CoTemporalConvolution,
 )
 from .agcn import AdaptiveGraphConvolution, AGcn, CoAdaptiveGraphConvolution, CoAGcn  # noqa: F401
+from .str import CoSTr, GcnUnitAttention, STr  # noqa: F401
 from . import fusion, native, weights  # noqa: F401
 from .weights import load_pretrained  # noqa: F401
 
@@ -40,6 +41,7 @@ __all__ = [
     "Graph", "ntu_graph", "kinetics_graph", "GraphConvolution", "TemporalConvolution",
     "SpatioTemporalBlock", "SpatialGraphConv", "StGcnBlock", "CoStGcnBlock", "StGcn", "CoStGcn",
     "CoGraphConvolution", "CoTemporalConvolution", "CoSpatioTemporalBlock",
-    "AdaptiveGraphConvolution", "CoAdaptiveGraphConvolution", "AGcn", "CoAGcn", "init_weights", "zero", "unity",
+    "AdaptiveGraphConvolution", "CoAdaptiveGraphConvolution", "AGcn", "CoAGcn", "GcnUnitAttention", "STr", "CoSTr",
+    "init_weights", "zero", "unity",
     "native", "fusion", "set_precision", "set_clip_latency_mode",
 ]

@@ -29,7 +29,7 @@ import torch.nn as nn
 
 from . import blocks, fold, native
 from .blocks import GraphConvolution, SpatioTemporalBlock, TemporalConvolution, _Folded, init_weights, unity, zero
-from .models import layer_table
+from .models import layer_table, per_layer
 
 MAX_CYCLE = 8
 
@@ -465,9 +465,10 @@ class CoStGcn(_Folded):
         (c_in, t, v, m) = input_shape
         self.input_shape, self.num_classes = tuple(input_shape), num_classes
         self.data_bn = nn.BatchNorm1d(m * c_in * v)
+        convs = [CoGraphConvolution if f is None else f for f in per_layer(CoGraphConv)]   # one factory, or ten (None: default)
         self.layers = nn.ModuleDict(OrderedDict(
             (f"layer{i + 1}", CoSpatioTemporalBlock(ci, co, graph_A, stride=s, residual=r, padding="equal",
-                                                    CoGraphConv=CoGraphConv))
+                                                    CoGraphConv=convs[i]))
             for i, (ci, co, s, r) in enumerate(layer_table(c_in))))
         self.fc = nn.Linear(256, num_classes)
         init_weights(self.data_bn, bs=1)

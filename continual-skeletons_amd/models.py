@@ -21,17 +21,29 @@ def layer_table(c_in):
     ]
 
 
+def per_layer(factory):
+    """A graph-conv factory for all ten layers, or a sequence of ten (None entries: the model's default) -> list of ten."""
+    if isinstance(factory, (list, tuple)):
+        if len(factory) != 10:
+            raise ValueError(f"a per-layer graph-conv list needs 10 entries, got {len(factory)}")
+        return list(factory)
+    return [factory] * 10
+
+
 class StGcn(_Folded):
     def __init__(self, graph_A, input_shape=(3, 300, 25, 2), num_classes=60, GraphConv=None):
-        """graph_A: (3, V, V) adjacency; input_shape = (C, T, V, M) as datasets/datasets.py:128-134."""
+        """graph_A: (3, V, V) adjacency; input_shape = (C, T, V, M) as datasets/datasets.py:128-134.  ``GraphConv``: the
+        graph-conv factory of every block, or a sequence of ten (one per layer; None = GraphConvolution) -- S-TR keeps the
+        plain graph conv in layers 1-3 (models/s_tr/s_tr.py:507-518)."""
         super().__init__()
         (num_channels, num_frames, num_vertices, num_skeletons) = input_shape
         self.input_shape = tuple(input_shape)
         self.num_classes = num_classes
-        kw = {} if GraphConv is None else {"GraphConv": GraphConv}
+        convs = per_layer(GraphConv)
         self.data_bn = nn.BatchNorm1d(num_skeletons * num_channels * num_vertices)
         self.layers = nn.ModuleDict({
-            f"layer{i + 1}": SpatioTemporalBlock(ci, co, graph_A, stride=s, residual=r, **kw)
+            f"layer{i + 1}": SpatioTemporalBlock(ci, co, graph_A, stride=s, residual=r,
+                                                 **({} if convs[i] is None else {"GraphConv": convs[i]}))
             for i, (ci, co, s, r) in enumerate(layer_table(num_channels))
         })
         self.fc = nn.Linear(256, num_classes)

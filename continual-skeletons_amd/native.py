@@ -48,6 +48,7 @@ SIGNATURES = {
     "csk_co_plan_counters": [_p, C.POINTER(C.c_int64), _i, _i],
     "csk_co_plan_set_fusion": [_p, _i],
     "csk_co_plan_cycle": [_p, _p, _i, _p, _p, _p, _p, _p],
+    "csk_str_unit_f32": [_p, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _l, _l, _l, _l, _p],
 }
 RESTYPES = {"csk_co_plan_create": C.c_void_p, "csk_co_plan_destroy": None, "csk_co_plan_reset": None}
 

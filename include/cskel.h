@@ -453,6 +453,28 @@ int csk_co_plan_set_fusion(csk_co_plan *plan, int enable);
 int csk_co_plan_cycle(csk_co_plan *plan, const float *const *frames, int r, float *logits, int *last_slot,
                       int *n_feat, int *n_logits, void *stream);
 
+/*
+ * S-TR spatial-attention graph unit (GcnUnitAttention, models/s_tr/s_tr.py:303-477, in the configuration STr / CoSTr build:
+ * only_attention, no relative / adjacency / more_channels, data_bn, skip, BN; Nh = 8, dk = C_out / 4, dv = C_out).  Per
+ * frame (seg, f) of x:
+ *     x^ = s_in[c, v] x + t_in[c, v]                      (data_bn, BatchNorm1d over c*V + v)
+ *     [q; k; v] = w_qkv^T x^ + b_qkv                      (qkv_conv; q rows pre-scaled by dkh^-0.5)
+ *     o[h dvh + d, i] = sum_j softmax_j(sum_e q[h dkh + e, i] k[h dkh + e, j]) v[h dvh + d, j]     (8 heads)
+ *     y = ReLU(w_out^T o + b_out (+ res_scale[c] x[c]))   (attn_out with BN folded in; the skip when C_in == C_out)
+ * Element (seg, c, f, v) of x / y at seg * seg_stride + c * chan_stride + f * V + v: the clip layout (seg = sample, chan
+ * stride = T V, frames = T) and the continual channel-major ring slots (seg = slot, chan stride = P, frames = skeletons).
+ *  w_qkv    packed [c_in][Mq], Mq = 2 dk + dv rounded up to 64, zero columns beyond 2 dk + dv; b_qkv [Mq]   (16-B aligned)
+ *  s_in / t_in  [c_in][V]
+ *  w_out    packed [c_out][Mo], Mo = c_out rounded up to 64; b_out [Mo]; res_scale [c_out] or NULL (no skip)
+ *  scratch  >= n_seg * (2 dk + 2 dv) * frames * V floats (scratch_floats): the qkv and attention-output images
+ * Three launches (data_bn + QKV GEMM, attention, output GEMM + epilogue); fp32 MFMA for both GEMMs, exact fp32 throughout.
+ * Returns -2 for shapes not built: V not in {18, 25}, C_out not in {32, 64, 128, 256}, C_in not a multiple of 16.
+ */
+int csk_str_unit_f32(const float *x, float *y, float *scratch, int64_t scratch_floats, const float *w_qkv,
+                     const float *b_qkv, const float *s_in, const float *t_in, const float *w_out, const float *b_out,
+                     const float *res_scale, int n_seg, int c_in, int c_out, int frames, int V, int64_t x_seg_stride,
+                     int64_t x_chan_stride, int64_t y_seg_stride, int64_t y_chan_stride, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
