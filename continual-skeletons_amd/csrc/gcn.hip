@@ -50,7 +50,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void gcn_stage_kernel(const GcnParams 
     }
     // dense mode: every subset lists all V source joints in order (src[e] == e), as the A-GCN host code builds it
     const bool dense_all = p.dense;
-    const bool csk_odd_path = p.no_pair_reads;      // diagnostic: scalar LDS reads also for even V
     // aggregation-pass coordinates of this thread: one column, KPT channels
     const int aj = tid % NT, ak0 = (tid / NT) * KPT;
     const int aq = min(q0 + aj, Q - 1);
@@ -97,7 +96,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gcn_stage_kernel(const GcnParams 
             const int fo = p.adj_per_frame ? (at - ta) * adj_n : 0;          // this column's frame matrix
             const int eb0 = fo + aw * EW, eb1 = fo + (V + aw) * EW, eb2 = fo + (2 * V + aw) * EW;
             int e = 0;
-            if ((V & 1) == 0 && !csk_odd_path) {
+            if ((V & 1) == 0) {
                 // even joint count (Kinetics V = 18): every row / adjacency column starts 8-byte aligned, so two source
                 // joints are fetched per LDS instruction (the pass is LDS-issue bound: 3 + KPT reads per 3*KPT FMAs)
                 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -333,7 +332,7 @@ __global__ __launch_bounds__(NTHREADS, 3) void gcn_stage_sparse2_kernel(const Gc
         blo[u] = (unsigned)j;
     }
     const int nvec = (span + 3) / 4;
-    const bool vec = ta * V + 4 * nvec <= Q && p.Cin >= KCG_ && !p.no_vec;     // uniform (a 3-channel input: nothing to gain)
+    const bool vec = ta * V + 4 * nvec <= Q && p.Cin >= KCG_;     // uniform (a 3-channel input: nothing to gain)
     unsigned bgo4[NJ4], blo4[NJ4];
 #pragma unroll
     for (int u = 0; u < NJ4; ++u) {
@@ -793,7 +792,7 @@ static int gcn_stage_impl(const float *x, float *y, const float *w, const float 
         p.ell_cnt[i] = ell_cnt[i];
     }
     p.ell_w = ell_w; p.adj_seg_stride = adj_seg_stride;
-    p.x_ring_slots = p.y_ring_slots = 1 << 30; p.x_ring_slot0 = p.y_ring_slot0 = 0; p.stagger = 0; p.stamps = nullptr;
+    p.x_ring_slots = p.y_ring_slots = 1 << 30; p.x_ring_slot0 = p.y_ring_slot0 = 0;
     p.x_seg_stride = x_seg_stride; p.x_chan_stride = x_chan_stride;
     p.y_seg_stride = y_seg_stride; p.y_chan_stride = y_chan_stride;
     p.Cin = c_in; p.CinPad = round_up(c_in, CSK_CPAD); p.Cout = c_out; p.Mpad = round_up(c_out, CSK_MT);
@@ -801,10 +800,8 @@ static int gcn_stage_impl(const float *x, float *y, const float *w, const float 
     // per-segment adjacencies are dense by contract (include/cskel.h): ell_w == V, ell_cnt == {V,V,V}, src[e] == e
     p.dense = adj_seg_stride != 0 && ell_w == V && ell_cnt[0] == V && ell_cnt[1] == V && ell_cnt[2] == V;
     p.adj_per_frame = adj_per_frame != 0;
-    p.no_pair_reads = csk_diag_flag("CSK_NO_PAIR_READS");
-    p.no_vec = csk_diag_flag("CSK_GCN_NOVEC");
     // 32-bit lane byte offsets: 4 * (4 * row_stride + position) must stay below 2^32
-    p.fast_epi = x_chan_stride < (1ll << 27) && y_chan_stride < (1ll << 27) && !csk_diag_flag("CSK_SLOW_EPI");
+    p.fast_epi = x_chan_stride < (1ll << 27) && y_chan_stride < (1ll << 27);
     if (p.adj_per_frame && !p.dense) CSK_FAIL("gcn_stage: per-frame adjacency must be dense (ell_w == V, ell_cnt == V)");
     p.vmagic = vmagic_of(V);
     const bool big = (p.Mpad % 128) == 0;
@@ -861,7 +858,7 @@ static int gcn_stage_impl(const float *x, float *y, const float *w, const float 
     }
     // dense per-sample / per-frame adjacency with an even V <= 18: on-the-fly aggregation from register-resident adjacency
     // columns (gcn_dense.hip); every other dense shape continues below
-    if (p.dense && !csk_diag_flag("CSK_GCN_DENSE_OLD")) {
+    if (p.dense) {
         const int rc = csk_launch_gcn_dense2(p, n_seg, stream);
         if (rc != -2) return rc;
     }
@@ -870,7 +867,7 @@ static int gcn_stage_impl(const float *x, float *y, const float *w, const float 
     // dense per-segment adjacency (A-GCN clip form): aggregation on the matrix pipe, frame-aligned tiles
     // (128-row tiles only: on the 64-row tiles of the C_out = 64 layers the VALU aggregation of the general kernel measured
     // 0.31 ms per launch against 0.34 ms for this form -- profiles/r03a_agcn_clip_layers.md vs r03b)
-    if (big && p.dense && !p.adj_per_frame && V >= 4 && V <= 32 && NT / V >= 1 && frames * (int64_t)V >= 4 && !csk_diag_flag("CSK_GCN_VALU_AGG")) {
+    if (big && p.dense && !p.adj_per_frame && V >= 4 && V <= 32 && NT / V >= 1 && frames * (int64_t)V >= 4) {
         const int KC2 = 8;
         p.lds_frames = NT / V;                                  // FT: whole frames per tile
         int ldbx = round_up(p.lds_frames * V, 4);
@@ -930,7 +927,6 @@ extern "C" int csk_conv1x1_f32(const float *x, float *y, const float *w, const f
     p.Cin = c_in; p.CinPad = round_up(c_in, CSK_CPAD); p.Cout = c_out; p.Mpad = round_up(c_out, CSK_MT);
     p.frames = frames; p.V = V; p.R = 1; p.res_mode = CSK_RES_NONE;
     p.fast_epi = x_chan_stride < (1ll << 27) && y_chan_stride < (1ll << 27);
-    p.no_vec = csk_diag_flag("CSK_GCN_NOVEC");
     p.vmagic = vmagic_of(V);
     const bool big = (p.Mpad % 128) == 0;
     const int MT = big ? 128 : 64, NT = 16384 / MT;

@@ -16,16 +16,12 @@ struct GcnParams {
     int adj_per_frame;   // the (dense) adjacency varies per FRAME of a segment: index = seg * frames + frame
     int lds_frames;      // frames of adjacency staged per workgroup in that mode
     int fast_epi;        // channel strides fit the 32-bit lane offsets of the scalar-base epilogue addressing
-    int no_pair_reads;   // diagnostic (CSK_NO_PAIR_READS): general kernel aggregates with scalar LDS reads for even V too
-    int no_vec;          // diagnostic (CSK_GCN_NOVEC): sparse kernel stages activations element-wise on every tile
     // split-K (latency mode, csk_gcn_stage_splitk_f32): split ks of a tile covers channels [ks * cper, + cper) and writes raw
     // partial sums to part[(seg * ksplit + ks)][Cout][y_chan_stride]; gcn_reduce_kernel adds them up in split order
     int ksplit, cper;
     float *part;
     // step16.hip: segment s of the launch is slot (ring_slot0 + s) % ring_slots of x / y (plain calls: no wrap, 1 << 30 slots)
     int x_ring_slots, x_ring_slot0, y_ring_slots, y_ring_slot0;
-    int stagger;         // step16.hip: start delay of the odd-slot workgroup of a CU, x 64 cycles
-    unsigned long long *stamps;   // step16.hip diagnostic (CSK_STAMPS under CSK_DIAG=1): s_memtime phase sums per wave, tools/stamp16_probe.py
 };
 
 // gcn_dense.hip: dense (per-segment or per-frame) adjacency with an even joint count V <= 18; returns -2 when the shape is

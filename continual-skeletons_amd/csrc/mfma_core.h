@@ -25,10 +25,9 @@ static inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
 // Raise a kernel's dynamic-LDS cap once (and again only if a larger tile is requested): steady-state launches
 // then consist of hipLaunchKernel alone.  Returns hipSuccess (0) or the error.
 int csk_ensure_lds(const void *kernel, size_t bytes);
-// diagnostic switches (runtime.hip): active only when CSK_DIAG was set when the library was loaded
+// kernel-family switches (runtime.hip): active only when CSK_DIAG was set when the library was loaded
 bool csk_diag_flag(const char *name);
 int csk_diag_int(const char *name);
-unsigned long long *csk_diag_stamps();
 static inline unsigned vmagic_of(int V) { return (unsigned)(((1ull << 32) + V - 1) / V); }
 
 // ------------------------------------------------------------------------------------------------

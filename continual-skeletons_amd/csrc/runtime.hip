@@ -37,20 +37,19 @@ char *csk_err_buf() { return g_err; }
 extern "C" int csk_abi_version(void) { return CSK_ABI_VERSION; }
 extern "C" const char *csk_last_error(void) { return g_err; }
 
-// Diagnostics are read from the environment per call only when CSK_DIAG is set at library load (so that the normal
-// launch path never touches the environment): CSK_STAMPS=<device ptr> enables the s_memtime stamps of
-// tcn_stage_kernel (tools/stamp_probe.py), CSK_GCN_GENERAL=1 forces the general (dense-capable) GCN kernel,
-// CSK_NOPRIO=1 drops the raised wave priority inside MFMA segments (tools/ab_probe.py).
+// Kernel-family switches, read from the environment per call only when CSK_DIAG is set at library load (so that the normal
+// launch path never touches the environment).  Each picks between two production kernel families that compute the same
+// result, for A/B runs and as references in the tests:
+//   CSK_TCN16=1 / =2   the clip temporal conv never / wherever supported on the 16x16x4 family (tcn16.hip)
+//   CSK_GCN16=1 / =2   the graph conv never / wherever supported on the 16x16x4 family (step16.hip)
+//   CSK_TCN_WINO=1     the direct temporal conv instead of the Winograd kernel (tcn_wino.hip)
+//   CSK_GCN_GENERAL=1  the general (dense-capable) GCN kernel instead of the skeleton-sparse one (gcn.hip)
+//   CSK_STEP16=1       the continual step on the 32x32x2 kernels everywhere (step16.hip)
 static const bool g_diag = getenv("CSK_DIAG") != nullptr;
 bool csk_diag_flag(const char *name) { return g_diag && getenv(name) != nullptr; }
 int csk_diag_int(const char *name) {
     const char *v = g_diag ? getenv(name) : nullptr;
     return v ? atoi(v) : 0;
-}
-unsigned long long *csk_diag_stamps() {
-    if (!g_diag) return nullptr;
-    const char *d = getenv("CSK_STAMPS");
-    return d ? (unsigned long long *)strtoull(d, nullptr, 0) : nullptr;
 }
 
 // ---- stream concurrency probe (include/cskel.h: csk_stream_overlap_probe) -----------------------------------------

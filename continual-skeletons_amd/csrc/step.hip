@@ -613,14 +613,12 @@ extern "C" int csk_tcn_step_f32(const float *ring, int slots, int head, int head
     }
     if (((uintptr_t)ring | (uintptr_t)(x_res ? x_res : ring)) & 15) CSK_FAIL("tcn_step: state pointers must be 16-byte aligned");
     StepParams p;
-    p.stagger = 0;
-    p.stamps = nullptr;
     p.ring = ring; p.w = w; p.xres = x_res ? x_res : ring; p.wres = w_res; p.bias = bias; p.out = out;
     p.C = c; p.Cpad = round_up(c, CSK_CPAD); p.Cout = c_out; p.Mpad = round_up(c_out, CSK_MT);
     p.K = k; p.slots = slots; p.head = head; p.head_step = head_step; p.res_mode = res_mode;
     p.Cres = c_res > 0 ? c_res : 1; p.CresPad = round_up(p.Cres, CSK_CPAD); p.relu = relu; p.P = P;
     // 32-bit lane byte offsets: 4 * (4 * row_stride + position) must stay below 2^32
-    p.fast_epi = P < (1ll << 27) && !csk_diag_flag("CSK_SLOW_EPI");
+    p.fast_epi = P < (1ll << 27);
     p.xres_slots = x_res ? x_res_slots : 1; p.xres_slot0 = x_res ? x_res_slot0 : 0; p.xres_step = x_res_step;
     p.out_slots = out_slots; p.out_slot0 = out_slot0;
     // split-K: every split owns >= 1 real channel; fewer splits than asked for if the channel count does not allow more
@@ -640,14 +638,14 @@ extern "C" int csk_tcn_step_f32(const float *ring, int slots, int head, int head
     // per emission (a wave's 64 columns must belong to one emission); stride-2 launches only as 128-row tiles of two
     // emissions (the only stride-2 shapes of the ST-GCN stack); split-K and the E = 1 form use the plain tile.
     int E = 1;
-    if (k == 9 && !csk_diag_flag("CSK_STEP_NOFOLD")) {
+    if (k == 9) {
         if (!big && head_step == 1 && p.ksplit == 1) E = (n_emit % 4 == 0) ? 4 : (n_emit % 2 == 0) ? 2 : 1;
         if (big && head_step <= 2 && head_step >= 1) E = (n_emit % 2 == 0) ? 2 : 1;      // also with split-K
     }
     const int NP = NT / E;
     void (*kern)(StepParams);
     size_t stage_floats;
-    const bool k9 = k == 9 && !csk_diag_flag("CSK_STEP_NOCT");     // E > 1 implies k == 9 (folding condition above)
+    const bool k9 = k == 9;     // E > 1 implies k == 9 (folding condition above)
 #define CSK_PICK(MT_, E_, HS_, SP_) (kern = (E_ > 1 || k9) ? tcn_step_kernel<MT_, E_, HS_, SP_, true> : tcn_step_kernel<MT_, E_, HS_, SP_, (E_ > 1)>, stage_floats = RingStage<16384 / MT_ / E_, 8 + (E_ - 1) * HS_ + 1>::LDS_FLOATS)
     if (p.ksplit > 1) {
         if (big) E == 2 ? (head_step == 2 ? CSK_PICK(128, 2, 2, true) : CSK_PICK(128, 2, 1, true)) : CSK_PICK(128, 1, 1, true);
@@ -662,7 +660,7 @@ extern "C" int csk_tcn_step_f32(const float *ring, int slots, int head, int head
     // The 64-row, four-emission form also exists within 168 registers (three workgroups per CU, 43 KB of LDS each): taken when
     // the launch needs fewer rounds of 768 resident workgroups than of 512 (256 CUs) -- CoAGCN at the Kinetics shape is 576
     // tiles per 64-channel block: one round instead of a full one plus an eighth.  A function of the launch size only.
-    if (!big && E == 4 && p.ksplit == 1 && k9 && !csk_diag_flag("CSK_STEP_NOOCC3")) {
+    if (!big && E == 4 && p.ksplit == 1 && k9) {
         const unsigned g = grid.x;
         if ((g + 767) / 768 < (g + 511) / 512) kern = tcn_step_kernel<64, 4, 1, false, true, 3>;
     }
@@ -707,7 +705,7 @@ extern "C" int csk_co_block_step_f32(const float *xin, int xin_slots, int xin_sl
     t.C = c_out; t.Cpad = round_up(c_out, CSK_CPAD); t.Cout = c_out; t.Mpad = round_up(c_out, CSK_MT);
     t.K = 9; t.slots = y_slots; t.head = y_slot0; t.head_step = 1; t.res_mode = res_mode;
     t.Cres = res_mode ? c_in : 1; t.CresPad = round_up(t.Cres, CSK_CPAD); t.relu = 1; t.P = P;
-    t.fast_epi = P < (1ll << 27) && !csk_diag_flag("CSK_SLOW_EPI");
+    t.fast_epi = P < (1ll << 27);
     t.xres_slots = xin_slots; t.xres_slot0 = x_res_slot0; t.xres_step = 1; t.out_slots = out_slots; t.out_slot0 = out_slot0;
     t.ksplit = 1; t.cper = t.Cpad; t.part = nullptr; t.gx = (unsigned)((P + NP - 1) / NP); t.gy = 1; t.gz = 1;
     p.xin = xin; p.gw = gcn_w; p.gbias = gcn_bias; p.ell_src = ell_src; p.ell_val = ell_val;

@@ -64,10 +64,6 @@ __device__ __forceinline__ void tcn16_tile(const StepParams &p, const int bx, co
     f32x4 acc[NB];
 #pragma unroll
     for (int cb = 0; cb < NB; ++cb) acc[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // diagnostic (p.stamps): per wave the cycles of the three parts of a chunk summed over the K loop, per workgroup start /
-    // loop start / loop end / end
-    unsigned long long st0 = 0, st1 = 0, st2 = 0, ph0 = 0, ph1 = 0, ph2 = 0, tq = 0;
-    if (p.stamps) st0 = __builtin_amdgcn_s_memtime();
 
     // fragment bases: weights (B operand) lane (n = l15 -> output channel, k = kq), activations (A operand) lane (i = l15 ->
     // position inside the column block, k = kq)
@@ -83,22 +79,18 @@ __device__ __forceinline__ void tcn16_tile(const StepParams &p, const int bx, co
         ws.issue(wbase);
         if (TAIL && KCH > p.C) rs.issue_tail(rbase, 0, p.C, P, tid);
         else rs.issue(rbase);
-        if (p.stamps) st1 = tq = __builtin_amdgcn_s_memtime();
         // Issue priority inside the MFMA segments.  The two workgroups of a CU do identical work; at EQUAL priority the
         // arbiter prefers the older wave: the workgroup that started ~400 cycles earlier runs 22 % ahead, finishes, and its
-        // partner walks the rest of its K loop alone -- bound by its own LDS round trips (stamps, 256-channel launch: 951 k
-        // against 1 215 k cycles in EVERY CU).  So the favoured workgroup alternates chunk by chunk (priority 2 against 1):
-        // 1 058 k / 1 153 k, the launch 4.6 % shorter.  p.stagger >> 16 (CSK_TCN16_PRIO under CSK_DIAG=1): 0 = equal
-        // priorities, 1 = alternating, 2 = always the younger workgroup.
-        const int pmode = p.stagger >> 16;
-        int turn = pmode == 0 ? 0 : (int)(__builtin_amdgcn_s_getreg(6148) & 1);   // HW_ID wave slot: 0 = the older workgroup of the CU
+        // partner walks the rest of its K loop alone -- bound by its own LDS round trips (measured with in-kernel stamps,
+        // 256-channel launch: 951 k against 1 215 k cycles in EVERY CU).  So the favoured workgroup alternates chunk by chunk
+        // (priority 2 against 1): 1 058 k / 1 153 k, the launch 4.6 % shorter.  Round 6, 1024 NTU streams, same process:
+        // 985 -> 1 004 k frames/s (temporal step) -> 1 011 k (+ graph conv, gcn16_tile).
+        int turn = (int)(__builtin_amdgcn_s_getreg(6148) & 1);            // HW_ID wave slot: 0 = the older workgroup of the CU
         for (int c0 = 0; c0 < p.Cpad; c0 += KCH) {
             __syncthreads();
-            if (p.stamps) { const unsigned long long t = __builtin_amdgcn_s_memtime(); ph0 += t - tq; tq = t; }
             ws.commit(Wl);
             rs.commit(Bl);
             __syncthreads();
-            if (p.stamps) { const unsigned long long t = __builtin_amdgcn_s_memtime(); ph1 += t - tq; tq = t; }
             // next chunk's loads in three bursts between the three tap segments; past the end the last chunk is loaded again
             // into the (then dead) staging registers so that the K loop stays one basic block
             const int cn = min(c0 + KCH, p.Cpad - KCH);
@@ -107,7 +99,7 @@ __device__ __forceinline__ void tcn16_tile(const StepParams &p, const int bx, co
             ws.issue_one(0, wnext);
             if (!tail) rs.template issue_third<0>(rnext);
             if (turn & 1) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(1);
-            turn += pmode & 1;
+            ++turn;
 #pragma unroll
             for (int r = 0; r < 3; ++r) mfma16_tap<NB>(wl_lane + r * KCH * LDW, bl_lane + G::slot_lds(r), acc);
             ws.issue_one(1, wnext);
@@ -120,9 +112,7 @@ __device__ __forceinline__ void tcn16_tile(const StepParams &p, const int bx, co
 #pragma unroll
             for (int r = 6; r < 9; ++r) mfma16_tap<NB>(wl_lane + r * KCH * LDW, bl_lane + G::slot_lds(r), acc);
             __builtin_amdgcn_s_setprio(0);
-            if (p.stamps) { const unsigned long long t = __builtin_amdgcn_s_memtime(); ph2 += t - tq; tq = t; }
         }
-        if (p.stamps) st2 = __builtin_amdgcn_s_memtime();
     }
     // ---- phase 2: 1x1 residual conv on the delayed block input (one "tap" per emission: the E residual frames back to back)
     if (p.res_mode == CSK_RES_CONV) {
@@ -162,18 +152,11 @@ __device__ __forceinline__ void tcn16_tile(const StepParams &p, const int bx, co
     const int nval = (int)min((int64_t)NP, P - p0);                             // positions of the tile inside the row (multiple of 4)
     epilogue16<NB, E, NP>(acc, p.bias, p.Cout, m0 + wave * 16 + l15, kq, p.res_mode == CSK_RES_IDENTITY, p.relu != 0, p.xres, p.out,
                           xslot, oslot, P, P, p0, nval, nval);
-    if (p.stamps && lane == 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // the epilogue's stores have left
-        unsigned long long *o = p.stamps + ((size_t)blockIdx.x * 4 + wave) * 8;
-        o[0] = st0; o[1] = st1; o[2] = st2; o[3] = __builtin_amdgcn_s_memtime(); o[4] = ph0; o[5] = ph1; o[6] = ph2;
-        o[7] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));    // HW_REG_HW_ID
-    }
 }
 
 template <int NB, int E, int HS, bool TAIL>
 __global__ __launch_bounds__(NTHREADS, TAIL ? 1 : 2) void tcn_step16_kernel(const StepParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    stagger_odd_slot(p.stagger & 0xffff);
     // XCD-contiguous work order, m-tile fastest (the m-tiles of a position tile read the same ring window)
     const unsigned wid = xcd_contiguous_id(blockIdx.x, gridDim.x);
     tcn16_tile<NB, E, HS, TAIL>(p, (int)(wid / (p.gy * p.gz)), (int)(wid % p.gy), (int)((wid / p.gy) % p.gz), smem);
@@ -273,85 +256,70 @@ __device__ __forceinline__ void gcn16_tile(const GcnParams &p, const int mt, con
     xs.commit(Xs);
     issue_x(1);
     __syncthreads();
-    const int gmode = (p.stagger >> 20) & 7, godd = (int)(__builtin_amdgcn_s_getreg(6148) & 1);   // HW_ID wave slot: 0 = the older workgroup
-    unsigned long long gp0 = 0, gp1 = 0, gp2 = 0, gp3 = 0, gp4 = 0, gq = 0, gst0 = 0;   // diagnostic phase sums (p.stamps only)
-    if (p.stamps) gst0 = gq = __builtin_amdgcn_s_memtime();
+    const int godd = (int)(__builtin_amdgcn_s_getreg(6148) & 1);      // HW_ID wave slot: 0 = the older workgroup
     for (int c = 0; c < nchunks; ++c) {
         // ---- P1: aggregate chunk c, commit its weights, load the next chunk's.  Four rounds (channel half h, column n): the six
         // source joints of a column with 4 channels each in six 16-byte gathers from the channel-interleaved x tile (WinT16),
         // multiplied out, the two columns of a thread written as pairs
-        if (!(p.stagger & 0x10000) && p1_wave) {               // (diagnostic: CSK_GCN16_SKIP=1 times the kernel without its aggregation phase)
+        if (p1_wave) {
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {                          // channels 4 h .. 4 h + 3 of the chunk
-            float res[4][3][NC];
+            for (int h = 0; h < 2; ++h) {                      // channels 4 h .. 4 h + 3 of the chunk
+                float res[4][3][NC];
 #pragma unroll
-            for (int n = 0; n < NC; ++n) {
-                // (the six 16-byte gathers of the NEXT round in flight under this round's arithmetic: 4.75 k -> 4.45 k cycles for
-                // the phase, which the partner's MFMA phase lost again -- 6.7 k -> 7.3 k: not kept)
-                f32x4 x[6];
+                for (int n = 0; n < NC; ++n) {
+                    // (the six 16-byte gathers of the NEXT round in flight under this round's arithmetic: 4.75 k -> 4.45 k cycles
+                    // for the phase, which the partner's MFMA phase lost again -- 6.7 k -> 7.3 k: not kept)
+                    f32x4 x[6];
 #pragma unroll
-                for (int e = 0; e < 6; ++e) x[e] = *reinterpret_cast<const f32x4 *>(Xs + h * XH + eoff[n][e]);
-                __builtin_amdgcn_sched_barrier(0);
+                    for (int e = 0; e < 6; ++e) x[e] = *reinterpret_cast<const f32x4 *>(Xs + h * XH + eoff[n][e]);
+                    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int kk = 0; kk < 4; ++kk) {
-                    res[kk][0][n] = eval[n][0] * x[0][kk];
-                    res[kk][1][n] = eval[n][1] * x[1][kk];
-                    float s2 = eval[n][2] * x[2][kk];
-                    s2 = fmaf(eval[n][3], x[3][kk], s2);
-                    s2 = fmaf(eval[n][4], x[4][kk], s2);
-                    s2 = fmaf(eval[n][5], x[5][kk], s2);
-                    res[kk][2][n] = s2;
+                    for (int kk = 0; kk < 4; ++kk) {
+                        res[kk][0][n] = eval[n][0] * x[0][kk];
+                        res[kk][1][n] = eval[n][1] * x[1][kk];
+                        float s2 = eval[n][2] * x[2][kk];
+                        s2 = fmaf(eval[n][3], x[3][kk], s2);
+                        s2 = fmaf(eval[n][4], x[4][kk], s2);
+                        s2 = fmaf(eval[n][5], x[5][kk], s2);
+                        res[kk][2][n] = s2;
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
                 }
-                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+                    for (int r = 0; r < 3; ++r) {
+                        float *d = Ba + gcn_entry(4 * h + kk, r, R) * AROW + c0;
+                        if constexpr (NC == 2) *reinterpret_cast<f32x2 *>(d) = f32x2{res[kk][r][0], res[kk][r][NC - 1]};
+                        else *d = res[kk][r][0];
+                    }
+                if (CONVRES) {                                // fourth "subset": the input itself (the conv gcn_residual's operand)
+                    const f32x4 x0 = *reinterpret_cast<const f32x4 *>(Xs + h * XH + ioff[0]);
+                    const f32x4 x1 = *reinterpret_cast<const f32x4 *>(Xs + h * XH + ioff[NC - 1]);
+#pragma unroll
+                    for (int kk = 0; kk < 4; ++kk) {
+                        float *d = Ba + gcn_entry(4 * h + kk, 3, R) * AROW + c0;
+                        if constexpr (NC == 2) *reinterpret_cast<f32x2 *>(d) = f32x2{x0[kk], x1[kk]};
+                        else *d = x0[kk];
+                    }
+                }
             }
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-                for (int r = 0; r < 3; ++r) {
-                    float *d = Ba + gcn_entry(4 * h + kk, r, R) * AROW + c0;
-                    if constexpr (NC == 2) *reinterpret_cast<f32x2 *>(d) = f32x2{res[kk][r][0], res[kk][r][NC - 1]};
-                    else *d = res[kk][r][0];
-                }
-            if (CONVRES) {                                    // fourth "subset": the input itself (the conv gcn_residual's operand)
-                const f32x4 x0 = *reinterpret_cast<const f32x4 *>(Xs + h * XH + ioff[0]);
-                const f32x4 x1 = *reinterpret_cast<const f32x4 *>(Xs + h * XH + ioff[NC - 1]);
-#pragma unroll
-                for (int kk = 0; kk < 4; ++kk) {
-                    float *d = Ba + gcn_entry(4 * h + kk, 3, R) * AROW + c0;
-                    if constexpr (NC == 2) *reinterpret_cast<f32x2 *>(d) = f32x2{x0[kk], x1[kk]};
-                    else *d = x0[kk];
-                }
-            }
-        }
         }
         ws.commit(Wl);
         ws.issue(wbase + (size_t)min(c + 1, nchunks - 1) * KCG * p.Mpad);
-        if (p.stamps) { const unsigned long long t = __builtin_amdgcn_s_memtime(); gp0 += t - gq; gq = t; }
         __syncthreads();
-        if (p.stamps) { const unsigned long long t = __builtin_amdgcn_s_memtime(); gp1 += t - gq; gq = t; }
         // ---- P2: x rows of chunk c + 1 -> LDS, chunk c + 2 -> registers, MFMAs of chunk c
         xs.commit(Xs);
         issue_x(c + 2);
-        if (p.stamps) { const unsigned long long t = __builtin_amdgcn_s_memtime(); gp2 += t - gq; gq = t; }
-        // (issue priority of the MFMA phase: see tcn16_tile -- mode 1 / 2: the favoured workgroup of the CU alternates chunk by chunk)
-        if (gmode == 0) __builtin_amdgcn_s_setprio(1);
-        else if (gmode != 4) { if (((gmode == 3 ? 0 : c) + godd) & 1) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(1); }
-        if (!(p.stagger & 0x20000)) {                          // (diagnostic: CSK_GCN16_SKIP=2: without its MFMA phase)
+        // (issue priority of the MFMA phase: see tcn16_tile -- the favoured workgroup of the CU alternates chunk by chunk)
+        if ((c + godd) & 1) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int m = 0; m < NE / 4; ++m) {
             if constexpr (NW == 8 && (NB & 1)) mfma16_tap_opt_last<NBW, GCN_AHEAD>(wl_lane + 4 * m * LDW, ba_lane + 4 * m * AROW, acc, wh == 0);
             else mfma16_tap<NBW, GCN_AHEAD>(wl_lane + 4 * m * LDW, ba_lane + 4 * m * AROW, acc);
         }
-        }
         __builtin_amdgcn_s_setprio(0);
-        if (p.stamps) { const unsigned long long t = __builtin_amdgcn_s_memtime(); gp3 += t - gq; gq = t; }
         __syncthreads();
-        if (p.stamps) { const unsigned long long t = __builtin_amdgcn_s_memtime(); gp4 += t - gq; gq = t; }
-    }
-    if (p.stamps && lane == 0 && wave < 4) {
-        unsigned long long *o = p.stamps + ((size_t)blockIdx.x * 4 + wave) * 8;
-        o[0] = gst0; o[1] = gq; o[2] = gp0; o[3] = gp1; o[4] = gp2; o[5] = gp3; o[6] = gp4;
-        o[7] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));    // HW_REG_HW_ID
     }
     unsigned oslot[F], xslot[F];
 #pragma unroll
@@ -372,16 +340,8 @@ __device__ __forceinline__ void gcn16_tile(const GcnParams &p, const int mt, con
 template <int NB, int F, bool CONVRES, int NW>
 __global__ __launch_bounds__(64 * NW, NW / 2) void gcn16_kernel(const GcnParams p) {   // (second figure: waves per SIMD = two workgroups per CU)
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    stagger_odd_slot(p.stagger & 0xffff);
     const unsigned wid = xcd_contiguous_id(blockIdx.x, gridDim.x);
-    unsigned long long k0 = 0;
-    if (p.stamps) k0 = __builtin_amdgcn_s_memtime();
     gcn16_tile<NB, F, CONVRES, NW>(p, (int)(wid % p.mtiles), (int)((wid / p.mtiles) % p.qtiles), (int)(wid / (p.mtiles * p.qtiles)), smem);
-    if (p.stamps && (threadIdx.x & 63) == 0) {                 // diagnostic: workgroup start / end (stores retired), behind the per-wave records
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        unsigned long long *o = p.stamps + (size_t)gridDim.x * 32 + ((size_t)blockIdx.x * 4 + ((threadIdx.x >> 6) & 3)) * 2;
-        if ((threadIdx.x >> 6) < 4) { o[0] = k0; o[1] = __builtin_amdgcn_s_memtime(); }
-    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -411,7 +371,6 @@ __device__ __forceinline__ void stage_handoff() {
 template <int NB>
 __global__ __launch_bounds__(NTHREADS, 2) void co_stack16_kernel(const CoStackParams sp) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    stagger_odd_slot(sp.b[0].g.stagger & 0xffff);
     const int bx = (int)xcd_contiguous_id(blockIdx.x, gridDim.x);
     for (int i = 0; i < sp.nblk; ++i) {
         const CoStackBlock &b = sp.b[i];
@@ -432,8 +391,6 @@ int launch_gcn16(GcnParams p, int n_seg, hipStream_t s) {
     if (grid >= (1ll << 31)) CSK_FAIL("gcn_stage: grid too large");
     constexpr int NW = CSK_GCN16_WAVES;
     void (*kern)(GcnParams) = p.R == 4 ? gcn16_kernel<NB, F, true, NW> : gcn16_kernel<NB, F, false, NW>;
-    p.stagger = stagger_units("CSK_GCN16_STAGGER", GCN16_STAGGER) | ((csk_diag_int("CSK_GCN16_SKIP") & 15) << 16) | (prio_mode("CSK_GCN16_PRIO", GCN16_PRIO) << 20);
-    p.stamps = csk_diag_stamps();
     const size_t lds = (size_t)(8 * p.R * (80 + row16(NT)) + 2 * WinT16<F, NPG>::HALF) * sizeof(float);
     if (const int e = csk_ensure_lds((const void *)kern, lds)) return e;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * NW), lds, s, p);
@@ -448,8 +405,6 @@ int launch16(StepParams p, int n_emit, hipStream_t s) {
     // the fast instantiation walks Cpad (CresPad) channel rows: it is only for operands without padding rows -- a channel count
     // that is a multiple of the chunk but not of CSK_CPAD (C = 4, 8: test shapes) would read up to 12 rows past the last ring slot
     const bool tail = p.Cpad != p.C || (p.res_mode == CSK_RES_CONV && p.CresPad != p.Cres);
-    p.stagger = stagger_units("CSK_TCN16_STAGGER", TCN16_STAGGER) | (prio_mode("CSK_TCN16_PRIO", TCN16_PRIO) << 16);
-    p.stamps = csk_diag_stamps();
     void (*kern)(StepParams) = tail ? tcn_step16_kernel<NB, E, HS, true> : tcn_step16_kernel<NB, E, HS, false>;
     const size_t lds = (size_t)G::LDS_FLOATS * sizeof(float);
     if (const int e = csk_ensure_lds((const void *)kern, lds)) return e;
@@ -524,9 +479,9 @@ int csk_launch_gcn16(GcnParams p, int n_seg, void *stream) {
 }
 
 // ---- stack of 64-channel blocks ------------------------------------------------------------------------------------------
-// -2: not a shape the fused stack is built for (the caller issues the per-stage launches); CSK_STACK16=1 under CSK_DIAG=1: never
+// -2: not a shape the fused stack is built for (the caller issues the per-stage launches)
 int csk_launch_co_stack16(int n_blocks, const csk_co_block_args *b, int n_skel, int V, int64_t P, void *stream) {
-    if (!csk_step16_enabled() || csk_diag_int("CSK_STACK16") == 1) return -2;
+    if (!csk_step16_enabled()) return -2;
     if (n_blocks < 1 || n_blocks > CSK_CO_STACK_MAX || P < 8 || (P & 3)) return -2;
     const int64_t Q = (int64_t)n_skel * V;
     int best_nb = 0;
@@ -561,8 +516,6 @@ int csk_launch_co_stack16(int n_blocks, const csk_co_block_args *b, int n_skel, 
         g.frames = n_skel; g.V = V; g.R = a.gcn_res_mode == CSK_RES_CONV ? 4 : 3; g.res_mode = a.gcn_res_mode;
         g.vmagic = vmagic_of(V); g.mtiles = 1; g.qtiles = (unsigned)((Q + NP - 1) / NP); g.ksplit = 1; g.cper = g.CinPad; g.part = nullptr;
         g.x_ring_slots = a.xin_slots; g.x_ring_slot0 = a.xin_slot0; g.y_ring_slots = a.y_slots; g.y_ring_slot0 = a.y_slot0;
-        g.stagger = stagger_units("CSK_GCN16_STAGGER", GCN16_STAGGER) | (prio_mode("CSK_GCN16_PRIO", GCN16_PRIO) << 20);
-        g.stamps = nullptr;
         StepParams &t = sp.b[i].t;
         t = StepParams{};
         t.ring = a.y_ring; t.w = a.tcn_w; t.xres = a.xin; t.wres = nullptr; t.bias = a.tcn_bias; t.out = a.out;
@@ -570,7 +523,6 @@ int csk_launch_co_stack16(int n_blocks, const csk_co_block_args *b, int n_skel, 
         t.K = 9; t.slots = a.y_slots; t.head = a.y_slot0; t.head_step = 1; t.res_mode = a.res_mode;
         t.Cres = a.res_mode ? a.c_in : 1; t.CresPad = round_up(t.Cres, CSK_CPAD); t.relu = 1; t.P = P; t.fast_epi = 1;
         t.xres_slots = a.xin_slots; t.xres_slot0 = a.x_res_slot0; t.xres_step = 1; t.out_slots = a.out_slots; t.out_slot0 = a.out_slot0;
-        t.stamps = nullptr; t.stagger = prio_mode("CSK_TCN16_PRIO", TCN16_PRIO) << 16;
         t.ksplit = 1; t.cper = t.Cpad; t.part = nullptr; t.gx = (unsigned)((P + NP - 1) / NP); t.gy = 1; t.gz = 1;
     }
     void (*kern)(CoStackParams) = best_nb == 25 ? co_stack16_kernel<25> : co_stack16_kernel<18>;

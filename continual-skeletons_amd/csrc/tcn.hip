@@ -71,8 +71,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void tcn_stage_kernel(const TcnParams 
             for (int g = 0; g < 16; ++g) acc[a][b][g] = 0.f;
 
     const int offA = wm * 64 + l31;
-    unsigned long long st0 = 0, st1 = 0, st2 = 0;
-    if (p.stamps) st0 = __builtin_amdgcn_s_memtime();
     WStage<MT> ws;
     BStage<NJ> bs;
     // epilogue operands: 32 biases + (identity residual) 64 block-input values per lane.  They are loaded
@@ -144,57 +142,46 @@ __global__ __launch_bounds__(NTHREADS, 2) void tcn_stage_kernel(const TcnParams 
             ws1.issue(wbase);
             bx.issue(seg_base, Cl, cs, 0, wave);
             int c0 = 0;
-            unsigned long long ph0 = 0, ph1 = 0, ph2 = 0, ph3 = 0, tq = 0;   // diagnostic phase sums (p.stamps only)
             for (; c0 + KC < CpadL; c0 += KC) {
-                if (p.stamps) tq = __builtin_amdgcn_s_memtime();
                 __syncthreads();                       // previous chunk's LDS reads are done
-                if (p.stamps) { const unsigned long long t = __builtin_amdgcn_s_memtime(); ph0 += t - tq; tq = t; }
                 ws1.commit(Wl);
                 bx.commit(Bl, p.ldb, wave);
                 __syncthreads();
-                if (p.stamps) { const unsigned long long t = __builtin_amdgcn_s_memtime(); ph1 += t - tq; tq = t; }
-                if (p.stamps && c0 == 0) st1 = __builtin_amdgcn_s_memtime();
                 {
                     // the next chunk's loads are issued in three bursts between three tap segments (see mfma_taps)
                     const float *wnext = wbase + (size_t)(c0 + KC) * p.Mpad;
                     const int cn = c0 + KC, t1 = (p.K + 2) / 3, t2 = min(p.K, 2 * t1);
-                    if (p.stamps) { const unsigned long long t = __builtin_amdgcn_s_memtime(); ph2 += t - tq; tq = t; }
 #pragma unroll
                     for (int j = 0; j < 3; ++j) ws1.issue_slot(j, wnext);
                     bx.template issue_third<0>(seg_base, Cl, cs, cn, wave);
                     // raised priority while in an MFMA segment: this wave then wins issue arbitration against the
                     // SIMD partner's commit / load-issue phase (+2 % measured)
-                    if (p.prio) __builtin_amdgcn_s_setprio(1);
+                    __builtin_amdgcn_s_setprio(1);
                     if (CT) mfma_taps_ct<MT, 3, LAT_AHEAD>(Wl, Bl, 0, p.ldb, V, offA, off[0], off[1], kh, acc);
                     else mfma_taps<MT>(Wl, Bl, 0, t1, p.ldb, V, offA, off[0], off[1], kh, acc);
                     __builtin_amdgcn_s_setprio(0);
 #pragma unroll
                     for (int j = 3; j < 6; ++j) ws1.issue_slot(j, wnext);
                     bx.template issue_third<1>(seg_base, Cl, cs, cn, wave);
-                    if (p.prio) __builtin_amdgcn_s_setprio(1);
+                    __builtin_amdgcn_s_setprio(1);
                     if (CT) mfma_taps_ct<MT, 3, LAT_AHEAD>(Wl, Bl, 3, p.ldb, V, offA, off[0], off[1], kh, acc);
                     else if (t1 < t2) mfma_taps<MT>(Wl, Bl, t1, t2, p.ldb, V, offA, off[0], off[1], kh, acc);
                     __builtin_amdgcn_s_setprio(0);
 #pragma unroll
                     for (int j = 6; j < 9; ++j) ws1.issue_slot(j, wnext);
                     bx.template issue_third<2>(seg_base, Cl, cs, cn, wave);
-                    if (p.prio) __builtin_amdgcn_s_setprio(1);
+                    __builtin_amdgcn_s_setprio(1);
                     if (CT) mfma_taps_ct<MT, 3, LAT_AHEAD>(Wl, Bl, 6, p.ldb, V, offA, off[0], off[1], kh, acc);
                     else if (t2 < p.K) mfma_taps<MT>(Wl, Bl, t2, p.K, p.ldb, V, offA, off[0], off[1], kh, acc);
                     __builtin_amdgcn_s_setprio(0);
                 }
-                if (p.stamps) { const unsigned long long t = __builtin_amdgcn_s_memtime(); ph3 += t - tq; tq = t; }
-            }
-            if (p.stamps && lane == 0) {
-                unsigned long long *o = p.stamps + (size_t)gridDim.x * 6 + ((size_t)blockIdx.x * 4 + wave) * 4;
-                o[0] = ph0; o[1] = ph1; o[2] = ph2; o[3] = ph3;
             }
             __syncthreads();                           // peeled last chunk
             ws1.commit(Wl);
             bx.commit(Bl, p.ldb, wave);
             __syncthreads();
         };
-        const bool interior = p.vec_stage && fa >= 0 && fa * V + 4 * ((span + 3) / 4) <= p.Tin * V;     // uniform
+        const bool interior = fa >= 0 && fa * V + 4 * ((span + 3) / 4) <= p.Tin * V;     // uniform
         if (interior) {
             BStage4<(NJ + 3) / 4> b4;
             b4.setup(fa * V, span, lane);
@@ -204,8 +191,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void tcn_stage_kernel(const TcnParams 
             phase1(bs);
         }
         if (!conv_res && OCC == 2) { load_half(0); load_half(1); }
-        if (K9 && NJ < 9 && !p.no_peel_ct) {   // the peeled last chunk in straight-line 3-tap segments too, where the register budget allows
-                                               // (+0.1 ... +0.7 %; diagnostic CSK_TCN_NOPEELCT keeps it rolled)
+        if (K9 && NJ < 9) {   // the peeled last chunk in straight-line 3-tap segments too, where the register budget allows (+0.1 ... +0.7 %)
             mfma_taps_ct<MT, 3, LAT_AHEAD>(Wl, Bl, 0, p.ldb, V, offA, off[0], off[1], kh, acc);
             mfma_taps_ct<MT, 3, LAT_AHEAD>(Wl, Bl, 3, p.ldb, V, offA, off[0], off[1], kh, acc);
             mfma_taps_ct<MT, 3, LAT_AHEAD>(Wl, Bl, 6, p.ldb, V, offA, off[0], off[1], kh, acc);
@@ -269,7 +255,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void tcn_stage_kernel(const TcnParams 
             if (OCC == 2) { load_half(0); load_half(1); }
         }
     }
-    if (p.stamps) st2 = __builtin_amdgcn_s_memtime();
     // ---- epilogue: + bias (+ identity residual), ReLU, predicated stores.
     // C/D map: col = lane&31, row = (g&3) + 8(g>>2) + 4(lane>>5).  A plain store of accumulator register g
     // writes two 128-B half rows (rows r and r+4).  v_permlane32_swap of the ni=0 / ni=1 registers gives each
@@ -314,13 +299,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void tcn_stage_kernel(const TcnParams 
         finish_half(0);
         load_half(1);
         finish_half(1);
-    }
-    if (p.stamps && tid == 0) {
-        unsigned long long st3 = __builtin_amdgcn_s_memtime();
-        unsigned long long *o = p.stamps + (size_t)blockIdx.x * 6;
-        o[0] = st0; o[1] = st1; o[2] = st2; o[3] = st3;
-        o[4] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));    // HW_REG_HW_ID
-        o[5] = __builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11));   // HW_REG_XCC_ID
     }
 }
 
@@ -389,12 +367,8 @@ static int tcn_stage_impl(const float *y, const float *w, const float *x_res, co
     p.cper = round_up((p.Cpad + ksplit - 1) / ksplit, KC);
     p.ksplit = ksplit > 1 ? (c + p.cper - 1) / p.cper : 1;
     p.part = partial;
-    p.stamps = csk_diag_stamps();
-    p.prio = !csk_diag_flag("CSK_NOPRIO");
-    p.vec_stage = !csk_diag_flag("CSK_TCN_NOVEC");
-    p.no_peel_ct = csk_diag_flag("CSK_TCN_NOPEELCT");
     // 32-bit lane byte offsets: 4 * (4 * row_stride + position) must stay below 2^32
-    p.fast_epi = (int64_t)p.Tres * V < (1ll << 27) && (int64_t)t_out * V < (1ll << 27) && !csk_diag_flag("CSK_SLOW_EPI");
+    p.fast_epi = (int64_t)p.Tres * V < (1ll << 27) && (int64_t)t_out * V < (1ll << 27);
     // the register staging holds <= 9 (128-row tiles) / 14 (64-row tiles) x 64 positions of an activation row -- the
     // widest spill-free instantiations; tiles whose input span (stride * frames + k taps) * V is longer than that
     // (stride 2 with V > 32, stride 3, ...) are narrowed: a tile then covers nt < NT output positions and the remaining
@@ -458,12 +432,12 @@ static int tcn_stage_impl(const float *y, const float *w, const float *x_res, co
     void (*kern)(TcnParams) =
         big ? (nj <= 6 ? tcn_stage_kernel<128, 6> : tcn_stage_kernel<128, 9>)
             : (nj <= 6 ? tcn_stage_kernel<64, 6> : nj <= 9 ? tcn_stage_kernel<64, 9> : tcn_stage_kernel<64, 14>);
-    if (k == 9 && !csk_diag_flag("CSK_TCN_NOK9"))     // the 9-tap form with straight-line 3-tap MFMA segments
+    if (k == 9)     // the 9-tap form with straight-line 3-tap MFMA segments
         kern = big ? (nj <= 6 ? tcn_stage_kernel<128, 6, true> : tcn_stage_kernel<128, 9, true>)
                    : (nj <= 6 ? tcn_stage_kernel<64, 6, true> : nj <= 9 ? tcn_stage_kernel<64, 9, true> : tcn_stage_kernel<64, 14>);
     // the two skeleton sizes of the reference's datasets (NTU-25, OpenPose-18) with V as a compile-time constant: the tap
-    // shift of an LDS read becomes an immediate offset (+0.1 ... +0.8 % per launch, in-process A/B CSK_TCN_NOVT)
-    if (k == 9 && (V == 25 || V == 18) && vt_ok && !csk_diag_flag("CSK_TCN_NOK9") && !csk_diag_flag("CSK_TCN_NOVT") && nj <= 9) {
+    // shift of an LDS read becomes an immediate offset (+0.1 ... +0.8 % per launch)
+    if (k == 9 && (V == 25 || V == 18) && vt_ok && nj <= 9) {
         if (V == 25)
             kern = big ? (nj <= 6 ? tcn_stage_kernel<128, 6, true, false, 25> : tcn_stage_kernel<128, 9, true, false, 25>)
                        : (nj <= 6 ? tcn_stage_kernel<64, 6, true, false, 25> : tcn_stage_kernel<64, 9, true, false, 25>);

@@ -5,7 +5,7 @@
 // Why.  In-kernel stamps of the 32x32x2 stage kernel: a C = 256 tile spends 590 k of its 712 k cycles in MFMAs (0.83 of the
 // loop) -- one LDS round trip per 64-cycle MFMA pair, a 2 x 2 accumulator tile per wave, 144 MFMAs between two barriers.  The
 // step kernels of round 6 (step16.hip) showed what the 16-wide block buys: a wave carries 25 independent accumulators, 450
-// MFMAs between two barriers, and its K loop runs at 0.985 of the matrix pipe (tools/stamp16_probe.py).  This is the same
+// MFMAs between two barriers, and its K loop runs at 0.985 of the matrix pipe (in-kernel stamps, round 6).  This is the same
 // tile for the clip layout: the temporal taps are address shifts of r * V positions in ONE staged row per input channel
 // (16 output frames + 8 halo frames), so a fragment read is one VGPR base + an immediate.
 //   stride 2: output frame t' reads input frames 2 t' + r: the row holds the 40 input frames of the tile in natural order and

@@ -37,7 +37,6 @@ struct TcnSplitParams {
     int res_mode, Cres, nchunks_res, Tres, res_off, relu, ldb;
     unsigned vmagic, mtiles, qtiles;
     int nt, fast_epi;
-    int diag;   // CSK_DIAG + CSK_SPLIT_SKIP=<bits>: 1 weight staging, 2 activation staging, 4 MFMAs, 8 barriers skipped in the K loop (timing experiments)
 };
 
 template <int MT, int NS4>
@@ -108,7 +107,7 @@ __global__ __launch_bounds__(NTH2, 2) void tcn_split_stage_kernel(const TcnSplit
         if (nst > 1) ws.issue(wb + sstride, p.Mpad, tid);
         if (nchunks > 1) bs.issue(seg_base, p.C, cs, KS);
         __syncthreads();
-        const bool early = wave < 4 || (p.diag & 16);
+        const bool early = wave < 4;
         for (int c = 0; c < nchunks; ++c) {
 #pragma unroll
             for (int s = 0; s < NSTAGE; ++s) {
@@ -118,25 +117,25 @@ __global__ __launch_bounds__(NTH2, 2) void tcn_split_stage_kernel(const TcnSplit
                 // opposite orders, so one feeds the matrix pipe while the other stages -- both orders are legal inside the
                 // barrier interval (the staging writes the OTHER weight buffer and registers only)
                 auto stage_work = [&]() {
-                    if (g + 1 < nst && !(p.diag & 1)) ws.commit(oth, tid);
-                    if (g + 2 < nst && !(p.diag & 1)) ws.issue(wb + (g + 2) * sstride, p.Mpad, tid);
+                    if (g + 1 < nst) ws.commit(oth, tid);
+                    if (g + 2 < nst) ws.issue(wb + (g + 2) * sstride, p.Mpad, tid);
                 };
                 auto stage_mfma = [&]() {
                     __builtin_amdgcn_s_setprio(1);
-                    if (!(p.diag & 4)) mfma_split_taps<MT, TG>(cur, Bl, p.ldb, toff + s * TG, offA, off[0], off[1], kh, acc);
+                    mfma_split_taps<MT, TG>(cur, Bl, p.ldb, toff + s * TG, offA, off[0], off[1], kh, acc);
                     __builtin_amdgcn_s_setprio(0);
                 };
                 if (early) stage_work();
                 if (PRE && s == NSTAGE - 1 && c + 1 < nchunks) bs.presplit();      // next tile's pieces, beside this stage's MFMAs
                 stage_mfma();
                 if (!early) stage_work();
-                if (!(p.diag & 8)) __syncthreads();
+                __syncthreads();
             }
-            if (c + 1 < nchunks && !(p.diag & 2)) {
+            if (c + 1 < nchunks) {
                 if (PRE) bs.commit_pk(Bl, p.ldb);
                 else bs.commit(Bl, p.ldb);
                 if (c + 2 < nchunks) bs.issue(seg_base, p.C, cs, (c + 2) * KS);
-                if (!(p.diag & 8)) __syncthreads();
+                __syncthreads();
             }
         }
     }
@@ -148,15 +147,18 @@ __global__ __launch_bounds__(NTH2, 2) void tcn_split_stage_kernel(const TcnSplit
         const int64_t sstride = (int64_t)TG * 6 * p.Mpad;      // one stage (tap 0 + two zero slots) per chunk
         const int one[4] = {1, 0, 0, 0};
         const int tz[1] = {0};
-        bs.setup(p.stride * ta + p.res_off, p.stride, dt, 1, one, p.Tres, V, p.vmagic, lane, wave);
-        ws.issue(wb, p.Mpad, tid);
+        // (thread coordinates recomputed from an opaque thread id: kept live across the K loop above they spill)
+        int tid2 = threadIdx.x;
+        asm volatile("" : "+v"(tid2));
+        bs.setup(p.stride * ta + p.res_off, p.stride, dt, 1, one, p.Tres, V, p.vmagic, tid2 & 63, __builtin_amdgcn_readfirstlane(tid2 >> 6));
+        ws.issue(wb, p.Mpad, tid2);
         bs.issue(seg_base, p.Cres, cs, 0);
         for (int c = 0; c < p.nchunks_res; ++c) {
-            ws.commit(Wl0, tid);                       // (phase 1 / the previous chunk ended with a barrier)
+            ws.commit(Wl0, tid2);                      // (phase 1 / the previous chunk ended with a barrier)
             bs.commit(Bl, p.ldb);
             __syncthreads();
             if (c + 1 < p.nchunks_res) {
-                ws.issue(wb + (c + 1) * sstride, p.Mpad, tid);
+                ws.issue(wb + (c + 1) * sstride, p.Mpad, tid2);
                 bs.issue(seg_base, p.Cres, cs, (c + 1) * KS);
             }
             mfma_split_taps<MT, 1>(Wl0, Bl, p.ldb, tz, offA, off[0], off[1], kh, acc);
@@ -202,7 +204,6 @@ extern "C" int csk_tcn_stage_bf16x3(const float *y, const void *w_split, const f
     p.Tres = t_res > 0 ? t_res : 1; p.res_off = res_off; p.relu = relu;
     p.vmagic = vmagic_of(V);
     p.fast_epi = (int64_t)p.Tres * V < (1ll << 27) && (int64_t)t_out * V < (1ll << 27);
-    p.diag = csk_diag_int("CSK_SPLIT_SKIP");
     const bool big = (p.Mpad % 128) == 0;
     const int MT = big ? 128 : 64, NT = 32768 / MT;
     // a tile stages (stride * frames spanned + 9) * V positions per 16-byte row: at most 16 (64-row tiles) / 16 (128-row

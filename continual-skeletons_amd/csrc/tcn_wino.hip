@@ -130,19 +130,19 @@ __global__ __launch_bounds__(NTHREADS, 2) void tcn_stage_wino_kernel(const TcnPa
                 ws.issue_slot(0, wnext);
                 ws.issue_slot(1, wnext);
                 bx.template issue_third<0>(seg_base, p.C, cs, cn, wave);
-                if (p.prio) __builtin_amdgcn_s_setprio(1);
+                __builtin_amdgcn_s_setprio(1);
                 wino_group<VT, 0>(Wl, Bl, off, l31, kh, acc);
                 __builtin_amdgcn_s_setprio(0);
                 ws.issue_slot(2, wnext);
                 ws.issue_slot(3, wnext);
                 bx.template issue_third<1>(seg_base, p.C, cs, cn, wave);
-                if (p.prio) __builtin_amdgcn_s_setprio(1);
+                __builtin_amdgcn_s_setprio(1);
                 wino_group<VT, 1>(Wl, Bl, off, l31, kh, acc);
                 __builtin_amdgcn_s_setprio(0);
                 ws.issue_slot(4, wnext);
                 ws.issue_slot(5, wnext);
                 bx.template issue_third<2>(seg_base, p.C, cs, cn, wave);
-                if (p.prio) __builtin_amdgcn_s_setprio(1);
+                __builtin_amdgcn_s_setprio(1);
                 wino_group<VT, 2>(Wl, Bl, off, l31, kh, acc);
                 __builtin_amdgcn_s_setprio(0);
             }
@@ -155,7 +155,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void tcn_stage_wino_kernel(const TcnPa
             wino_group<VT, 2>(Wl, Bl, off, l31, kh, acc);
         };
         // tiles whose staged span lies inside the sequence: 16-byte staging; the others (zero padding at either end) element-wise
-        const bool interior = p.vec_stage && fa >= 0 && fa * VT + 4 * ((span + 3) / 4) <= TV;     // uniform
+        const bool interior = fa >= 0 && fa * VT + 4 * ((span + 3) / 4) <= TV;     // uniform
         if (interior) {
             BStage4<(NJ + 3) / 4> b4;
             b4.setup(fa * VT, span, lane);
@@ -223,8 +223,6 @@ static int tcn_stage_wino_launch(const float *y, const float *w_wino, const floa
     p.Tin = t_in; p.Tout = t_in; p.V = V; p.K = k; p.stride = 1; p.pad = pad;
     p.res_mode = res_mode; p.Cres = c_res; p.CresPad = round_up(c_res, CSK_CPAD); p.Tres = t_res; p.res_off = 0; p.relu = relu;
     p.vmagic = vmagic_of(V); p.mtiles = (unsigned)mtiles; p.qtiles = (unsigned)qtiles; p.nt = qp;
-    p.prio = !csk_diag_flag("CSK_NOPRIO");
-    p.vec_stage = !csk_diag_flag("CSK_TCN_NOVEC");
     void (*kern)(TcnParams) = V == 25 ? tcn_stage_wino_kernel<25> : tcn_stage_wino_kernel<18>;
     const int ldb = V == 25 ? wino_ldb<25>() : wino_ldb<18>();
     p.ldb = ldb;

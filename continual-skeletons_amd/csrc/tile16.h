@@ -11,21 +11,6 @@ namespace {
 // resident; what counts is the largest number of tiles ONE CU has to run (tiles dealt evenly over the 256 CUs of an MI355X)
 // times the columns a 64-row tile carries (padding included).
 constexpr int64_t CUS = 256;
-// start stagger of the odd-slot workgroup in units of 64 cycles (stagger_odd_slot); CSK_*_STAGGER under CSK_DIAG=1 overrides
-// (value + 1: 1 = off)
-constexpr int GCN16_STAGGER = 0, TCN16_STAGGER = 0;       // swept in round 6: no effect (+- 0.1 %)
-inline int stagger_units(const char *env, int dflt) {
-    const int v = csk_diag_int(env);
-    return v > 0 ? v - 1 : dflt;
-}
-// which workgroup of a CU the issue arbiter favours inside the MFMA segments (step16.hip, tcn16_tile / gcn16_tile): 0 = equal
-// priorities (= the older one, always), 1 = alternating chunk by chunk, 2 = always the younger one; CSK_*_PRIO under CSK_DIAG=1
-// overrides (value + 1).  Round 6, 1024 NTU streams, same process: 985 -> 1 004 k frames/s (temporal step) -> 1 011 k (+ graph conv).
-constexpr int TCN16_PRIO = 1, GCN16_PRIO = 1;
-inline int prio_mode(const char *env, int dflt) {
-    const int v = csk_diag_int(env);
-    return v > 0 ? v - 1 : dflt;
-}
 inline double cost_model(int64_t tiles64, double tile_cols) { return (double)((tiles64 + CUS - 1) / CUS) * tile_cols; }
 
 constexpr int imax(int a, int b) { return a > b ? a : b; }
@@ -185,15 +170,6 @@ struct W16 {
         for (int u = 0; u < NSW; ++u) *reinterpret_cast<f32x4 *>(Wl + loff[u]) = v[u];
     }
 };
-
-// The two workgroups of a CU start together and do identical work: left alone they run in LOCKSTEP -- both in their
-// matrix-free phase (graph conv: aggregation; temporal step: commit + barriers) at the same time, the matrix pipe idle, then
-// both contending for it.  The workgroup in the odd wave slot of its SIMDs (HW_ID.wave_id) therefore starts `units` x 64
-// cycles late: one phase behind its partner, where it stays (matrix beside memory).  Speed only, never correctness.
-__device__ __forceinline__ void stagger_odd_slot(int units) {
-    if (units > 0 && (__builtin_amdgcn_s_getreg(6148) & 1))                     // HW_REG_HW_ID bits [3:0]: wave slot on the SIMD
-        for (int i = 0; i < units; ++i) __builtin_amdgcn_s_sleep(1);
-}
 
 // Operand reads AHEAD of their use.  Left to itself the scheduler emits `ds_read2_b32; s_waitcnt lgkmcnt(0); mfma; mfma` 13
 // times per tap: every MFMA pair waits for the LDS round trip of the read issued right in front of it, and a wave that has

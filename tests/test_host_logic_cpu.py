@@ -286,6 +286,28 @@ def test_no_kernel_spills():
     assert not spilling, spilling
 
 
+def test_environment_switches_are_only_the_kernel_family_selectors():
+    """Under CSK_DIAG=1 the library reads exactly five switches, each choosing between two production kernel families
+    that compute the same result; nothing in the sources times kernels from the inside or hands them a device address
+    parsed from the environment."""
+    import glob
+    srcs = sorted(glob.glob(os.path.join(ROOT, "continual-skeletons_amd", "csrc", "*.hip")) +
+                  glob.glob(os.path.join(ROOT, "continual-skeletons_amd", "csrc", "*.h")))
+    assert len(srcs) >= 10, srcs
+    names = set()
+    for path in srcs:
+        text = open(path).read()
+        assert "csk_diag_stamps" not in text and "s_memtime" not in text, path
+        if os.path.basename(path) in ("runtime.hip", "mfma_core.h"):       # the definitions and their declarations
+            continue
+        # every call names its switch as a literal: a forwarding helper (csk_diag_int(env)) would hide the switches it reads
+        calls = re.findall(r"csk_diag_(?:flag|int)\(\s*([^)]*)\)", text)
+        literal = [re.fullmatch(r'"([A-Z0-9_]+)"\s*', a) for a in calls]
+        assert all(literal), (path, calls)
+        names |= {m.group(1) for m in literal}
+    assert names == {"CSK_TCN16", "CSK_GCN16", "CSK_TCN_WINO", "CSK_GCN_GENERAL", "CSK_STEP16"}, sorted(names)
+
+
 def test_split_weight_packing_reconstructs_the_fp32_weights():
     """fold.pack_conv_weight_split (operand image of csk_tcn_stage_bf16x3): the three bf16 pieces of every element sum back
     to the fp32 weight the exact path packs (24 significand bits), the nine taps sit in class-major order (residue classes

@@ -1,7 +1,7 @@
 """Interleaved in-process A/B of a diagnostic env switch on the A-GCN clip forward (Kinetics shape, batch 64).
-usage: python tools/ab_agcn_probe.py CSK_SLOW_EPI | CSK_TCN16=2"""
+usage: python tools/ab_agcn_probe.py CSK_TCN16=2 | CSK_TCN16=1 | CSK_GCN_GENERAL"""
 import os, sys, time, statistics
-VAR = sys.argv[1] if len(sys.argv) > 1 else "CSK_SLOW_EPI"
+VAR = sys.argv[1] if len(sys.argv) > 1 else "CSK_TCN16=2"
 VAR, VAL = VAR.split("=") if "=" in VAR else (VAR, "1")
 os.environ["CSK_DIAG"] = "1"
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

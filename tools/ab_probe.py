@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Interleaved in-process A/B of a diagnostic env switch on the TCN stage (guide rule 24).
-usage: python tools/ab_probe.py CSK_NOPRIO [BASE_VAR ...]  -- BASE_VARs are set in BOTH arms (e.g. CSK_TCN_NOLW)"""
+usage: python tools/ab_probe.py CSK_TCN16[=2] [BASE_VAR ...]  -- BASE_VARs are set in BOTH arms (e.g. CSK_TCN_WINO)"""
 import os, sys
 os.environ["CSK_DIAG"] = "1"
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
