@@ -9,7 +9,8 @@ import torch
 
 import _bootstrap
 from oracle import stgcn_oracle as o
-from tests.helpers import check_parity, g6_state_dict, randomise_unit_
+from tests import str_oracle as so
+from tests.helpers import check_parity, g6_state_dict, model_fixture, randomise_unit_
 
 pytestmark = pytest.mark.gpu
 pkg = _bootstrap.load()
@@ -223,3 +224,71 @@ def test_config5_per_gpu_shard_of_1024_clips():
     assert full.shape == (1024, 60) and bool(torch.isfinite(full).all())
     for lo in (0, 768):
         assert torch.equal(net(x[lo:lo + 256].contiguous()), full[lo:lo + 256])
+
+
+def test_str_batch256_clip_forward():
+    """S-TR clip forward, batch 256, NTU-60 shape (512 segments x 7500 columns in layer 4, 2.4 GB of unit scratch): logits of a
+    32-clip slice vs the oracle with the attention unit as the graph conv of layers 4-10, and batch invariance over all 256 clips."""
+    a, sd, _ = model_fixture("g12_str_ntu", 25)
+    net = pkg.STr(A).eval()
+    net.load_state_dict(sd, strict=True)
+    net = net.to(DEV)
+    x = torch.rand((256, 3, 300, 25, 2), device=DEV, generator=torch.Generator(device=DEV).manual_seed(11))
+    full = net(x)
+    assert full.shape == (256, 60) and bool(torch.isfinite(full).all())
+    idx = [0, 1, 254, 255] + list(range(5, 256, 9))[:28]          # 32 clips spread over the batch, both ends included
+    assert len(idx) == 32 == len(set(idx))
+    with torch.no_grad():
+        want = o.stgcn_forward(x[idx].cpu(), sd, gcn=so.gcn)
+    check_parity(full[idx].cpu(), want, note="STr batch 256")
+    for lo in range(0, 256, 64):                                  # batch invariance, bitwise
+        part = net(x[lo:lo + 64].contiguous())
+        assert torch.equal(part, full[lo:lo + 64])
+
+
+def _costr_1024_streams(v, classes, fixture, seed, pick, sel):
+    """CoS-TR online inference with 1024 concurrent streams in 4-frame cycles: predictions of 8 streams vs the oracle stepping
+    those streams alone (CoStGcnOracle with the attention unit as every block's graph conv), and stream invariance (bitwise)
+    against a 4-stream model stepped frame by frame."""
+    graph = A if v == 25 else pkg.kinetics_graph().A
+    a, sd, _ = model_fixture(fixture, v)
+    T = 76 + 4 * 4 + 1
+
+    def make():
+        net = pkg.CoSTr(graph, (3, 300, v, 2), classes, pool_size=3, pool_padding=1).eval()
+        net.load_state_dict(net.map_state_dict(sd), strict=True)
+        return net.to(DEV)
+    frames = torch.rand((T, 1024, 3, v, 2), device=DEV, generator=torch.Generator(device=DEV).manual_seed(seed))
+    big = make()
+    got, t = [], 0
+    while t < T:
+        r = min(4, T - t)
+        got += big.forward_cycle([frames[t + f] for f in range(r)])
+        t += r
+    assert len(got) >= 3 and all(gv.shape == (1024, classes) for gv in got)
+    orc = o.CoStGcnOracle(sd, pool_size=3, pool_padding=1)
+    for b in orc.blocks:
+        b.gcn = so.gcn
+    want = []
+    with torch.no_grad():
+        for t in range(T):
+            r = orc.forward_step(frames[t][pick].cpu())
+            if r is not None:
+                want.append(r)
+    assert len(want) == len(got)
+    for gv, wv in zip(got, want):
+        check_parity(gv[pick].cpu(), wv, note=f"CoSTr 1024 streams V={v}")
+    small = make()
+    got_small = [r for r in (small.forward_step(frames[t][sel].contiguous()) for t in range(T)) if r is not None]
+    assert len(got_small) == len(got)
+    for gv, sv in zip(got, got_small):
+        assert torch.equal(gv[sel], sv)
+
+
+def test_costr_1024_streams_online():
+    _costr_1024_streams(25, 60, "g12_str_ntu", 12, pick=[0, 5, 255, 256, 511, 777, 1000, 1023], sel=[5, 6, 999, 1000])
+
+
+def test_costr_1024_streams_kinetics_shape():
+    """The same at Kinetics shape (V = 18, 400 classes): 36 864 ring columns per slot, 18-joint attention."""
+    _costr_1024_streams(18, 400, "g12_str_kin", 13, pick=[0, 7, 340, 341, 682, 683, 1001, 1023], sel=[7, 8, 1001, 1023])

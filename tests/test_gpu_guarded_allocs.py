@@ -7,7 +7,7 @@ import pytest
 import torch
 
 import _bootstrap
-from tests.helpers import guarded_allocs
+from tests.helpers import guarded_allocs, randomise_unit_
 
 pytestmark = pytest.mark.gpu
 pkg = _bootstrap.load()
@@ -93,6 +93,84 @@ def test_continual_stepping_with_guarded_buffers(model, native_plan, latency):
             with guarded_allocs() as ga:
                 outs.append(run())
             assert ga.count >= 3, ga.count           # the state slab, the pooling ring, per-cycle buffers
+        else:
+            outs.append(run())
+    assert len(outs[0]) == len(outs[1]) and len(outs[0]) >= 1
+    for a, b in zip(*outs):
+        assert bool(torch.isfinite(b).all()), "a kernel read outside a buffer"
+        assert torch.equal(a, b)
+
+
+class _StageSpy:
+    """Records, for every GcnUnitAttention.stage call, how many guarded allocations were made inside it (its per-call scratch
+    is the only buffer stage allocates)."""
+
+    def __init__(self, monkeypatch, ga):
+        self.inside = []
+        real = pkg.GcnUnitAttention.stage
+        spy = self
+
+        def stage(unit, *args, **kw):
+            before = ga.count
+            real(unit, *args, **kw)
+            spy.inside.append(ga.count - before)
+        monkeypatch.setattr(pkg.GcnUnitAttention, "stage", stage)
+
+
+@pytest.mark.parametrize("mode", ["default", "latency"])
+def test_str_clip_forward_with_guarded_buffers(mode, monkeypatch):
+    """S-TR clip forward: activations and the unit's qkv / attention scratch between NaN guards."""
+    x = torch.rand((3, 3, 52, 25, 2), generator=torch.Generator().manual_seed(4)).to(DEV)
+    outs = []
+    for guard in (False, True):
+        net = pkg.STr(pkg.ntu_graph().A).eval()
+        randomise_unit_(net, 3)
+        net = net.to(DEV)
+        if mode == "latency":
+            net.set_latency_mode(4)
+        if guard:
+            with guarded_allocs() as ga:
+                spy = _StageSpy(monkeypatch, ga)
+                outs.append(net(x).cpu())
+            monkeypatch.undo()
+            assert len(spy.inside) == 7 and min(spy.inside) >= 1, spy.inside     # the scratch of each attention layer
+            assert ga.count >= 20 + 7, ga.count
+        else:
+            outs.append(net(x).cpu())
+    assert bool(torch.isfinite(outs[1]).all()), "a kernel read outside a buffer"
+    assert torch.equal(outs[0], outs[1])
+
+
+def test_costr_stepping_with_guarded_buffers(monkeypatch):
+    """CoS-TR on the Python step engine, 7 streams (a ragged tile), 104 frames: single frames, then 4-frame cycles; slab, the unit's
+    per-call scratch and every other per-call buffer guarded."""
+    frames = torch.rand((104, 7, 3, 25, 2), generator=torch.Generator().manual_seed(5)).to(DEV)
+    outs = []
+    for guard in (False, True):
+        net = pkg.CoSTr(pkg.ntu_graph().A, pool_size=2, pool_padding=0).eval()
+        randomise_unit_(net, 3)
+        net = net.to(DEV)
+
+        def run():
+            got = []
+            for t in range(8):
+                o = net.forward_step(frames[t])
+                if o is not None:
+                    got.append(o.cpu())
+            for c in range(24):
+                for o in net.forward_cycle([frames[8 + 4 * c + f] for f in range(4)]):
+                    got.append(o.cpu())
+            return got
+
+        if guard:
+            with guarded_allocs() as ga:
+                spy = _StageSpy(monkeypatch, ga)
+                outs.append(run())
+            monkeypatch.undo()
+            assert "_plan" not in net.__dict__                                      # the Python step engine
+            # layer 4 runs its unit on every one of the 8 + 24 calls; each call of each layer allocated its scratch under the hook
+            assert len(spy.inside) >= 7 + 32 and min(spy.inside) >= 1, spy.inside
+            assert ga.count >= 3 + len(spy.inside), ga.count
         else:
             outs.append(run())
     assert len(outs[0]) == len(outs[1]) and len(outs[0]) >= 1

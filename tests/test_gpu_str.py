@@ -68,6 +68,7 @@ def test_stage_on_ring_slots_equals_clip_form(ci, co, v):
     m.stage(ring[3], yr[3], n_seg=2, frames=n, x_strides=(ci * p, p), y_strides=(co * p, p))
     got = yr[:, :, : n * v].reshape(s, co, n, v).permute(2, 1, 0, 3).cpu()
     check_parity(got, clip.cpu(), tol=1e-6, note="ring slots vs clip")
+    assert torch.equal(got, clip.cpu())            # the K order per column is fixed: a column does not depend on its place
     assert torch.isnan(yr[:, :, n * v:]).all()                                     # nothing written past frames * V
 
 
