@@ -7,7 +7,10 @@
 //   gcn.hip       gcn_stage_* kernels   + csk_gcn_stage_f32        (GCN stage: sparse fast path + general)
 //   agcn.hip      agcn_attention_kernel + csk_agcn_attention_f32   (A-GCN per-sample adjacency)
 //   head.hip      input norm / pooling / FC kernels and entry points
-//   step.hip      continual path: tcn_step_kernel, spatial pool, window mean, logit fusion
+//   step.hip      continual path, 32x32x2 tiles: tcn_step_kernel + csk_tcn_step_f32 (what step16.hip does not take: split-K,
+//                 k != 9, rings >= 4 GB), split-K reduce, spatial pool, window mean, logit fusion
+//   step16.hip    continual path, slot-balanced 16x16x4 tiles: temporal step, graph conv, and the fused block / stack step
+//                 (csk_co_block_step_f32, csk_co_stack_step_f32)
 //   executor.hip  native step executor (csk_co_plan_*)
 #include <stdlib.h>
 #include <string.h>
@@ -38,13 +41,12 @@ extern "C" int csk_abi_version(void) { return CSK_ABI_VERSION; }
 extern "C" const char *csk_last_error(void) { return g_err; }
 
 // Kernel-family switches, read from the environment per call only when CSK_DIAG is set at library load (so that the normal
-// launch path never touches the environment).  Each picks between two production kernel families that compute the same
-// result, for A/B runs and as references in the tests:
+// launch path never touches the environment).  Each of the four picks between two production kernel families that compute
+// the same result, for A/B runs and as references in the tests:
 //   CSK_TCN16=1 / =2   the clip temporal conv never / wherever supported on the 16x16x4 family (tcn16.hip)
 //   CSK_GCN16=1 / =2   the graph conv never / wherever supported on the 16x16x4 family (step16.hip)
 //   CSK_TCN_WINO=1     the direct temporal conv instead of the Winograd kernel (tcn_wino.hip)
 //   CSK_GCN_GENERAL=1  the general (dense-capable) GCN kernel instead of the skeleton-sparse one (gcn.hip)
-//   CSK_STEP16=1       the continual step on the 32x32x2 kernels everywhere (step16.hip)
 static const bool g_diag = getenv("CSK_DIAG") != nullptr;
 bool csk_diag_flag(const char *name) { return g_diag && getenv(name) != nullptr; }
 int csk_diag_int(const char *name) {

@@ -9,9 +9,12 @@
 // (C_out = 256, four m-tiles): with 16-wide MFMA blocks every launch of the cycle is EXACTLY 512 workgroups of equal work =
 // one full round at two workgroups per CU (Kinetics: P = 512 x 72, NB = 18).  v_mfma_f32_16x16x4_f32 has the rate of
 // v_mfma_f32_32x32x2_f32 (64 FLOP / clk / SIMD, MI355X_MICROARCH.md) and is the same fmaf chain in ascending k
-// (tools/microbench/mfma16_order_probe.hip), so the kernels here are BITWISE interchangeable with the ones they stand in
-// for: the K loop visits (chunk, tap, channel) in the same order, the epilogue is the same expression.  Which family a
-// launch gets is therefore a pure throughput policy of the launch shape (csk_step16_wins below).
+// (tools/microbench/mfma16_order_probe.hip).  What that makes of the two kernels of the family (see "dispatch" below):
+//   graph conv     walks its K rows in the order of gcn_stage_sparse2_kernel with the same epilogue expression: BITWISE the
+//                  32x32x2 kernel, so which of the two a launch gets is a throughput policy of the launch shape;
+//   temporal step  walks (4-channel chunk, tap) where the 32x32x2 kernel walks (8-channel chunk, tap): its OWN fp32 summation
+//                  order, so which of the two a launch gets is a function of (k, ksplit, ring size) only, never of the launch
+//                  size -- a stream's results must not depend on how many streams share the slab.
 //
 // Wave tile: a wave owns 16 output channels (wave w: rows 16 w ..) and ALL NB column blocks: 4 NB accumulator registers.
 // The MFMA is issued "transposed" -- A = activations (16 positions x 4 channels), B = weights (4 channels x 16 output
@@ -415,15 +418,11 @@ int launch16(StepParams p, int n_emit, hipStream_t s) {
 }  // namespace
 
 // ---- dispatch ------------------------------------------------------------------------------------------------------------
-// CSK_STEP16 (under CSK_DIAG=1): 1 = never (the 32x32x2 kernels everywhere: A/B runs).
 // Temporal step: the K loop of this family walks (4-channel chunk, tap) where the 32x32x2 kernels walk (8-channel chunk, tap) --
 // a different fp32 summation order -- so WHICH family runs must not depend on the launch size (a stream's results must not
 // depend on how many streams share the slab, nor on how many frames a launch carries): every k = 9, unsplit launch whose
 // rings fit 32-bit byte offsets takes this family; only the tile WIDTH (NB) follows the launch shape.
-int csk_step16_enabled() { return csk_diag_int("CSK_STEP16") != 1; }
-
 int csk_launch_tcn_step16(StepParams p, int n_emit, void *stream) {
-    if (!csk_step16_enabled()) return -2;
     if (p.K != 9 || p.ksplit != 1 || p.head_step < 1 || p.head_step > 2) return -2;
     // 32-bit byte offsets inside the rings
     const int64_t ring_bytes = (int64_t)p.slots * p.C * p.P * 4, xres_bytes = (int64_t)p.xres_slots * p.Cres * p.P * 4;
@@ -449,7 +448,7 @@ int csk_launch_tcn_step16(StepParams p, int n_emit, void *stream) {
 // where the cost model says the launch packs the chip better (CSK_GCN16=2 under CSK_DIAG=1: whenever the shape is supported).
 int csk_launch_gcn16(GcnParams p, int n_seg, void *stream) {
     const int mode = csk_diag_int("CSK_GCN16");
-    if (!csk_step16_enabled() || mode == 1) return -2;
+    if (mode == 1) return -2;
     if (p.adj_seg_stride != 0 || p.ksplit != 1 || p.ell_cnt[0] > 1 || p.ell_cnt[1] > 1 || p.ell_cnt[2] > 4) return -2;
     if ((p.x_seg_stride | p.x_chan_stride | p.y_seg_stride | p.y_chan_stride) & 3) return -2;
     if (((uintptr_t)p.x | (uintptr_t)p.y) & 15) return -2;
@@ -479,9 +478,8 @@ int csk_launch_gcn16(GcnParams p, int n_seg, void *stream) {
 }
 
 // ---- stack of 64-channel blocks ------------------------------------------------------------------------------------------
-// -2: not a shape the fused stack is built for (the caller issues the per-stage launches)
+// -2: not a shape the fused stack is built for (the caller issues the per-stage launches).  The blocks have passed check_co_block.
 int csk_launch_co_stack16(int n_blocks, const csk_co_block_args *b, int n_skel, int V, int64_t P, void *stream) {
-    if (!csk_step16_enabled()) return -2;
     if (n_blocks < 1 || n_blocks > CSK_CO_STACK_MAX || P < 8 || (P & 3)) return -2;
     const int64_t Q = (int64_t)n_skel * V;
     int best_nb = 0;
@@ -535,35 +533,86 @@ int csk_launch_co_stack16(int n_blocks, const csk_co_block_args *b, int n_skel, 
     return (int)hipGetLastError();
 }
 
+// ---- fused block step: C ABI ----------------------------------------------------------------------------------------------
+// What csk_co_block_step_f32 and every block of csk_co_stack_step_f32 must satisfy (include/cskel.h): 0, or -1 with the message
+// set.  Nothing reaches a kernel or the per-stage entry points before it passed.
+static int check_co_block(const csk_co_block_args &a, int n_skel, int V, int64_t P) {
+    if (!a.xin || !a.gcn_w || !a.gcn_bias || !a.ell_src || !a.ell_val || !a.y_ring || !a.tcn_w || !a.tcn_bias || !a.out)
+        CSK_FAIL("co_block_step: null pointer");
+    if (a.c_in <= 0 || a.c_out <= 0 || a.c_out > 64 || n_skel <= 0 || V < 2 || V > 64 || P < (int64_t)n_skel * V || (P & 3) || P < 4)
+        CSK_FAIL("co_block_step: bad dims (c_out <= 64, P a multiple of 4 holding n_skel * V positions)");
+    if (P >= (1ll << 31) - 256) CSK_FAIL("co_block_step: P too large");
+    if (a.xin_slots < 8 || a.y_slots < 12 || a.out_slots < 4) CSK_FAIL("co_block_step: rings too shallow for a 4-frame cycle");
+    if (a.xin_slot0 < 0 || a.xin_slot0 >= a.xin_slots || a.y_slot0 < 0 || a.y_slot0 >= a.y_slots || a.out_slot0 < 0 ||
+        a.out_slot0 >= a.out_slots || a.x_res_slot0 < 0 || a.x_res_slot0 >= a.xin_slots)
+        CSK_FAIL("co_block_step: slot index out of range");
+    if (a.gcn_res_mode != CSK_RES_IDENTITY && a.gcn_res_mode != CSK_RES_CONV) CSK_FAIL("co_block_step: gcn_res_mode must be identity or conv");
+    if (a.gcn_res_mode == CSK_RES_IDENTITY && a.c_in != a.c_out) CSK_FAIL("co_block_step: identity gcn residual needs c_in == c_out");
+    if (a.res_mode != CSK_RES_NONE && a.res_mode != CSK_RES_IDENTITY) CSK_FAIL("co_block_step: block residual must be none or identity");
+    if (a.res_mode == CSK_RES_IDENTITY && a.c_in != a.c_out) CSK_FAIL("co_block_step: identity block residual needs c_in == c_out");
+    if (a.ell_w < 1 || a.ell_w > V || a.ell_cnt[0] < 0 || a.ell_cnt[0] > 1 || a.ell_cnt[1] < 0 || a.ell_cnt[1] > 1 || a.ell_cnt[2] < 0 ||
+        a.ell_cnt[2] > 4 || a.ell_cnt[2] > a.ell_w)
+        CSK_FAIL("co_block_step: needs a skeleton-sparse adjacency (<= 1/1/4 non-zeros per column)");
+    if (((uintptr_t)a.xin | (uintptr_t)a.y_ring | (uintptr_t)a.out) & 15) CSK_FAIL("co_block_step: state pointers must be 16-byte aligned");
+    // a bound of the contract, not of a kernel here: the callers choose the fused step by the same expression
+    // (continual.py:_fusable, executor.hip:fusable_cycle), so a V they would never send stays an argument error
+    if (((64 + V - 2) / V + 1) * V > 128)
+        CSK_FAIL("co_block_step: %d joints per skeleton make the input strip of a 64-position tile longer than 128", V);
+    return 0;
+}
+
+// The 4-frame cycle of one checked block: the fused launch where the tile family covers the shape, else the family's two stages
+// -- one graph-conv launch per non-wrapping slot run, then the four emitting temporal steps.  The same kernels on the same
+// operands either way: a block gives the same bits however its cycle is launched.
+static int co_block_cycle(const csk_co_block_args &a, int n_skel, int V, int64_t P, void *stream) {
+    const int rc1 = csk_launch_co_stack16(1, &a, n_skel, V, P, stream);
+    if (rc1 != -2) return rc1;
+    for (int f = 0; f < 4;) {
+        const int xs = (a.xin_slot0 + f) % a.xin_slots, ys = (a.y_slot0 + f) % a.y_slots;
+        int run = 4 - f;
+        if (run > a.xin_slots - xs) run = a.xin_slots - xs;
+        if (run > a.y_slots - ys) run = a.y_slots - ys;
+        if (const int rc = csk_gcn_stage_f32(a.xin + (int64_t)xs * a.c_in * P, a.y_ring + (int64_t)ys * a.c_out * P, a.gcn_w, a.gcn_bias,
+                                             a.ell_src, a.ell_val, a.ell_cnt, a.ell_w, 0, 0, run, a.c_in, a.c_out, n_skel, V,
+                                             (int64_t)a.c_in * P, P, (int64_t)a.c_out * P, P, a.gcn_res_mode, stream))
+            return rc;
+        f += run;
+    }
+    return csk_tcn_step_f32(a.y_ring, a.y_slots, a.y_slot0, 1, 4, a.tcn_w, a.res_mode ? a.xin : nullptr, a.xin_slots, a.x_res_slot0, 1,
+                            nullptr, a.tcn_bias, a.out, a.out_slots, a.out_slot0, a.c_out, a.c_out, P, 9, a.res_mode,
+                            a.res_mode ? a.c_in : 0, 1, 1, nullptr, stream);
+}
+
+extern "C" int csk_co_block_step_f32(const float *xin, int xin_slots, int xin_slot0, int c_in, const float *gcn_w,
+                                     const float *gcn_bias, const int32_t *ell_src, const float *ell_val,
+                                     const int32_t *ell_cnt, int ell_w, int gcn_res_mode, float *y_ring, int y_slots,
+                                     int y_slot0, const float *tcn_w, const float *tcn_bias, int res_mode, int x_res_slot0,
+                                     float *out, int out_slots, int out_slot0, int c_out, int n_skel, int V, int64_t P,
+                                     void *stream) {
+    if (!ell_cnt) CSK_FAIL("co_block_step: null pointer");
+    csk_co_block_args a;
+    a.xin = xin; a.xin_slots = xin_slots; a.xin_slot0 = xin_slot0; a.c_in = c_in; a.gcn_w = gcn_w; a.gcn_bias = gcn_bias;
+    a.ell_src = ell_src; a.ell_val = ell_val; a.ell_cnt[0] = ell_cnt[0]; a.ell_cnt[1] = ell_cnt[1]; a.ell_cnt[2] = ell_cnt[2];
+    a.ell_w = ell_w; a.gcn_res_mode = gcn_res_mode; a.y_ring = y_ring; a.y_slots = y_slots; a.y_slot0 = y_slot0; a.tcn_w = tcn_w;
+    a.tcn_bias = tcn_bias; a.res_mode = res_mode; a.x_res_slot0 = x_res_slot0; a.out = out; a.out_slots = out_slots;
+    a.out_slot0 = out_slot0; a.c_out = c_out;
+    if (const int rc = check_co_block(a, n_skel, V, P)) return rc;
+    return co_block_cycle(a, n_skel, V, P, stream);
+}
+
 extern "C" int csk_co_stack_step_f32(int n_blocks, const csk_co_block_args *b, int n_skel, int V, int64_t P, void *stream) {
     if (!b || n_blocks < 1 || n_blocks > CSK_CO_STACK_MAX) CSK_FAIL("co_stack_step: 1..%d blocks expected", CSK_CO_STACK_MAX);
     for (int i = 0; i + 1 < n_blocks; ++i)
         if (b[i + 1].xin != b[i].out || b[i + 1].xin_slots != b[i].out_slots || b[i + 1].xin_slot0 != b[i].out_slot0 ||
             b[i + 1].c_in != b[i].c_out)
             CSK_FAIL("co_stack_step: block %d does not read what block %d emits (ring, slot count, first slot, channels)", i + 1, i);
-    bool fusable = true;                                      // what csk_co_block_step_f32 would reject must not reach the kernel
-    for (int i = 0; i < n_blocks && fusable; ++i) {
-        const csk_co_block_args &a = b[i];
-        fusable = a.xin && a.gcn_w && a.gcn_bias && a.ell_src && a.ell_val && a.y_ring && a.tcn_w && a.tcn_bias && a.out && a.c_in > 0 &&
-                  a.c_out > 0 && n_skel > 0 && V >= 2 && V <= 64 && P >= (int64_t)n_skel * V && !(P & 3) && P < (1ll << 31) - 256 &&
-                  a.xin_slots >= 8 && a.y_slots >= 12 && a.out_slots >= 4 && a.xin_slot0 >= 0 && a.xin_slot0 < a.xin_slots &&
-                  a.y_slot0 >= 0 && a.y_slot0 < a.y_slots && a.out_slot0 >= 0 && a.out_slot0 < a.out_slots && a.x_res_slot0 >= 0 &&
-                  a.x_res_slot0 < a.xin_slots && (a.gcn_res_mode == CSK_RES_IDENTITY || a.gcn_res_mode == CSK_RES_CONV) &&
-                  (a.gcn_res_mode != CSK_RES_IDENTITY || a.c_in == a.c_out) && (a.res_mode == CSK_RES_NONE || a.res_mode == CSK_RES_IDENTITY) &&
-                  (a.res_mode != CSK_RES_IDENTITY || a.c_in == a.c_out) && a.ell_w >= 1 && a.ell_w <= V && a.ell_cnt[0] >= 0 &&
-                  a.ell_cnt[1] >= 0 && a.ell_cnt[2] >= 0 && a.ell_cnt[2] <= a.ell_w &&
-                  !(((uintptr_t)a.xin | (uintptr_t)a.y_ring | (uintptr_t)a.out) & 15);
-    }
-    if (fusable && n_blocks > 1) {
+    for (int i = 0; i < n_blocks; ++i)
+        if (const int rc = check_co_block(b[i], n_skel, V, P)) return rc;
+    if (n_blocks > 1) {
         const int rc = csk_launch_co_stack16(n_blocks, b, n_skel, V, P, stream);
         if (rc != -2) return rc;
     }
-    for (int i = 0; i < n_blocks; ++i) {                      // per block (argument errors are reported from there)
-        const csk_co_block_args &a = b[i];
-        if (const int rc = csk_co_block_step_f32(a.xin, a.xin_slots, a.xin_slot0, a.c_in, a.gcn_w, a.gcn_bias, a.ell_src, a.ell_val, a.ell_cnt,
-                                                 a.ell_w, a.gcn_res_mode, a.y_ring, a.y_slots, a.y_slot0, a.tcn_w, a.tcn_bias, a.res_mode,
-                                                 a.x_res_slot0, a.out, a.out_slots, a.out_slot0, a.c_out, n_skel, V, P, stream))
-            return rc;
-    }
+    for (int i = 0; i < n_blocks; ++i)
+        if (const int rc = co_block_cycle(b[i], n_skel, V, P, stream)) return rc;
     return 0;
 }

@@ -19,9 +19,9 @@ struct StepParams {
 };
 
 // step16.hip: the slot-balanced tile family (64 channels x 16*NB columns, v_mfma_f32_16x16x4_f32).  Both return -2 when the
-// launch shape is not one they are built for or the policy prefers the 32x32x2 kernels (the caller then launches those);
-// otherwise the launch status.  Bitwise the same results as the kernels they stand in for (same fp32 summation order).
+// launch is not one they take (the caller then launches the 32x32x2 kernels / the per-stage launches); otherwise the launch
+// status.  The family's temporal step has its own fp32 summation order (4-channel chunks where the 32x32x2 kernel walks 8), so
+// it takes a launch by (k, ksplit, ring size) only, never by the launch size.
 int csk_launch_tcn_step16(StepParams p, int n_emit, void *stream);
-int csk_step16_enabled();   // 0 only under CSK_DIAG=1 CSK_STEP16=1 (A/B runs)
-// fused stack of 64-channel blocks (csk_co_stack_step_f32); -2: shape not supported / switched off
+// fused stack of 64-channel blocks (csk_co_block_step_f32 / csk_co_stack_step_f32); -2: shape not supported
 int csk_launch_co_stack16(int n_blocks, const csk_co_block_args *blocks, int n_skel, int V, int64_t P, void *stream);

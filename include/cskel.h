@@ -300,11 +300,14 @@ int csk_tcn_step_f32(const float *ring, int slots, int head, int head_step, int 
                      void *stream);
 
 /*
- * One CoSpatioTemporalBlock.forward_step cycle in ONE launch (models/base.py:412-446): graph conv of the 4 new frames of
+ * One CoSpatioTemporalBlock.forward_step cycle in one call (models/base.py:412-446): graph conv of the 4 new frames of
  * a stride cycle + the 4 emitting steps of the temporal conv + residual + ReLU -- csk_gcn_stage_f32 followed by
- * csk_tcn_step_f32 with n_emit = 4, fused (same arithmetic, same summation order, bit-identical results).  For blocks
- * with c_out <= 64, temporal stride 1, k = 9, a skeleton-sparse adjacency (ell_cnt <= 1/1/4) and a block residual that
- * is absent (CSK_RES_NONE) or the identity; all 4 frames must emit (the block has seen >= 4 frames before).
+ * csk_tcn_step_f32 with n_emit = 4.  ONE launch where the slot-balanced tile family covers the shape (csrc/step16.hip:
+ * identity gcn_residual, V dividing a tile of 100 or 72 positions (25, 18), c_out a multiple of 16, rings below 4 GB),
+ * else that family's two launches: the same arithmetic in the same summation order, bit-identical results either way.
+ * For blocks with c_out <= 64, temporal stride 1, k = 9, a skeleton-sparse adjacency (ell_cnt <= 1/1/4) and a block
+ * residual that is absent (CSK_RES_NONE) or the identity; all 4 frames must emit (the block has seen >= 4 frames
+ * before).  Arguments are checked before anything is launched (-1 and csk_last_error()).
  *  xin     block input ring [xin_slots][c_in][P]; new frame f = 0..3 in slot (xin_slot0 + f) mod xin_slots; the residual
  *          frame of emission j in slot (x_res_slot0 + j) mod xin_slots (the input delayed by 4 frames)
  *  y_ring  [y_slots][c_out][P] post-GCN frames, y_slots >= 12; new frame f is WRITTEN to slot (y_slot0 + f) mod y_slots,
@@ -325,7 +328,9 @@ int csk_co_block_step_f32(const float *xin, int xin_slots, int xin_slot0, int c_
  * its new frames the slots block i emits into.  A workgroup owns the same positions (whole skeletons) of the four frames
  * through every block: no workgroup depends on another (step mode has no temporal halo), stage outputs travel through the
  * state rings and L2.  Bitwise the results of the per-block calls.  Needs the slot-balanced tile family (csrc/step16.hip:
- * V = 25 or 18 joints, c_out a multiple of 4, rings below 4 GB); otherwise (or with one block) it IS the per-block calls.
+ * the shapes named at csk_co_block_step_f32); otherwise (or with one block) it issues the launches of the per-block calls.
+ * Every block is checked as csk_co_block_step_f32 checks its arguments BEFORE anything is launched: an invalid block i
+ * fails the call without the blocks in front of it having been launched.
  */
 #define CSK_CO_STACK_MAX 4
 typedef struct csk_co_block_args {          /* the arguments of csk_co_block_step_f32 that differ per block */

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Interleaved in-process sweep of diagnostic env settings on the online path (CoST-GCN, 1024 streams, one stream shard by
 default): every configuration is timed in turn, several rounds, medians reported.  The library reads the switches per launch.
-usage: python tools/ab_env_sweep.py [--shards 1] [--model costgcn|coagcn] "CSK_STEP16=1" "CSK_GCN16=1" "CSK_GCN16=2" ...
+usage: python tools/ab_env_sweep.py [--shards 1] [--model costgcn|coagcn] "" "CSK_GCN16=1" "CSK_GCN16=2" ...
 (the empty string "" is the default configuration)"""
 import argparse, os, statistics, sys, time
 os.environ["CSK_DIAG"] = "1"

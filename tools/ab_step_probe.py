@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Interleaved in-process A/B of a diagnostic env switch on the whole online path (CoST-GCN, 1024 streams, 2 shards).
-usage: python tools/ab_step_probe.py CSK_STEP16 | CSK_GCN16=1"""
+usage: python tools/ab_step_probe.py CSK_GCN16=1 | CSK_GCN16=2"""
 import os, sys, time, statistics
 os.environ["CSK_DIAG"] = "1"
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
