@@ -127,11 +127,18 @@ class CoTemporalConvolution(TemporalConvolution):
         return torch.stack(outs, dim=2)
 
 
+def _counter(i, doc):
+    """Attribute that IS element ``i`` of the owner's ctypes counter array ``_ctr`` (no copy to keep in step)."""
+    return property(lambda self: self._ctr[i], lambda self, value: self._ctr.__setitem__(i, value), doc=doc)
+
+
 class _BlockState:
-    """Slice of the state slab owned by one block: y ring, output ring, (optionally own) input ring, counters."""
+    """Slice of the state slab owned by one block: y ring, output ring, (optionally own) input ring, counters.
+    ``counters``: the block's (received, emitted) pair inside its model's counter buffer (CoStGcn._bind); a stand-alone
+    block makes its own."""
 
     def __init__(self, c_in, c_out, k, p, device, xin=None, ksplit=1, max_emit=MAX_CYCLE, scratch=None, max_in=MAX_CYCLE,
-                 out_slots=None, gcn_ksplit=1):
+                 out_slots=None, gcn_ksplit=1, counters=None):
         self.p = p
         self.ksplit = ksplit
         self.gcn_ksplit = gcn_ksplit      # split-K of the graph conv (latency mode); shares the partial-sum buffer
@@ -159,8 +166,10 @@ class _BlockState:
         self.xin = torch.zeros((in_slots(max_in), c_in, p), device=device, dtype=torch.float32) if xin is None else xin
         if self.xin.shape[0] < in_slots(max_in):
             raise ValueError(f"input ring of {self.xin.shape[0]} slots is too shallow for launches of {max_in} frames")
-        self.s = 0      # frames received
-        self.e = 0      # frames emitted
+        self._ctr = (ctypes.c_int64 * 2)() if counters is None else counters
+
+    s = _counter(0, "frames received")
+    e = _counter(1, "frames emitted")
 
     def zero_(self):
         self.y.zero_()
@@ -244,13 +253,15 @@ class CoSpatioTemporalBlock(SpatioTemporalBlock):
 
     # ---- persistent state --------------------------------------------------------------------------
     def bind_state(self, p: int, device, xin: Optional[torch.Tensor] = None, max_emit: int = MAX_CYCLE,
-                   scratch: Optional[torch.Tensor] = None, max_in: int = MAX_CYCLE, out_slots: Optional[int] = None) -> _BlockState:
+                   scratch: Optional[torch.Tensor] = None, max_in: int = MAX_CYCLE, out_slots: Optional[int] = None,
+                   counters=None) -> _BlockState:
         """(Re)allocate this block's slab slice for P positions; ``xin`` = upstream block's output ring; ``max_in`` /
         ``max_emit`` = frames one launch of this block can receive / emit; ``out_slots`` = depth of the output ring (what
-        the consuming block needs as its input history); ``scratch`` = split-K scratch shared with the other blocks."""
+        the consuming block needs as its input history); ``scratch`` = split-K scratch shared with the other blocks;
+        ``counters`` = this block's pair of the model's counter buffer."""
         self._state = _BlockState(self.in_channels, self.out_channels, self.kernel_size, p, device, xin,
                                   ksplit=self._pick_ksplit(p), max_emit=max_emit, scratch=scratch, max_in=max_in,
-                                  out_slots=out_slots, gcn_ksplit=self._pick_gcn_ksplit(p))
+                                  out_slots=out_slots, gcn_ksplit=self._pick_gcn_ksplit(p), counters=counters)
         return self._state
 
     def scratch_floats(self, p: int, max_emit: int = MAX_CYCLE, max_in: int = MAX_CYCLE) -> int:
@@ -457,7 +468,9 @@ class CoStGcn(_Folded):
     (what ``map_state_dict`` does in the reference, base.py:200-224).
     """
 
-    use_native_plan = True      # False: drive every launch from Python (same kernels, same results)
+    # False: drive every launch from Python (same kernels, same results).  Read on every cycle: both engines step on the one
+    # counter buffer, so they may alternate; the plan itself is built when the slab is bound with the attribute set
+    use_native_plan = True
 
     def __init__(self, graph_A, input_shape=(3, 300, 25, 2), num_classes=60, pool_size=-1, pool_padding=-1,
                  CoGraphConv=CoGraphConvolution):
@@ -530,16 +543,22 @@ class CoStGcn(_Folded):
                 "channel ranges whatever the slab size -- it is meant for a handful of streams; use the default mode "
                 "(set_latency_mode(0)) for slabs that fill the GPU")
         self._scratch = torch.empty((need,), device=device, dtype=torch.float32) if need else None
+        # THE stepping position, in the layout csk_co_plan_cycle takes (include/cskel.h): {frames, features, then (received,
+        # emitted) per block}.  _frames / _feats and every block's s / e are views of it; nothing else holds a counter
+        self._ctr = (ctypes.c_int64 * 22)()
         for i in range(10):
             out_slots = in_slots(recv[i + 1]) if i < 9 else max(4, emits[i])
             st = self.layers[f"layer{i + 1}"].bind_state(p, device, xin, max_emit=emits[i], scratch=self._scratch,
-                                                         max_in=recv[i], out_slots=out_slots)
+                                                         max_in=recv[i], out_slots=out_slots,
+                                                         counters=(ctypes.c_int64 * 2).from_buffer(self._ctr, 16 * (i + 1)))
             xin = st.out
         self._pool_ring = torch.zeros((self.pool_size, n, 256), device=device, dtype=torch.float32)
         self._pooled = torch.empty((n, 256), device=device, dtype=torch.float32)
-        self._frames = self._feats = 0
         self._flushed = False
         self._build_plan(device)
+
+    _frames = _counter(0, "input frames received")
+    _feats = _counter(1, "layer-10 emissions the head has taken")
 
     max_cycle = MAX_CYCLE   # frames ONE forward_cycle may carry: sizes the state rings (set_max_cycle)
 
@@ -730,10 +749,8 @@ class CoStGcn(_Folded):
             for i in range(10):
                 self.layers[f"layer{i + 1}"].clean_state()
             self._pool_ring.zero_()
-            self._frames = self._feats = 0
+            self._set_counters([0] * 22)
             self._flushed = False
-            if self.__dict__.get("_plan"):
-                native.lib().csk_co_plan_reset(self._plan)
 
     # ---- stepping ------------------------------------------------------------------------------------
     def _cycle(self, frames):
@@ -760,28 +777,16 @@ class CoStGcn(_Folded):
         if self._flushed:
             raise RuntimeError("the state was flushed by forward_steps(pad_end=True): the end padding has consumed ring slots "
                                "and advanced the blocks past the input frame count; call clean_state() before stepping on")
-        if self.__dict__.get("_plan"):
+        if self.use_native_plan and self.__dict__.get("_plan"):
             return self._plan_cycle(frames)
         return self._python_cycle(frames)
 
     # ---- update_state=False (base.py:183-190 hand the flag through to co.Sequential) -------------------
     def _counters(self):
-        snap = dict(frames=self._frames, feats=self._feats,
-                    layers=[(b._state.s, b._state.e) for b in (self.layers[f"layer{i + 1}"] for i in range(10))])
-        if self.__dict__.get("_plan"):
-            buf = (ctypes.c_int64 * 22)()
-            native.check(native.lib().csk_co_plan_counters(self._plan, buf, 22, 0), "csk_co_plan_counters")
-            snap["plan"] = list(buf)
-        return snap
+        return list(self._ctr)
 
     def _set_counters(self, snap):
-        self._frames, self._feats = snap["frames"], snap["feats"]
-        for i, (s_, e_) in enumerate(snap["layers"]):
-            st = self.layers[f"layer{i + 1}"]._state
-            st.s, st.e = s_, e_
-        if "plan" in snap and self.__dict__.get("_plan"):
-            buf = (ctypes.c_int64 * 22)(*snap["plan"])
-            native.check(native.lib().csk_co_plan_counters(self._plan, buf, 22, 1), "csk_co_plan_counters")
+        self._ctr[:] = snap
 
     def _state_tensors(self):
         ts = [self._xin0, self._pool_ring, self._pooled]
@@ -802,11 +807,9 @@ class CoStGcn(_Folded):
         ptrs = (ctypes.c_void_p * len(frames))(*[x_t.data_ptr() for x_t in frames])
         logits = torch.empty((MAX_CYCLE, n, self.num_classes), device=frames[0].device, dtype=torch.float32)
         slot, nf, nl = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
-        rc = native.lib().csk_co_plan_cycle(self._plan, ptrs, len(frames), native.ptr(logits), ctypes.byref(slot),
+        rc = native.lib().csk_co_plan_cycle(self._plan, self._ctr, 22, ptrs, len(frames), native.ptr(logits), ctypes.byref(slot),
                                             ctypes.byref(nf), ctypes.byref(nl), native.stream_of(frames[0]))
-        native.check(rc, "csk_co_plan_cycle")      # on failure the plan has put its counters back (executor.hip)
-        self._frames += len(frames)
-        self._feats += nf.value
+        native.check(rc, "csk_co_plan_cycle")      # a failed cycle leaves the counters as they were (include/cskel.h)
         if nf.value == 0:
             return None, 0, []
         return slot.value, nf.value, [logits[j] for j in range(nl.value)]
@@ -909,19 +912,10 @@ class CoStGcn(_Folded):
 
     def _flush(self):
         """End padding of the whole model (``pad_end=True``): returns the predictions it releases.  Runs on the Python
-        engine; a native plan's counters are read before and written back afterwards.  The flush ends the sequence: it
-        zeroes y-ring slots and advances the per-block counters by their padding while the input frame count stays,
-        so the rings no longer line up with ``frames % depth`` -- the model is marked flushed and the next step raises
-        until ``clean_state()`` (continual-inference's own end padding does not save state either; a caller that wants
-        to go on uses ``update_state=False``, which runs the flush on a snapshot)."""
-        plan = self.__dict__.get("_plan")
-        if plan:
-            buf = (ctypes.c_int64 * 22)()
-            native.check(native.lib().csk_co_plan_counters(plan, buf, 22, 0), "csk_co_plan_counters")
-            self._frames, self._feats = int(buf[0]), int(buf[1])
-            for i in range(10):
-                st = self.layers[f"layer{i + 1}"]._state
-                st.s, st.e = int(buf[2 + 2 * i]), int(buf[3 + 2 * i])
+        engine.  The flush ends the sequence: it zeroes y-ring slots and advances the per-block counters by their padding
+        while the input frame count stays, so the rings no longer line up with ``frames % depth`` -- the model is marked
+        flushed and the next step raises until ``clean_state()`` (continual-inference's own end padding does not save state
+        either; a caller that wants to go on uses ``update_state=False``, which runs the flush on a snapshot)."""
         n = self._n
         _, _, v, m = self.input_shape
         outs, depth = [], self.layers["layer10"]._state.out.shape[0]
@@ -945,18 +939,7 @@ class CoStGcn(_Folded):
             o = self._head_step(None, n)
             if o is not None:
                 outs.append(o)
-        if plan:
-            self._set_counters(self._counters_py())
         return outs
-
-    def _counters_py(self):
-        snap = dict(frames=self._frames, feats=self._feats,
-                    layers=[(b._state.s, b._state.e) for b in (self.layers[f"layer{i + 1}"] for i in range(10))])
-        flat = [self._frames, self._feats]
-        for s_, e_ in snap["layers"]:
-            flat += [s_, e_]
-        snap["plan"] = flat
-        return snap
 
     def forward(self, x, forward_mode="clip"):
         """CoModelBase.forward (base.py:166-181).  'clip': whole-clip computation with the continual head

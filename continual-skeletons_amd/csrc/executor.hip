@@ -1,25 +1,31 @@
 // executor.hip -- native step executor for the continual stack (host code only; launches go through the C ABI
 // entry points of gcn.hip / step.hip / head.hip).  Mirrors continual.py:CoSpatioTemporalBlock.engine_advance and
-// CoStGcn.features_cycle / _head_step one to one; the Python versions remain the reference for the protocol.
+// CoStGcn._python_cycle / _head_step one to one; the Python versions remain the reference for the protocol.  The stepping
+// position (frames, features, per-layer received / emitted) belongs to the caller: a cycle works on a copy of the caller's
+// counters and stores it back when every launch of the cycle was issued, so either driver can run any cycle.
 #include <vector>
 
 #include "mfma_core.h"
 
 struct BlockCounters {
-    long s = 0;   // frames received
-    long e = 0;   // frames emitted
+    int64_t s;   // frames received
+    int64_t e;   // frames emitted
+};
+
+// one cycle's working copy of the caller's counters (include/cskel.h: csk_co_plan_cycle)
+struct Counters {
+    int64_t frames, feats;
+    std::vector<BlockCounters> layer;
 };
 
 struct csk_co_plan {
     std::vector<csk_co_layer> layers;
-    std::vector<BlockCounters> cnt;
     float *xin0;
     int xin0_slots;
     int N, C, V, M, classes, pool_size, pool_padding;
     int64_t P;
     const float *bn_scale, *bn_shift, *fc_w, *fc_b;
     float *pool_ring, *pooled;
-    long frames = 0, feats = 0;
     bool fuse = true;          // csk_co_block_step_f32 for the blocks that qualify
     int max_cycle = CSK_CO_MAX_CYCLE;   // frames one cycle may carry = what the rings were sized for (xin0_slots - 4, at most 8)
 };
@@ -83,7 +89,6 @@ extern "C" csk_co_plan *csk_co_plan_create(int n_layers, const csk_co_layer *lay
     csk_co_plan *p = new csk_co_plan();
     p->max_cycle = max_cycle;
     p->layers.assign(layers, layers + n_layers);
-    p->cnt.resize(n_layers);
     p->xin0 = xin0; p->xin0_slots = xin0_slots; p->N = N; p->C = C; p->V = V; p->M = M; p->P = P;
     p->bn_scale = bn_scale; p->bn_shift = bn_shift; p->classes = classes; p->fc_w = fc_w; p->fc_b = fc_b;
     p->pool_size = pool_size; p->pool_padding = pool_padding;
@@ -116,27 +121,6 @@ extern "C" int csk_co_plan_set_fusion(csk_co_plan *plan, int enable) {
     if (!plan) CSK_FAIL("co_plan_set_fusion: null pointer");
     plan->fuse = enable != 0;
     return 0;
-}
-
-extern "C" int csk_co_plan_counters(csk_co_plan *plan, int64_t *buf, int n, int set) {
-    if (!plan || !buf) CSK_FAIL("co_plan_counters: null pointer");
-    if (n != 2 + 2 * (int)plan->layers.size()) CSK_FAIL("co_plan_counters: expected %d values", 2 + 2 * (int)plan->layers.size());
-    if (set) {
-        for (int i = 0; i < n; ++i)
-            if (buf[i] < 0) CSK_FAIL("co_plan_counters: negative counter");
-        plan->frames = (long)buf[0]; plan->feats = (long)buf[1];
-        for (size_t i = 0; i < plan->cnt.size(); ++i) { plan->cnt[i].s = (long)buf[2 + 2 * i]; plan->cnt[i].e = (long)buf[3 + 2 * i]; }
-    } else {
-        buf[0] = plan->frames; buf[1] = plan->feats;
-        for (size_t i = 0; i < plan->cnt.size(); ++i) { buf[2 + 2 * i] = plan->cnt[i].s; buf[3 + 2 * i] = plan->cnt[i].e; }
-    }
-    return 0;
-}
-
-extern "C" void csk_co_plan_reset(csk_co_plan *plan) {
-    if (!plan) return;
-    for (auto &c : plan->cnt) c = BlockCounters();
-    plan->frames = plan->feats = 0;
 }
 
 // a whole emitting 4-frame cycle of a 64-row block that csk_co_block_step_f32 / csk_co_stack_step_f32 take (continual.py:_fusable)
@@ -221,14 +205,14 @@ static int advance_block(const csk_co_layer &l, BlockCounters &c, const float *x
 }
 
 // the ten blocks for r new frames: *n_last emissions of the last block starting at output-ring slot *slot0
-static int run_blocks(csk_co_plan *p, int r, int *slot0, int *n_last, void *stream) {
+static int run_blocks(const csk_co_plan *p, std::vector<BlockCounters> &cnt, int r, int *slot0, int *n_last, void *stream) {
     const float *xin = p->xin0;
     int rr = r, in_slots = p->xin0_slots;
     *n_last = 0;
     for (size_t i = 0; i < p->layers.size(); ++i) {
         // consecutive blocks that each advance a whole emitting cycle: ONE launch for the run (csk_co_stack_step_f32)
         auto stackable = [&](size_t k, int r) {             // identity gcn_residual: what the fused stack kernel covers
-            return fusable_cycle(p->layers[k], p->cnt[k], r, p->V) && p->layers[k].gcn_res_mode == CSK_RES_IDENTITY;
+            return fusable_cycle(p->layers[k], cnt[k], r, p->V) && p->layers[k].gcn_res_mode == CSK_RES_IDENTITY;
         };
         if (p->fuse && i + 1 < p->layers.size() && stackable(i, rr) && stackable(i + 1, 4)) {
             csk_co_block_args args[CSK_CO_STACK_MAX];
@@ -236,7 +220,7 @@ static int run_blocks(csk_co_plan *p, int r, int *slot0, int *n_last, void *stre
             size_t j = i;
             for (; j < p->layers.size() && n < CSK_CO_STACK_MAX && stackable(j, 4); ++j, ++n) {
                 const csk_co_layer &l = p->layers[j];
-                const long s0 = p->cnt[j].s;
+                const long s0 = cnt[j].s;
                 if (4 + 8 > l.y_slots || 4 + 4 > in_slots) CSK_FAIL("co_plan_cycle: 4 frames do not fit the rings of layer %d", (int)j);
                 csk_co_block_args &a = args[n];
                 a.xin = xin; a.xin_slots = in_slots; a.xin_slot0 = (int)(s0 % in_slots); a.c_in = l.c_in; a.gcn_w = l.gcn_w;
@@ -244,19 +228,19 @@ static int run_blocks(csk_co_plan *p, int r, int *slot0, int *n_last, void *stre
                 a.ell_cnt[0] = l.ell_cnt[0]; a.ell_cnt[1] = l.ell_cnt[1]; a.ell_cnt[2] = l.ell_cnt[2];
                 a.ell_w = l.ell_w; a.gcn_res_mode = l.gcn_res_mode; a.y_ring = l.y_ring; a.y_slots = l.y_slots; a.y_slot0 = (int)(s0 % l.y_slots);
                 a.tcn_w = l.tcn_w; a.tcn_bias = l.tcn_bias; a.res_mode = l.res_kind; a.x_res_slot0 = (int)((s0 - 4) % in_slots);
-                a.out = l.out_ring; a.out_slots = l.out_slots; a.out_slot0 = (int)(p->cnt[j].e % l.out_slots); a.c_out = l.c_out;
+                a.out = l.out_ring; a.out_slots = l.out_slots; a.out_slot0 = (int)(cnt[j].e % l.out_slots); a.c_out = l.c_out;
                 xin = l.out_ring;
                 in_slots = l.out_slots;
             }
             if (const int rc = csk_co_stack_step_f32(n, args, p->N * p->M, p->V, p->P, stream)) return rc;
-            for (size_t k = i; k < j; ++k) { p->cnt[k].s += 4; p->cnt[k].e += 4; }
+            for (size_t k = i; k < j; ++k) { cnt[k].s += 4; cnt[k].e += 4; }
             *slot0 = args[n - 1].out_slot0;
             rr = 4;
             i = j - 1;
             continue;
         }
         int ne = 0;
-        const int rc = advance_block(p->layers[i], p->cnt[i], xin, in_slots, rr, p->N * p->M, p->V, p->P, slot0, &ne, p->fuse, stream);
+        const int rc = advance_block(p->layers[i], cnt[i], xin, in_slots, rr, p->N * p->M, p->V, p->P, slot0, &ne, p->fuse, stream);
         if (rc) return rc;
         if (ne == 0) return 0;
         rr = ne;
@@ -267,47 +251,56 @@ static int run_blocks(csk_co_plan *p, int r, int *slot0, int *n_last, void *stre
     return 0;
 }
 
-extern "C" int csk_co_plan_cycle(csk_co_plan *p, const float *const *frames, int r, float *logits, int *last_slot,
-                                 int *n_feat, int *n_logits, void *stream) {
-    if (!p || !frames || !logits || !last_slot || !n_feat || !n_logits) CSK_FAIL("co_plan_cycle: null pointer");
-    if (r < 1 || r > p->max_cycle) CSK_FAIL("co_plan_cycle: r must be in [1, %d] (the rings of this plan were sized for cycles of %d frames)", p->max_cycle, p->max_cycle);
-    *n_feat = *n_logits = 0;
-    *last_slot = 0;
-    // A launch can fail half way through a cycle (bad pointer, launch error): the counters are then put
-    // back to their values on entry, so that plan and caller-side counters stay consistent.  (Ring slots already overwritten belong to frames older than every window or to the
-    // cycle that failed; re-running the cycle rewrites them.)
-    struct Rollback {
-        csk_co_plan *p; long frames, feats; std::vector<BlockCounters> cnt; bool armed = true;
-        ~Rollback() { if (armed) { p->frames = frames; p->feats = feats; p->cnt = cnt; } }
-    } rollback{p, p->frames, p->feats, p->cnt};
+// the launches of one cycle on the working copy w.  A launch can fail half way through (bad pointer, launch error): w is
+// then dropped.  (Ring slots already overwritten belong to frames older than every window or to the cycle that failed;
+// re-running the cycle rewrites them.)
+static int run_cycle(const csk_co_plan *p, Counters &w, const float *const *frames, int r, float *logits, int *last_slot,
+                     int *n_feat, int *n_logits, void *stream) {
     {   // reshape1 + data_bn + reshape2 of the cycle's frames into the channel-major ring: one launch
         float *dst[CSK_CO_MAX_CYCLE];
         for (int f = 0; f < r; ++f) {
             if (!frames[f]) CSK_FAIL("co_plan_cycle: null frame");
-            dst[f] = p->xin0 + ((p->frames + f) % p->xin0_slots) * (int64_t)p->C * p->P;
+            dst[f] = p->xin0 + ((w.frames + f) % p->xin0_slots) * (int64_t)p->C * p->P;
         }
         if (const int rc = csk_input_norm_frames_f32(frames, dst, r, p->bn_scale, p->bn_shift, p->N, p->C, p->V, p->M, p->P, stream)) return rc;
-        p->frames += r;
+        w.frames += r;
     }
     int rr = 0, slot0 = 0;
-    if (const int rc = run_blocks(p, r, &slot0, &rr, stream)) return rc;
-    if (rr == 0) { rollback.armed = false; return 0; }
+    if (const int rc = run_blocks(p, w.layer, r, &slot0, &rr, stream)) return rc;
+    if (rr == 0) return 0;
     *last_slot = slot0;
     *n_feat = rr;
     const csk_co_layer &last = p->layers.back();
-    const int64_t n_elem = (int64_t)p->N * last.c_out;
     for (int j = 0; j < rr; ++j) {                 // spatial_pool -> co.AvgPool1d window -> co.Linear: one launch per emission
         const int slot = (slot0 + j) % last.out_slots;
-        const int head = (int)(p->feats % p->pool_size);
-        p->feats++;
-        const int emit = p->feats >= p->pool_size - p->pool_padding;
-        const int count = (int)(p->feats < p->pool_size ? p->feats : p->pool_size);
+        const int head = (int)(w.feats % p->pool_size);
+        w.feats++;
+        const int emit = w.feats >= p->pool_size - p->pool_padding;
+        const int count = (int)(w.feats < p->pool_size ? w.feats : p->pool_size);
         const int rc = csk_co_head_step_f32(last.out_ring + slot * (int64_t)last.c_out * p->P, p->pool_ring, p->pooled, p->fc_w, p->fc_b,
                                             logits + (int64_t)(*n_logits) * p->N * p->classes, p->N, last.c_out, p->M * p->V, p->P,
                                             p->pool_size, head, count, emit, p->classes, stream);
         if (rc) return rc;
         if (emit) (*n_logits)++;
     }
-    rollback.armed = false;
+    return 0;
+}
+
+extern "C" int csk_co_plan_cycle(csk_co_plan *p, int64_t *counters, int n_counters, const float *const *frames, int r,
+                                 float *logits, int *last_slot, int *n_feat, int *n_logits, void *stream) {
+    if (!p || !counters || !frames || !logits || !last_slot || !n_feat || !n_logits) CSK_FAIL("co_plan_cycle: null pointer");
+    const int n_layers = (int)p->layers.size();
+    if (n_counters != 2 + 2 * n_layers) CSK_FAIL("co_plan_cycle: expected %d counters, got %d", 2 + 2 * n_layers, n_counters);
+    for (int i = 0; i < n_counters; ++i)
+        if (counters[i] < 0) CSK_FAIL("co_plan_cycle: negative counter");
+    if (r < 1 || r > p->max_cycle) CSK_FAIL("co_plan_cycle: r must be in [1, %d] (the rings of this plan were sized for cycles of %d frames)", p->max_cycle, p->max_cycle);
+    *n_feat = *n_logits = 0;
+    *last_slot = 0;
+    Counters w{counters[0], counters[1], std::vector<BlockCounters>(n_layers)};
+    for (int i = 0; i < n_layers; ++i) w.layer[i] = {counters[2 + 2 * i], counters[3 + 2 * i]};
+    const int rc = run_cycle(p, w, frames, r, logits, last_slot, n_feat, n_logits, stream);
+    if (rc) return rc;                             // the caller's counters are as they were passed in
+    counters[0] = w.frames; counters[1] = w.feats;
+    for (int i = 0; i < n_layers; ++i) { counters[2 + 2 * i] = w.layer[i].s; counters[3 + 2 * i] = w.layer[i].e; }
     return 0;
 }

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CSK_ABI_VERSION 15
+#define CSK_ABI_VERSION 16
 #define CSK_KC 8    /* channel-chunk of the K loop of the TCN kernels                                */
 #define CSK_CPAD 16 /* packed weights zero-pad C_in to a multiple of this                             */
 #define CSK_MT 64  /* packed weights pad C_out to a multiple of this                               */
@@ -386,7 +386,8 @@ int csk_fuse_rank_f32(const float *const *preds, int n_streams, int use_max, int
  * Native step executor ("plan"): the counterpart of co.Sequential.forward_step driving the ten continual
  * blocks and the head (models/base.py:108-122,183-190) -- one C call issues every launch of a cycle of 1..8
  * frames (input norm, per block one GCN-stage + one multi-emission TCN-step launch, spatial pool, temporal
- * window mean, FC), with the ring-slot / stride-phase bookkeeping kept in the plan.  No allocation, no sync.
+ * window mean, FC).  The plan holds operands and geometry only: the stepping position (the counters every ring slot and
+ * stride phase follows from) belongs to the caller and is handed to each csk_co_plan_cycle call.  No device allocation, no sync.
  * ------------------------------------------------------------------------------------------------ */
 #define CSK_CO_MAX_CYCLE 8
 /* Ring depths are per layer (csk_co_layer.y_slots / .out_slots, csk_co_plan_create xin0_slots), derived from the frames ONE
@@ -440,23 +441,22 @@ csk_co_plan *csk_co_plan_create(int n_layers, const csk_co_layer *layers, float 
                                 const float *fc_w, const float *fc_b, int pool_size, int pool_padding,
                                 float *pool_ring, float *pooled);
 void csk_co_plan_destroy(csk_co_plan *plan);
-/* swap in refolded weights (same geometry and state rings); counters and state are kept */
+/* swap in refolded weights (same geometry and state rings); the plan holds no stepping state, so none is touched */
 int csk_co_plan_update_weights(csk_co_plan *plan, int n_layers, const csk_co_layer *layers, const float *bn_scale,
                                const float *bn_shift, const float *fc_w, const float *fc_b);
-/* forget all counters (the caller zeroes the slab): clean_state(), models/base.py:161-164 */
-void csk_co_plan_reset(csk_co_plan *plan);
-/* read (set = 0) or write (set = 1) the plan's counters: buf = {frames, features, then (received, emitted) per layer},
- * n = 2 + 2*n_layers.  forward_step(x, update_state=False) (models/base.py:183-185) = read, cycle, write back: a
- * step only overwrites ring slots whose content is older than any window, so the counters are the whole state. */
-int csk_co_plan_counters(csk_co_plan *plan, int64_t *buf, int n, int set);
 /* 1 (default): blocks that qualify advance a 4-frame cycle with one csk_co_block_step_f32 launch instead of a
  * csk_gcn_stage_f32 + csk_tcn_step_f32 pair (bit-identical results); 0: always the two-launch form. */
 int csk_co_plan_set_fusion(csk_co_plan *plan, int enable);
 /* Advance by r = 1..CSK_CO_MAX_CYCLE frames, frames[i] = (N, C, V, M) device pointers.  On return
  * *last_slot / *n_feat describe the last layer's emissions of this cycle (slot of the first, count) and
- * *n_logits how many predictions were written to `logits` ([CSK_CO_MAX_CYCLE][N][classes], slice j = prediction j). */
-int csk_co_plan_cycle(csk_co_plan *plan, const float *const *frames, int r, float *logits, int *last_slot,
-                      int *n_feat, int *n_logits, void *stream);
+ * *n_logits how many predictions were written to `logits` ([CSK_CO_MAX_CYCLE][N][classes], slice j = prediction j).
+ * counters = the caller's stepping position, {frames, features, then (received, emitted) per layer}, n_counters =
+ * 2 + 2*n_layers values >= 0 (all zero = clean state, models/base.py:161-164).  Read on entry and advanced when the call
+ * returns 0; on any other return, after any number of launches, it is exactly what was passed in.  A step only overwrites
+ * ring slots whose content is older than any window, so the counters are the whole state of a single step:
+ * forward_step(x, update_state=False) (models/base.py:183-185) = run the cycle on a copy. */
+int csk_co_plan_cycle(csk_co_plan *plan, int64_t *counters, int n_counters, const float *const *frames, int r, float *logits,
+                      int *last_slot, int *n_feat, int *n_logits, void *stream);
 
 /*
  * S-TR spatial-attention graph unit (GcnUnitAttention, models/s_tr/s_tr.py:303-477, in the configuration STr / CoSTr build:

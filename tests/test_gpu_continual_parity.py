@@ -573,3 +573,116 @@ def test_max_cycle_4_slab_is_smaller_and_bitwise_the_same():
         small.forward_cycle([x[:, :, f].contiguous() for f in range(5)])
     with pytest.raises(ValueError):
         small.set_max_cycle(9)
+
+
+def _twins(count, native_plan, latency=False, pool=(4, 1)):
+    """``count`` CoST-GCNs with the G6 weights; element i steps on the native plan where native_plan[i]."""
+    a, sd, x = g6_state_dict("ntu")
+    nets = []
+    for i in range(count):
+        co = pkg.CoStGcn(A, pool_size=pool[0], pool_padding=pool[1]).eval()
+        co.use_native_plan = native_plan[i]
+        co.load_state_dict(sd, strict=True)
+        co = co.to(DEV)
+        if latency:
+            co.set_latency_mode(8)
+        nets.append(co)
+    return nets, x
+
+
+def _block_counters(net):
+    return [(net.layers[f"layer{i + 1}"]._state.s, net.layers[f"layer{i + 1}"]._state.e) for i in range(10)]
+
+
+@pytest.mark.parametrize("latency", [False, True])
+def test_plan_and_python_engine_interleave_on_one_counter_store(latency):
+    """The stepping position has ONE store (CoStGcn._ctr; the blocks' s / e and the plan's ``counters`` argument are that
+    buffer), so the native plan and the Python engine may take turns: a model whose ``use_native_plan`` flips on every
+    4-frame cycle equals -- logits, every state tensor and the counters, bit for bit after every cycle -- a twin that runs
+    the plan only and one that runs the Python engine only.  120 frames: the first prediction falls at frame 84 and the
+    16-slot y ring of layer 1 wraps seven times."""
+    (mixed, plan, py), x = _twins(3, (True, True, False), latency)
+    x = x[:2, :, :120].to(DEV)
+    n_pred = 0
+    for c in range(30):
+        fr = [x[:, :, 4 * c + f].contiguous() for f in range(4)]
+        mixed.use_native_plan = c % 2 == 0
+        outs = [net.forward_cycle(fr) for net in (mixed, plan, py)]
+        assert len(outs[0]) == len(outs[1]) == len(outs[2])
+        for lm, lp, ly in zip(*outs):
+            assert torch.equal(lm, lp) and torch.equal(lm, ly), c
+            n_pred += 1
+        assert mixed._counters() == plan._counters() == py._counters(), c
+        assert _block_counters(mixed) == _block_counters(plan) == _block_counters(py), c
+        for i, (tm, tp, ty) in enumerate(zip(mixed._state_tensors(), plan._state_tensors(), py._state_tensors())):
+            if n_pred or tm is not mixed._pooled:          # _pooled is torch.empty until the first prediction writes it
+                assert torch.equal(tm, tp) and torch.equal(tm, ty), (c, i)
+    assert n_pred == 9 and mixed._counters()[:4] == [120, 11, 120, 116]
+    assert mixed.__dict__.get("_plan") and plan.__dict__.get("_plan") and not py.__dict__.get("_plan")
+    assert plan.layers["layer9"]._state.ksplit == (32 if latency else 1)
+
+
+def test_failed_plan_cycle_leaves_no_trace():
+    """csk_co_plan_cycle works on a copy of the caller's counters and stores it back only when every launch of the cycle was
+    issued.  A second plan over the SAME rings whose layer 2 claims a split-K scratch for one graph-conv frame refuses a
+    2-frame cycle on the host, after the input norm and layer 1 were launched: non-zero return, the counters it was given
+    unchanged.  The model then takes the same two frames (rewriting the slots the failed call touched) and goes on bitwise
+    like a twin that never saw the failed call."""
+    import ctypes
+    native = pkg.native
+    lib = native.lib()
+    (net, twin), x = _twins(2, (True, True), latency=True)
+    x = x[:2, :, :120].to(DEV)
+    cycles = [[x[:, :, 2 * c + f].contiguous() for f in range(2)] for c in range(60)]
+    for fr in cycles[:20]:
+        assert net.forward_cycle(fr) == twin.forward_cycle(fr) == []
+    assert net.layers["layer2"]._state.gcn_ksplit > 1
+    arr, keep, ops, fcw, fcb = net._layer_structs(torch.device(DEV))
+    arr[1].gcn_partial_frames = 1
+    plan2 = lib.csk_co_plan_create(10, ctypes.byref(arr), native.ptr(net._xin0), net._xin0.shape[0], net._n, 3, 25, 2, net._p,
+                                   native.ptr(ops["scale"]), native.ptr(ops["shift"]), 60, native.ptr(fcw), native.ptr(fcb),
+                                   net.pool_size, net.pool_padding, native.ptr(net._pool_ring), native.ptr(net._pooled))
+    assert plan2, lib.csk_last_error()
+    before = net._counters()
+    assert before[:6] == [40, 0, 40, 36, 36, 32]
+    buf = (ctypes.c_int64 * 22)(*before)
+    ptrs = (ctypes.c_void_p * 2)(*[f.data_ptr() for f in cycles[20]])
+    logits = torch.empty((8, 2, 60), device=DEV)
+    slot, nf, nl = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    rc = lib.csk_co_plan_cycle(ctypes.c_void_p(plan2), buf, 22, ptrs, 2, native.ptr(logits), ctypes.byref(slot), ctypes.byref(nf),
+                               ctypes.byref(nl), native.stream_of(logits))
+    msg = lib.csk_last_error()
+    lib.csk_co_plan_destroy(ctypes.c_void_p(plan2))
+    assert rc != 0 and b"exceed the split-K scratch" in msg, (rc, msg)
+    assert all(buf[i] == before[i] for i in range(22)) and net._counters() == before
+    n_pred = 0
+    for c, fr in enumerate(cycles[20:]):
+        got, want = net.forward_cycle(fr), twin.forward_cycle(fr)
+        assert len(got) == len(want) and all(torch.equal(g, w) for g, w in zip(got, want)), c
+        n_pred += len(got)
+        assert net._counters() == twin._counters(), c
+    assert n_pred == 9
+    for tn, tt in zip(net._state_tensors(), twin._state_tensors()):
+        assert torch.equal(tn, tt)
+
+
+def test_peeking_at_a_plan_driven_model_leaves_every_counter_where_it_was():
+    """update_state=False on a model the native plan drives: after ``forward_step`` and after ``forward_steps(pad_end=True)``
+    -- whose flush runs on the Python engine -- the counter buffer equals its value before the call, and every block's
+    s / e is what a Python-engine twin holds at the same point (with a copy of the counters inside the plan, the blocks of
+    a plan-driven model read 0 here)."""
+    (net, py), x = _twins(2, (True, False))
+    x = x[:2, :, :130].to(DEV)
+    for t in range(110):
+        f = x[:, :, t].contiguous()
+        if t in (3, 50, 90):
+            before = net._counters()
+            net.forward_step(f, update_state=False)
+            assert net._counters() == before and _block_counters(net) == _block_counters(py), t
+            ahead = net.forward_steps(x[:, :, t:t + 20].contiguous(), pad_end=True, update_state=False)
+            assert ahead.shape[:2] == (2, 60) and not net._flushed
+            assert net._counters() == before and _block_counters(net) == _block_counters(py), t
+            assert before[0] == t and before[2:4] == [t, max(0, t - 4)]
+        got, want = net.forward_step(f), py.forward_step(f)
+        assert (got is None) == (want is None) and (want is None or torch.equal(got, want)), t
+    assert net.__dict__.get("_plan") and not py.__dict__.get("_plan")

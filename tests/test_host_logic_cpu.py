@@ -23,7 +23,7 @@ def test_library_exports_every_declared_symbol():
     for name in declared:
         assert hasattr(lib, name), f"{name} declared in cskel.h but not exported"
     assert declared - {"csk_last_error"} == set(pkg.native.SIGNATURES), "ctypes table out of sync with cskel.h"
-    assert pkg.native.lib().csk_abi_version() == pkg.native.ABI_VERSION == 15
+    assert pkg.native.lib().csk_abi_version() == pkg.native.ABI_VERSION == 16
 
 
 def test_argument_errors_do_not_need_a_gpu():
@@ -444,6 +444,48 @@ def test_fused_attention_entry_and_plan_validate_their_arguments_without_a_gpu()
     plan = create()
     assert plan
     lib.csk_co_plan_destroy(C.c_void_p(plan))
+
+
+def test_plan_cycle_rejects_bad_arguments_and_leaves_the_callers_counters_alone():
+    """csk_co_plan_cycle steps on the CALLER's counters ({frames, features, (received, emitted) per layer}): a null or
+    mis-sized buffer, a negative counter, a cycle length the rings were not sized for and a null frame are argument errors
+    reported before anything is launched (fake pointers here), and after each of them the buffer holds, element by element,
+    what was passed in."""
+    import ctypes as C
+    lib = pkg.native.lib()
+    fake = C.c_void_p(0x1000)
+    L = (pkg.native.CoLayer * 1)()
+    l = L[0]
+    l.c_in, l.c_out, l.stride, l.res_kind, l.gcn_res_mode, l.ell_w, l.tcn_ksplit = 3, 64, 1, 0, 2, 3, 1
+    for j in range(3):
+        l.ell_cnt[j] = 1
+    for f in ("gcn_w", "gcn_bias", "ell_src", "ell_val", "tcn_w", "tcn_bias", "y_ring", "out_ring"):
+        setattr(l, f, 0x1000)
+    l.y_slots, l.out_slots = 16, 8
+    plan = lib.csk_co_plan_create(1, C.byref(L), fake, 12, 2, 3, 18, 2, 72, fake, fake, 400, fake, fake, 4, 1, fake, fake)
+    assert plan, lib.csk_last_error()
+    plan = C.c_void_p(plan)
+    start = [9, 1, 9, 5]
+    frames = (C.c_void_p * 8)(*[0x1000] * 8)
+    no_frame = (C.c_void_p * 8)(0x1000, None, *[0x1000] * 6)
+    slot, nf, nl = C.c_int(0), C.c_int(0), C.c_int(0)
+
+    def cycle(counters=start, n=4, null_counters=False, fr=frames, r=2):
+        buf = (C.c_int64 * len(counters))(*counters)
+        rc = lib.csk_co_plan_cycle(plan, None if null_counters else buf, n, fr, r, fake, C.byref(slot), C.byref(nf),
+                                   C.byref(nl), None)
+        assert all(buf[i] == counters[i] for i in range(len(counters))), list(buf)
+        return rc, lib.csk_last_error()
+    try:
+        for kwargs, why in ((dict(null_counters=True), b"null pointer"), (dict(n=3), b"expected 4 counters"),
+                            (dict(counters=start + [0, 0], n=6), b"expected 4 counters"),
+                            (dict(counters=[9, 1, -1, 5]), b"negative counter"), (dict(r=0), b"r must be in [1, 8]"),
+                            (dict(r=9), b"r must be in [1, 8]"), (dict(fr=None), b"null pointer"),
+                            (dict(fr=no_frame), b"null frame")):
+            rc, msg = cycle(**kwargs)
+            assert rc == -1 and why in msg, (kwargs, rc, msg)
+    finally:
+        lib.csk_co_plan_destroy(plan)
 
 
 def test_plan_staleness_check_is_exact_for_every_kind_of_weight_edit():
