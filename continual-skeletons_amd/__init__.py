@@ -26,6 +26,7 @@ from .continual import (  # noqa: F401
     CoSpatioTemporalBlock,
     CoStGcn,
     CoTemporalConvolution,
+    set_step_precision,
 )
 from .agcn import AdaptiveGraphConvolution, AGcn, CoAdaptiveGraphConvolution, CoAGcn  # noqa: F401
 from .str import CoSTr, GcnUnitAttention, STr  # noqa: F401

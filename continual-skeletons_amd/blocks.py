@@ -491,3 +491,8 @@ SpatioTemporalBlock._forward_few_channels = _forward_few_channels
 def tcn_step_launch(*args):
     """csk_tcn_step_f32 launch (module-level so that bench.py can time it with HIP events)."""
     native.check(native.lib().csk_tcn_step_f32(*args), "csk_tcn_step_f32")
+
+
+def tcn_step_split_launch(*args):
+    """csk_tcn_step_bf16x3 launch (module-level beside tcn_step_launch: tools and tests time / count it here)."""
+    native.check(native.lib().csk_tcn_step_bf16x3(*args), "csk_tcn_step_bf16x3")

@@ -249,7 +249,8 @@ class CoSpatioTemporalBlock(SpatioTemporalBlock):
                     k = plain + k[len(co):]
                     break
             sd[k] = v
-        return fold.fold_block_tail(sd, "", has_conv_residual=self.kind == "conv", split=self.precision == "bf16x3", stride=self.stride)
+        split = self.precision == "bf16x3" or self.step_precision == "bf16x3"
+        return fold.fold_block_tail(sd, "", has_conv_residual=self.kind == "conv", split=split, stride=self.stride)
 
     # ---- persistent state --------------------------------------------------------------------------
     def bind_state(self, p: int, device, xin: Optional[torch.Tensor] = None, max_emit: int = MAX_CYCLE,
@@ -307,7 +308,7 @@ class CoSpatioTemporalBlock(SpatioTemporalBlock):
         post-GCN frames instead (end padding)."""
         st, k = self._state, self.kernel_size
         HIST, YRING, OUT = st.xin.shape[0], st.y.shape[0], st.out.shape[0]      # ring depths of this block's slab slice
-        if self.precision != "f32":
+        if self.precision != "f32" and self.step_precision == "f32":
             raise NotImplementedError(
                 "precision 'bf16x3' covers the clip kernels only: in step mode every ring slot feeds ONE tap per emission, so "
                 "the split kernel would stage twice the bytes per MFMA of the clip form and is bound by staging, not by the "
@@ -315,6 +316,7 @@ class CoSpatioTemporalBlock(SpatioTemporalBlock):
         if not 1 <= r <= st.max_in:
             raise ValueError(f"engine_advance handles 1..{st.max_in} frames per call of this block, got {r}")
         s0, p = st.s, st.p
+        split_step = self._use_split_step()
         if not flush and self._fusable(r, s0, V):
             return self._fused_advance(n_frames, V)
         f = 0
@@ -347,6 +349,13 @@ class CoSpatioTemporalBlock(SpatioTemporalBlock):
         group = n_emit if (st.partial is None or st.ksplit <= 1) else min(n_emit, st.max_emit)     # only a split temporal conv is bound by the scratch
         for e0 in range(0, n_emit, group):
             ne, f0 = min(group, n_emit - e0), first + e0 * self.stride
+            if split_step:          # csk_tcn_step_bf16x3: the same rings and slot arithmetic, the split weight images (no split-K)
+                blocks.tcn_step_split_launch(
+                    native.ptr(st.y), YRING, f0 % YRING, self.stride, ne, native.ptr(ops["w_split"]),
+                    native.ptr(st.xin) if mode else None, HIST, (f0 - lag) % HIST, self.stride,
+                    native.ptr(ops["w_res_split"]), native.ptr(ops["bias"]), native.ptr(st.out), OUT, (slot0 + e0) % OUT,
+                    self.out_channels, self.out_channels, p, k, mode, self.in_channels if mode else 0, 1, native.stream_of(st.y))
+                continue
             blocks.tcn_step_launch(
                 native.ptr(st.y), YRING, f0 % YRING, self.stride, ne, native.ptr(ops["w"]),
                 native.ptr(st.xin) if mode else None, HIST, (f0 - lag) % HIST, self.stride,
@@ -358,9 +367,22 @@ class CoSpatioTemporalBlock(SpatioTemporalBlock):
 
     fuse_step = True    # one launch per block and stride cycle where csk_co_block_step_f32 applies (bit-identical)
 
+    step_precision = "f32"      # or "bf16x3" (opt-in, set_step_precision): arithmetic of the temporal STEP kernel
+    SPLIT_STEP_MIN_CHANNELS = 128   # narrowest layer csk_tcn_step_bf16x3 takes (layers 5-10 of the ten-block table)
+
+    def _use_split_step(self) -> bool:
+        """csk_tcn_step_bf16x3 takes this block's emitting steps: the mode is on, the block is one of the 128- / 256-channel
+        layers (64-channel blocks keep the fused one-launch exact stack) with stride 1 or 2 and runs without split-K (latency
+        mode keeps its exact kernels).  A function of the LAYER only -- never of the slab, the cycle length or the ring
+        position -- so a stream's results do not depend on how many streams share the slab."""
+        return (self.step_precision == "bf16x3" and self.kernel_size == 9 and self.out_channels >= self.SPLIT_STEP_MIN_CHANNELS
+                and self.stride in (1, 2) and self._pick_ksplit(0) == 1 and self._pick_gcn_ksplit(0) == 1)
+
     def _fusable(self, r: int, s0: int, V: int) -> bool:
         """csk_co_block_step_f32 (include/cskel.h): 64-row blocks, stride 1, a whole 4-frame cycle of emitting steps,
         native sparse graph conv, block residual none / identity, no split-K."""
+        if self._use_split_step():
+            return False
         if not (self.fuse_step and r == 4 and self.stride == 1 and self.out_channels <= 64 and s0 >= self.delay
                 and self.kind in ("none", "identity") and type(self.gcn) is GraphConvolution and self._state.ksplit == 1
                 and self._state.gcn_ksplit == 1):
@@ -446,6 +468,42 @@ class CoSpatioTemporalBlock(SpatioTemporalBlock):
                 if slot is not None:
                     outs.append(st.out[slot, :, : n * v].view(self.out_channels, n, v).permute(1, 0, 2).contiguous())
         return torch.stack(outs, dim=2)
+
+
+STEP_PRECISIONS = ("f32", "bf16x3")
+
+
+def set_step_precision(module: nn.Module, precision: str = "f32") -> nn.Module:
+    """Select the arithmetic of the continual temporal STEP of every ``CoSpatioTemporalBlock`` below ``module``.
+
+    "f32" (default): the exact-fp32 step kernels.  "bf16x3" (opt-in): the blocks ``_use_split_step`` covers (128 and 256
+    channels, no split-K) launch ``csk_tcn_step_bf16x3`` -- fp32 operands as three bf16 pieces, six piece products per fp32
+    product on the bf16 matrix pipe, fp32 accumulation, the identity residual exact fp32 (csrc/step_split.hip); every other
+    block keeps its exact kernel.  fp32-GRADE, never reported as fp32.  Independent of ``set_precision`` (the clip kernels):
+    with the step precision "bf16x3" stepping is allowed whatever the clip precision is.  A ``CoStGcn`` in the mode runs on
+    the Python engine (no native plan).  Built for plain graph convs: a model whose blocks carry another graph-conv module
+    (CoAGcn, CoSTr) is refused.  Everything is validated before anything is switched; bound continual state is dropped, as
+    on a shape change.  Call it on the model (or on a block that is stepped on its own), not on a single block inside a
+    ``CoStGcn``: the model owns the slab and the plan of its blocks and would not see the switch."""
+    if precision not in STEP_PRECISIONS:
+        raise ValueError(f"step precision must be one of {STEP_PRECISIONS}, got {precision!r}")
+    blocks_ = [m for m in module.modules() if isinstance(m, CoSpatioTemporalBlock)]
+    if not blocks_:
+        raise ValueError("no CoSpatioTemporalBlock below this module: nothing to set")
+    if precision != "f32" and any(type(m.gcn) is not GraphConvolution for m in blocks_):
+        raise NotImplementedError("step precision 'bf16x3' is built for blocks with the plain GraphConvolution (CoStGcn); "
+                                  "the model is unchanged")
+    models = [m for m in module.modules() if isinstance(m, CoStGcn)]
+    owned = {id(b) for m in models for b in m.layers.values()}
+    for m in models:                # as set_max_cycle: the native plan goes now, the slab is re-bound (zeroed) on the next step
+        m._destroy_plan()
+        m._n = None
+    for m in blocks_:
+        m.step_precision = precision
+        m.refold()
+        if id(m) not in owned:      # a block stepped on its own: its state is bound again on its next step
+            m._state = None
+    return module
 
 
 def co_geometry(c_in=3):
@@ -685,9 +743,13 @@ class CoStGcn(_Folded):
     def _build_plan(self, device):
         """csk_co_plan (include/cskel.h): one C call per cycle instead of ~25 (CoAGCN: ~45) ctypes calls.  Built for stacks of
         plain GraphConvolution blocks and of adaptive graph convs in the shapes the fused embedding + attention entry
-        covers (``plan_operands``); other graph convs keep the Python engine below."""
+        covers (``plan_operands``); other graph convs keep the Python engine below.  No plan is built while any block has a
+        step precision other than "f32" (set_step_precision): ``csk_co_layer`` carries no split weight images, so that mode
+        runs on the Python engine (``_python_cycle``); plan support would change the struct and is out of scope."""
         self._destroy_plan()
         if not self.use_native_plan:
+            return
+        if any(self.layers[f"layer{i + 1}"].step_precision != "f32" for i in range(10)):
             return
         for i in range(10):
             gcn = self.layers[f"layer{i + 1}"].gcn
@@ -771,7 +833,7 @@ class CoStGcn(_Folded):
             raise RuntimeError(f"frame shape {tuple(x0.shape)} does not match input_shape {self.input_shape}")
         if self._n != n or self._xin0.device != x0.device:           # clean_state_on_shape_change (base.py:161-164)
             self._bind(n, x0.device)
-        if any(self.layers[f"layer{i + 1}"].precision != "f32" for i in range(10)):
+        if any(b.precision != "f32" and b.step_precision == "f32" for b in self.layers.values()):
             raise NotImplementedError("precision 'bf16x3' covers the clip kernels only (DESIGN.md section 4): step with the default "
                                       "precision -- set_precision(model, 'f32')")
         if self._flushed:

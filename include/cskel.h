@@ -300,6 +300,32 @@ int csk_tcn_step_f32(const float *ring, int slots, int head, int head_step, int 
                      void *stream);
 
 /*
+ * OPT-IN step precision "bf16x3" of csk_tcn_step_f32 (same reference method, models/base.py:307-334, 390-446; same rings,
+ * slot arithmetic and arguments except the weights and the split-K pair, which this entry does not take): the 9 x 1 temporal
+ * conv and the 1 x 1 conv residual of the emitting step(s) run on the bf16 matrix pipe with every fp32 operand split into
+ * three bf16 pieces and the six piece products of order <= 2 accumulated in fp32 (v_mfma_f32_16x16x32_bf16; see
+ * csk_tcn_stage_bf16x3) -- fp32-GRADE results, not the arithmetic of csk_tcn_step_f32.  The identity residual is added in
+ * exact fp32 from the x_res ring; the output ring is fp32.  The ring is split when a slot is staged (no shadow state).  Never
+ * selected implicitly: continual.set_step_precision(module, "bf16x3").  An output's summation order does not depend on
+ * n_emit, P or the tile the launch picks.
+ *  w_split      the image of csk_tcn_stage_bf16x3 packed for stride = head_step (fold.pack_conv_weight_split):
+ *               [c_pad / 16][9 tap slots, class-major][3 pieces][2 channel halves][c_out_pad] vectors of 8 bf16
+ *  w_res_split  [c_res_pad / 16][3 slots: tap 0, zero, zero][3][2][c_out_pad] (CSK_RES_CONV) or NULL
+ *  k            must be 9; head_step 1 or 2; every ring below 4 GB; images 16-byte aligned
+ */
+int csk_tcn_step_bf16x3(const float *ring, int slots, int head, int head_step, int n_emit, const void *w_split,
+                        const float *x_res, int x_res_slots, int x_res_slot0, int x_res_step,
+                        const void *w_res_split, const float *bias, float *out, int out_slots, int out_slot0,
+                        int c, int c_out, int64_t P, int k, int res_mode, int c_res, int relu, void *stream);
+
+/*
+ * The tile csk_tcn_step_bf16x3 picks for a launch shape: 16-position column blocks per workgroup (25 or 18 for an odd
+ * n_emit, one emission per tile; 13 or 9 for an even one, two emissions per tile).  Host arithmetic only (no GPU); -1 on bad
+ * dims.  For tests and tools: results do not depend on the tile.
+ */
+int csk_tcn_step_bf16x3_tile(int n_emit, int c_out, int64_t P);
+
+/*
  * One CoSpatioTemporalBlock.forward_step cycle in one call (models/base.py:412-446): graph conv of the 4 new frames of
  * a stride cycle + the 4 emitting steps of the temporal conv + residual + ReLU -- csk_gcn_stage_f32 followed by
  * csk_tcn_step_f32 with n_emit = 4.  ONE launch where the slot-balanced tile family covers the shape (csrc/step16.hip:
