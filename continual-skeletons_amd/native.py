@@ -48,6 +48,7 @@ SIGNATURES = {
     "csk_co_plan_update_weights": [_p, _i, _p, _p, _p, _p, _p],
     "csk_co_plan_set_fusion": [_p, _i],
     "csk_co_plan_cycle": [_p, C.POINTER(C.c_int64), _i, _p, _i, _p, _p, _p, _p, _p],
+    "csk_co_scrub_streams_f32": [_p, _i, _p, _i, _i, _p],
     "csk_str_unit_f32": [_p, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _l, _l, _l, _l, _p],
 }
 RESTYPES = {"csk_co_plan_create": C.c_void_p, "csk_co_plan_destroy": None}
@@ -65,6 +66,15 @@ class CoLayer(C.Structure):
                 ("agcn_inter", C.c_int32), ("agcn_pad_", C.c_int32), ("agcn_w_pairs", C.c_void_p), ("agcn_b_pairs", C.c_void_p),
                 ("agcn_a_sum", C.c_void_p), ("agcn_adj", C.c_void_p)]
 
+
+class ScrubJob(C.Structure):
+    """Mirror of ``csk_scrub_job`` (include/cskel.h)."""
+    _fields_ = [("ring", C.c_void_p), ("row_floats", C.c_int64), ("depth", C.c_int32), ("rows", C.c_int32),
+                ("slot0", C.c_int32), ("n_slots", C.c_int32), ("seg", C.c_int32), ("kind", C.c_int32)]
+
+
+SCRUB_MAX_JOBS = 24
+SCRUB_BLOCK_RING, SCRUB_POOL_RING = 0, 1
 
 _lib = None
 

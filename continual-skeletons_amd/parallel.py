@@ -109,6 +109,36 @@ class StreamShards:
             cur.wait_stream(st)
         return None if any(p is None for p in parts) else torch.cat(parts, dim=0)
 
+    def reset_streams(self, indices):
+        """``CoStGcn.reset_streams`` for GLOBAL stream indices: each shard resets its own, on its own HIP stream.  Every
+        shard checks its part before any shard launches (the shards step in lock step, so they agree)."""
+        if isinstance(indices, torch.Tensor) or not isinstance(indices, (list, tuple, range)):
+            raise ValueError("reset_streams takes a sequence of ints (a list, tuple or range), not a tensor")
+        idx = list(indices)
+        n = self.bounds[-1][1]
+        if any(isinstance(i, bool) or not isinstance(i, int) or not 0 <= i < n for i in idx) or len(set(idx)) != len(idx):
+            raise ValueError(f"stream indices {idx} must be distinct ints in [0, {n})")
+        local = [[i - lo for i in idx if lo <= i < hi] for lo, hi in self.bounds]
+        for part, model in zip(local, self.models):
+            model._check_reset(part)
+        cur = torch.cuda.current_stream(self.device) if len(self.models) > 1 else None
+        for part, model, st in zip(local, self.models, self.streams):
+            if not part:
+                continue
+            if st is None:
+                model.reset_streams(part)
+                continue
+            st.wait_stream(cur)
+            with torch.cuda.stream(st):
+                model.reset_streams(part)
+
+    def streams_ready(self):
+        """(N,) bool CPU tensor over the global stream axis (``CoStGcn.streams_ready`` of every shard, concatenated)."""
+        return torch.cat([m.streams_ready() for m in self.models], dim=0)
+
+    def stream_ages(self):
+        return torch.cat([m.stream_ages() for m in self.models], dim=0)
+
     def state_bytes(self):
         return sum(m.state_bytes() for m in self.models)
 

@@ -484,6 +484,31 @@ int csk_co_plan_set_fusion(csk_co_plan *plan, int enable);
 int csk_co_plan_cycle(csk_co_plan *plan, int64_t *counters, int n_counters, const float *const *frames, int r, float *logits,
                       int *last_slot, int *n_feat, int *n_logits, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Per-stream reset of the continual slab: zero the state of SOME of the N streams that share the rings, leaving every
+ * other stream -- and the P-padding behind the last one -- untouched.  A job names a ring and a run of n_slots slots
+ * starting at slot0, taken modulo the ring depth:
+ *   CSK_SCRUB_BLOCK_RING  ring [depth][rows][row_floats] (xin0, a layer's y_ring / out_ring: rows = channels, row_floats = P);
+ *                         stream n owns floats [n * seg, (n + 1) * seg) of every row (seg = M * V)
+ *   CSK_SCRUB_POOL_RING   ring [depth][rows][row_floats] with rows = N and seg = row_floats = feat_c (pool_ring): stream n
+ *                         owns row n
+ * One launch covers up to CSK_CO_SCRUB_MAX_JOBS jobs (a whole model is 21 block rings and the pooling ring) for the
+ * n_streams indices of the DEVICE array `streams` (values in [0, n_total), n_total = N; an index outside writes nothing).
+ * jobs is a HOST array.  The same entry serves the full reset (every slot of every ring) and the per-cycle scrub of a
+ * warming stream (the slots one cycle wrote; continual.py).  Segments need 4-byte alignment only; the store width follows
+ * the address.  n_streams == 0 and empty runs (n_slots == 0) are accepted and launch nothing.
+ * ------------------------------------------------------------------------------------------------ */
+#define CSK_CO_SCRUB_MAX_JOBS 24
+#define CSK_SCRUB_BLOCK_RING 0
+#define CSK_SCRUB_POOL_RING 1
+typedef struct csk_scrub_job {
+    float *ring;
+    int64_t row_floats;
+    int32_t depth, rows, slot0, n_slots, seg, kind;
+} csk_scrub_job;
+int csk_co_scrub_streams_f32(const csk_scrub_job *jobs, int n_jobs, const int32_t *streams, int n_streams, int n_total,
+                             void *stream);
+
 /*
  * S-TR spatial-attention graph unit (GcnUnitAttention, models/s_tr/s_tr.py:303-477, in the configuration STr / CoSTr build:
  * only_attention, no relative / adjacency / more_channels, data_bn, skip, BN; Nh = 8, dk = C_out / 4, dv = C_out).  Per
