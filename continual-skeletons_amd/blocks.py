@@ -58,9 +58,9 @@ class _Folded(nn.Module):
         """Modules whose tensors the packed operands are folded from (default: this module and everything below it)."""
         return [self]
 
-    def _snapshot(self):
+    def _snapshot(self, roots=None):
         tensors, modules, seen = [], [(self._modules, tuple(self._modules.items()))], set()   # own slots: a swapped child
-        for root in self._watched():
+        for root in self._watched() if roots is None else roots:
             for m in root.modules():
                 if id(m) in seen:
                     continue

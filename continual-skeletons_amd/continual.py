@@ -19,6 +19,7 @@ ring of block l is the input/residual history of block l+1, so the residual FIFO
 stride cycle of the 10-block stack) with one GCN launch and one multi-emission TCN launch per block,
 which is what fills the GPU at ~1000 streams; per-frame stepping is the same code with r = 1.
 """
+import contextlib
 import ctypes
 import math
 from collections import OrderedDict
@@ -29,9 +30,12 @@ import torch.nn as nn
 
 from . import blocks, fold, native
 from .blocks import GraphConvolution, SpatioTemporalBlock, TemporalConvolution, _Folded, init_weights, unity, zero
+from .co_plan import NativePlan
+from .co_reset import StreamReset
 from .models import layer_table, per_layer
 
-MAX_CYCLE = 8
+MAX_CYCLE = native.CO_MAX_CYCLE
+RES_MODE = {"none": 0, "identity": 1, "conv": 2}    # block residual as the step kernels and csk_co_layer.res_kind take it
 
 
 def y_slots(max_in: int) -> int:
@@ -48,6 +52,50 @@ def in_slots(max_in: int) -> int:
 
 def _round4(n: int) -> int:
     return (n + 3) // 4 * 4
+
+
+def emissions(s0: int, r: int, delay: int, stride: int):
+    """Of the steps ``s0 .. s0 + r - 1``, those that emit are the s >= delay with (s - delay) % stride == 0: returns
+    (first of them, how many), or (None, 0) if there is none."""
+    first = max(s0, delay)
+    first += (delay - first) % stride
+    if first >= s0 + r:
+        return None, 0
+    return first, (s0 + r - 1 - first) // stride + 1
+
+
+def ring_runs(s0: int, r: int, *depths: int):
+    """Yield ``(s, run)``: the frames ``s0 .. s0 + r - 1`` cut into runs that wrap in none of the rings of these depths (frame s
+    lives in slot s % depth), so that one launch can take a run with a constant slot stride."""
+    s, end = s0, s0 + r
+    while s < end:
+        run = min([end - s] + [d - s % d for d in depths])
+        yield s, run
+        s += run
+
+
+def frame_to_slot(x_t, slot):
+    """Store an (N, C, V) frame into a channel-major ring slot [C][P] (positions n * V + v; the padding up to P stays)."""
+    n, c, v = x_t.shape
+    slot[:, : n * v] = x_t.permute(1, 0, 2).reshape(c, n * v)
+
+
+def slot_to_frame(slot, n: int, v: int):
+    """The (N, C, V) frame held by a channel-major ring slot [C][P], as a contiguous tensor."""
+    return slot[:, : n * v].reshape(slot.shape[0], n, v).permute(1, 0, 2).contiguous()
+
+
+@contextlib.contextmanager
+def _snapshot(tensors, get_position, set_position):
+    """``forward_steps(update_state=False)``: several frames overwrite live window slots, so the steps run on the real state
+    and a copy of ``tensors`` and of the stepping position is put back afterwards, whatever the steps raise."""
+    keep, position = [t.clone() for t in tensors], get_position()
+    try:
+        yield
+    finally:
+        for t, k in zip(tensors, keep):
+            t.copy_(k)
+        set_position(position)
 
 
 def CoGraphConvolution(in_channels, out_channels, A, bn_momentum=0.1):
@@ -88,7 +136,7 @@ class CoTemporalConvolution(TemporalConvolution):
             None, 0, 0, 0, None, native.ptr(ops["bias"]), native.ptr(out), 1, 0,
             ops["c_in"], ops["c_out"], p, self.kernel_size, 0, 0, 0, 1, None, native.stream_of(out))
         native.check(rc, "csk_tcn_step_f32")
-        return out[:, : n * v].view(-1, n, v).permute(1, 0, 2).contiguous()
+        return slot_to_frame(out, n, v)
 
     def forward_step(self, x_t, update_state=True):
         """One frame.  ``update_state=False`` computes the step without advancing: the frame lands in the ring slot
@@ -97,31 +145,24 @@ class CoTemporalConvolution(TemporalConvolution):
         native.require_device_f32(x_t, "CoTemporalConvolution frame")
         n, c, v = x_t.shape
         p = self._state(n, v, x_t.device)
-        self._ring[self._s % self.kernel_size, :, : n * v] = x_t.permute(1, 0, 2).reshape(c, n * v)
-        s = self._s
-        out = None
-        if s >= self.delay and (s - self.delay) % self.stride == 0:
-            out = self._emit(n, v, p)
+        frame_to_slot(x_t, self._ring[self._s % self.kernel_size])
+        out = self._emit(n, v, p) if emissions(self._s, 1, self.delay, self.stride)[1] else None
         if update_state:
             self._s += 1
         return out
 
     def forward_steps(self, x, pad_end=False, update_state=True):
         n, c, t, v = x.shape
-        if not update_state:                       # several frames overwrite live window slots: keep a copy
+        if not update_state:
             self._state(n, v, x.device)
-            keep = (self._ring.clone(), self._s)
-            try:
+            with _snapshot([self._ring], lambda: self._s, lambda s: setattr(self, "_s", s)):
                 return self.forward_steps(x, pad_end, True)
-            finally:
-                self._ring.copy_(keep[0])
-                self._s = keep[1]
         outs = [o for o in (self.forward_step(x[:, :, i].contiguous()) for i in range(t)) if o is not None]
         if pad_end:
             p = self._state(n, v, x.device)
             for _ in range(self.padding):
                 self._ring[self._s % self.kernel_size].zero_()
-                if self._s >= self.delay and (self._s - self.delay) % self.stride == 0:
+                if emissions(self._s, 1, self.delay, self.stride)[1]:
                     outs.append(self._emit(n, v, p))
                 self._s += 1
         return torch.stack(outs, dim=2)
@@ -316,52 +357,39 @@ class CoSpatioTemporalBlock(SpatioTemporalBlock):
         if not 1 <= r <= st.max_in:
             raise ValueError(f"engine_advance handles 1..{st.max_in} frames per call of this block, got {r}")
         s0, p = st.s, st.p
-        split_step = self._use_split_step()
         if not flush and self._fusable(r, s0, V):
             return self._fused_advance(n_frames, V)
-        f = 0
-        while f < r:                               # per-frame graph conv, one launch per non-wrapping slot run
-            s = s0 + f
-            run = min(r - f, HIST - s % HIST, YRING - s % YRING)
+        split = dict(ksplit=st.gcn_ksplit, partial=st.partial) if st.gcn_ksplit > 1 else {}     # latency mode
+        for s, run in ring_runs(s0, r, YRING) if flush else ring_runs(s0, r, HIST, YRING):
             if flush:
                 st.y[s % YRING: s % YRING + run].zero_()
-            elif st.gcn_ksplit > 1:
+            elif hasattr(self.gcn, "stage"):     # per-frame graph conv, one launch per non-wrapping slot run
                 self.gcn.stage(st.xin[s % HIST], st.y[s % YRING], n_seg=run, frames=n_frames,
-                               x_strides=(self.in_channels * p, p), y_strides=(self.out_channels * p, p),
-                               ksplit=st.gcn_ksplit, partial=st.partial)
-            elif hasattr(self.gcn, "stage"):
-                self.gcn.stage(st.xin[s % HIST], st.y[s % YRING], n_seg=run, frames=n_frames,
-                               x_strides=(self.in_channels * p, p), y_strides=(self.out_channels * p, p))
+                               x_strides=(self.in_channels * p, p), y_strides=(self.out_channels * p, p), **split)
             else:
                 self._foreign_gcn_stage(st, s, run, n_frames, V)
-            f += run
-        first = next((s for s in range(s0, s0 + r) if s >= self.delay and (s - self.delay) % self.stride == 0), None)
+        first, n_emit = emissions(s0, r, self.delay, self.stride)
         st.s += r
-        if first is None:
+        if not n_emit:
             return None
-        n_emit = (s0 + r - 1 - first) // self.stride + 1
         ops = self._packed_ops(st.y.device)
         lag = (k - 1) // 2              # emission s pairs with input frame s - 4 (co.Delay / residual_shrink)
-        mode = {"none": 0, "identity": 1, "conv": 2}[self.kind]
-        slot0 = st.e % OUT
+        mode, slot0 = RES_MODE[self.kind], st.e % OUT
+        if self._use_split_step():      # csk_tcn_step_bf16x3: the same rings and slot arithmetic, the split weight images (no split-K)
+            launcher, w, w_res, splitk = "tcn_step_split_launch", ops["w_split"], ops["w_res_split"], ()
+        else:
+            launcher, w, w_res, splitk = "tcn_step_launch", ops["w"], ops["w_res"], (st.ksplit, native.ptr(st.partial))
         # one launch; with split-K at most max_emit emissions per launch (the scratch holds that many partial sums) --
         # only the end-padding flush of a stack exceeds it (per-output summation order does not depend on the grouping)
         group = n_emit if (st.partial is None or st.ksplit <= 1) else min(n_emit, st.max_emit)     # only a split temporal conv is bound by the scratch
         for e0 in range(0, n_emit, group):
             ne, f0 = min(group, n_emit - e0), first + e0 * self.stride
-            if split_step:          # csk_tcn_step_bf16x3: the same rings and slot arithmetic, the split weight images (no split-K)
-                blocks.tcn_step_split_launch(
-                    native.ptr(st.y), YRING, f0 % YRING, self.stride, ne, native.ptr(ops["w_split"]),
-                    native.ptr(st.xin) if mode else None, HIST, (f0 - lag) % HIST, self.stride,
-                    native.ptr(ops["w_res_split"]), native.ptr(ops["bias"]), native.ptr(st.out), OUT, (slot0 + e0) % OUT,
-                    self.out_channels, self.out_channels, p, k, mode, self.in_channels if mode else 0, 1, native.stream_of(st.y))
-                continue
-            blocks.tcn_step_launch(
-                native.ptr(st.y), YRING, f0 % YRING, self.stride, ne, native.ptr(ops["w"]),
+            getattr(blocks, launcher)(      # looked up per call: tools and tests time / count launches by replacing the attribute
+                native.ptr(st.y), YRING, f0 % YRING, self.stride, ne, native.ptr(w),
                 native.ptr(st.xin) if mode else None, HIST, (f0 - lag) % HIST, self.stride,
-                native.ptr(ops["w_res"]), native.ptr(ops["bias"]), native.ptr(st.out), OUT, (slot0 + e0) % OUT,
-                self.out_channels, self.out_channels, p, k, mode, self.in_channels if mode else 0, 1,
-                st.ksplit, native.ptr(st.partial) if st.partial is not None else None, native.stream_of(st.y))
+                native.ptr(w_res), native.ptr(ops["bias"]), native.ptr(st.out), OUT, (slot0 + e0) % OUT,
+                self.out_channels, self.out_channels, p, k, mode, self.in_channels if mode else 0, 1, *splitk,
+                native.stream_of(st.y))
         st.e += n_emit
         return slot0, n_emit
 
@@ -391,36 +419,52 @@ class CoSpatioTemporalBlock(SpatioTemporalBlock):
         cnt = g["ell_cnt_host"]
         return int(cnt[0]) <= 1 and int(cnt[1]) <= 1 and int(cnt[2]) <= 4 and ((64 + V - 2) // V + 1) * V <= 128
 
+    def _layer_struct(self, device):
+        """(csk_co_layer of this block, objects to keep alive): the packed graph-conv and temporal-conv operands and the bound
+        state as the native side takes them -- the plan as an array of these (co_plan.py), csk_co_block_step_f32 field by
+        field (``_fused_advance``).  ``keep`` = [graph-conv operands, temporal-conv operands]."""
+        g, t, st = self.gcn._packed_ops(device), self._packed_ops(device), self._state
+        L = native.CoLayer()
+        L.c_in, L.c_out, L.stride, L.res_kind = self.in_channels, self.out_channels, self.stride, RES_MODE[self.kind]
+        L.gcn_res_mode, L.ell_w = g["res_mode"], g["ell_w"]
+        L.ell_cnt[:] = [int(c) for c in g["ell_cnt_host"][:3]]
+        L.gcn_w, L.gcn_bias, L.ell_src = g["w"].data_ptr(), g["bias"].data_ptr(), g["ell_src"].data_ptr()
+        L.ell_val = g["ell_val"].data_ptr() if g["ell_val"] is not None else None
+        L.tcn_w, L.tcn_bias = t["w"].data_ptr(), t["bias"].data_ptr()
+        L.tcn_w_res = t["w_res"].data_ptr() if t["w_res"] is not None else None
+        L.y_ring, L.out_ring = st.y.data_ptr(), st.out.data_ptr()
+        L.y_slots, L.out_slots, L.tcn_ksplit = st.y.shape[0], st.out.shape[0], st.ksplit
+        L.partial_emits = st.max_emit if (st.partial is not None and st.ksplit > 1) else 0
+        L.gcn_ksplit, L.gcn_partial_frames = st.gcn_ksplit, (st.max_in if st.gcn_ksplit > 1 else 0)
+        L.tcn_partial = st.partial.data_ptr() if st.partial is not None else None
+        return L, [g, t]
+
     def _fused_advance(self, n_skel: int, V: int):
-        st = self._state
-        HIST, YRING, OUT = st.xin.shape[0], st.y.shape[0], st.out.shape[0]
-        g, t = self.gcn._packed_ops(st.y.device), self._packed_ops(st.y.device)
-        s0, slot0 = st.s, st.e % OUT
+        st, P = self._state, ctypes.c_void_p
+        L, (g, _) = self._layer_struct(st.y.device)
+        HIST, s0, slot0 = st.xin.shape[0], st.s, st.e % L.out_slots
         rc = native.lib().csk_co_block_step_f32(
-            native.ptr(st.xin), HIST, s0 % HIST, self.in_channels, native.ptr(g["w"]), native.ptr(g["bias"]),
-            native.ptr(g["ell_src"]), native.ptr(g["ell_val"]), native.ptr(g["ell_cnt_host"]), g["ell_w"], g["res_mode"],
-            native.ptr(st.y), YRING, s0 % YRING, native.ptr(t["w"]), native.ptr(t["bias"]),
-            {"none": 0, "identity": 1}[self.kind], (s0 - (self.kernel_size - 1) // 2) % HIST, native.ptr(st.out), OUT, slot0,
-            self.out_channels, n_skel, V, st.p, native.stream_of(st.y))
+            native.ptr(st.xin), HIST, s0 % HIST, L.c_in, P(L.gcn_w), P(L.gcn_bias), P(L.ell_src), P(L.ell_val),
+            native.ptr(g["ell_cnt_host"]), L.ell_w, L.gcn_res_mode,       # the entry reads the counts through a host pointer
+            P(L.y_ring), L.y_slots, s0 % L.y_slots, P(L.tcn_w), P(L.tcn_bias),
+            L.res_kind, (s0 - (self.kernel_size - 1) // 2) % HIST, P(L.out_ring), L.out_slots, slot0,
+            L.c_out, n_skel, V, st.p, native.stream_of(st.y))
         native.check(rc, "csk_co_block_step_f32")
-        st.s += 4
-        st.e += 4
+        st.s, st.e = st.s + 4, st.e + 4
         return slot0, 4
 
     def _foreign_gcn_stage(self, st, s: int, run: int, n_frames: int, V: int):
         """Graph-conv modules without a native ``stage`` (e.g. the S-TR spatial attention a sibling model passes as
         ``CoGraphConv``, models/base.py:390-400): applied per frame as ``module(x_t.unsqueeze(2)).squeeze(2)``
         (base.py:273-276) on (NM, C, 1, V) tensors converted from / to the channel-major ring slots."""
-        q = n_frames * V
         HIST, YRING = st.xin.shape[0], st.y.shape[0]
         for j in range(run):
             xs, ys = st.xin[(s + j) % HIST], st.y[(s + j) % YRING]
-            x_t = xs[:, :q].reshape(self.in_channels, n_frames, V).permute(1, 0, 2).unsqueeze(2).contiguous()
-            y_t = self.gcn(x_t)
+            y_t = self.gcn(slot_to_frame(xs, n_frames, V).unsqueeze(2))
             if tuple(y_t.shape) != (n_frames, self.out_channels, 1, V) or y_t.dtype != torch.float32 or y_t.device != xs.device:
                 raise RuntimeError(f"graph-conv module returned {tuple(y_t.shape)} {y_t.dtype} on {y_t.device}, expected "
                                    f"{(n_frames, self.out_channels, 1, V)} float32 on {xs.device}")
-            ys[:, :q] = y_t.squeeze(2).permute(1, 0, 2).reshape(self.out_channels, q)
+            frame_to_slot(y_t.squeeze(2), ys)
 
     def engine_step(self, n_frames: int, V: int, flush: bool = False) -> Optional[int]:
         """One frame; returns the output-ring slot of this step's emission or None."""
@@ -442,31 +486,25 @@ class CoSpatioTemporalBlock(SpatioTemporalBlock):
             raise RuntimeError(f"expected (N, {self.in_channels}, V) frame, got {tuple(x_t.shape)}")
         st = self._ensure_state(n, v, x_t.device)
         keep = (st.s, st.e)
-        st.xin[st.s % st.xin.shape[0], :, : n * v] = x_t.permute(1, 0, 2).reshape(c, n * v)
+        frame_to_slot(x_t, st.xin[st.s % st.xin.shape[0]])
         slot = self.engine_step(n, v)
         if not update_state:       # one step only touches ring slots that are older than every window: counters suffice
             st.s, st.e = keep
-        if slot is None:
-            return None
-        return st.out[slot, :, : n * v].view(self.out_channels, n, v).permute(1, 0, 2).contiguous()
+        return None if slot is None else slot_to_frame(st.out[slot], n, v)
 
     def forward_steps(self, x, pad_end=False, update_state=True):
         n, c, t, v = x.shape
-        if not update_state:                       # several frames overwrite live window slots: keep a copy
+        if not update_state:
             st = self._ensure_state(n, v, x.device)
-            keep = (st.y.clone(), st.out.clone(), st.xin.clone(), st.s, st.e)
-            try:
+            with _snapshot([st.y, st.out, st.xin], lambda: list(st._ctr), lambda ctr: st._ctr.__setitem__(slice(None), ctr)):
                 return self.forward_steps(x, pad_end, True)
-            finally:
-                st.y.copy_(keep[0]); st.out.copy_(keep[1]); st.xin.copy_(keep[2])
-                st.s, st.e = keep[3], keep[4]
         outs = [o for o in (self.forward_step(x[:, :, i].contiguous()) for i in range(t)) if o is not None]
         if pad_end:
             st = self._state
             for _ in range(self.padding):
                 slot = self.engine_step(n, v, flush=True)
                 if slot is not None:
-                    outs.append(st.out[slot, :, : n * v].view(self.out_channels, n, v).permute(1, 0, 2).contiguous())
+                    outs.append(slot_to_frame(st.out[slot], n, v))
         return torch.stack(outs, dim=2)
 
 
@@ -516,14 +554,15 @@ def co_geometry(c_in=3):
     return r, p, s
 
 
-class CoStGcn(_Folded):
+class CoStGcn(NativePlan, StreamReset, _Folded):
     """CoST-GCN: models/cost_gcn/cost_gcn.py:21-41 + CoModelBase (models/base.py:68-227) without the Ride shell.
 
     ``forward_step(x_t: (N, C, V, M))`` -> logits (N, classes) on the steps where the whole stack (10 blocks,
     total stride 4) and the temporal average pool emit, else None.  ``forward_steps(x: (N, C, T, V, M))``
     -> (N, classes, n_predictions).  ``forward(x)`` = clip mode of CoModelBase.forward (base.py:166-181).
     state_dict keys equal the reference's (``layers.layerK.0.1.gcn...``); a regular StGcn state_dict loads too
-    (what ``map_state_dict`` does in the reference, base.py:200-224).
+    (what ``map_state_dict`` does in the reference, base.py:200-224).  This class binds the state slab and steps on it; the
+    native plan (co_plan.py: NativePlan) and the per-stream reset (co_reset.py: StreamReset) are base classes.
     """
 
     # False: drive every launch from Python (same kernels, same results).  Read on every cycle: both engines step on the one
@@ -580,6 +619,8 @@ class CoStGcn(_Folded):
         return [self.data_bn]
 
     # ---- state slab --------------------------------------------------------------------------------
+    _blocks = property(lambda self: list(self.layers.values()), doc="the ten blocks in stack order")
+
     def _bind(self, n, device):
         c_in, _, v, m = self.input_shape
         p = _round4(n * m * v)
@@ -589,12 +630,12 @@ class CoStGcn(_Folded):
         # frames one launch of block i can receive / emit: max_cycle input frames / cumulative temporal stride.  They size
         # the rings (y: 8 + max_in, output = next block's input history: 4 + its max_in) and the split-K scratch, which is
         # ONE buffer sized by its largest user (launches of a model are stream-ordered)
-        recv, emits, cum = [], [], 1
-        for i in range(10):
+        blks, recv, emits, cum = self._blocks, [], [], 1
+        for blk in blks:
             recv.append(max(1, mc // cum))
-            cum *= self.layers[f"layer{i + 1}"].stride
+            cum *= blk.stride
             emits.append(max(1, mc // cum))
-        need = max(self.layers[f"layer{i + 1}"].scratch_floats(p, emits[i], recv[i]) for i in range(10))
+        need = max(blk.scratch_floats(p, emits[i], recv[i]) for i, blk in enumerate(blks))
         if need * 4 > self.LATENCY_SCRATCH_CAP_BYTES:
             raise RuntimeError(
                 f"set_latency_mode({self.layers.layer1.split_k}) on a slab of {n} streams needs a {need * 4 / 1e9:.2f} GB split-K "
@@ -605,12 +646,10 @@ class CoStGcn(_Folded):
         # THE stepping position, in the layout csk_co_plan_cycle takes (include/cskel.h): {frames, features, then (received,
         # emitted) per block}.  _frames / _feats and every block's s / e are views of it; nothing else holds a counter
         self._ctr = (ctypes.c_int64 * 22)()
-        for i in range(10):
+        for i, blk in enumerate(blks):
             out_slots = in_slots(recv[i + 1]) if i < 9 else max(4, emits[i])
-            st = self.layers[f"layer{i + 1}"].bind_state(p, device, xin, max_emit=emits[i], scratch=self._scratch,
-                                                         max_in=recv[i], out_slots=out_slots,
-                                                         counters=(ctypes.c_int64 * 2).from_buffer(self._ctr, 16 * (i + 1)))
-            xin = st.out
+            xin = blk.bind_state(p, device, xin, max_emit=emits[i], scratch=self._scratch, max_in=recv[i], out_slots=out_slots,
+                                 counters=(ctypes.c_int64 * 2).from_buffer(self._ctr, 16 * (i + 1))).out
         self._pool_ring = torch.zeros((self.pool_size, n, 256), device=device, dtype=torch.float32)
         self._pooled = torch.empty((n, 256), device=device, dtype=torch.float32)
         self._flushed = False
@@ -645,161 +684,13 @@ class CoStGcn(_Folded):
         frame-step -- and removed: profiles/HISTORY.md.)  The split factor does not shrink with the slab (a stream's bits must
         not depend on its neighbours), so the scratch grows with it: binding a slab whose scratch would exceed
         LATENCY_SCRATCH_CAP_BYTES (1 GiB: about 300 NTU streams at split_k = 8) raises instead of silently running slower than the default mode."""
-        for i in range(10):
-            self.layers[f"layer{i + 1}"].split_k = int(split_k)
+        for blk in self._blocks:
+            blk.split_k = int(split_k)
         self._n = None
-
-    # ---- native executor ---------------------------------------------------------------------------
-    def _mark_weights_dirty(self, *args, **kwargs):
-        self.__dict__["_weights_dirty"] = True
-
-    def _install_dirty_hooks(self):
-        """load_state_dict on the model or ANY sub-module and .to() / .float() / ... (``_apply``) flag the plan's operands
-        as stale immediately; see _weights_changed for everything else."""
-        if self.__dict__.get("_dirty_hooks"):
-            return
-        for m in self.modules():
-            m.register_load_state_dict_post_hook(lambda mod, keys, net=self: net._mark_weights_dirty())
-        self.__dict__["_dirty_hooks"] = True
-
-    def _apply(self, fn, *args, **kwargs):
-        self._mark_weights_dirty()
-        return super()._apply(fn, *args, **kwargs)
-
-    def _weight_slots(self):
-        """Flat snapshot of where every parameter / buffer / sub-module of the model LIVES (owning ``_parameters`` /
-        ``_buffers`` / ``_modules`` dict + name) with the tensor's identity, storage pointer and version counter at the
-        time the native plan's operands were folded.  Walking the module tree costs ~0.65 ms per call; re-reading these
-        ~240 + ~140 dict slots costs ~0.06 ms, so _weights_changed can afford to be exact on every cycle."""
-        tensors, modules = [], []
-        for m in self.modules():
-            for d in (m._parameters, m._buffers):
-                for name, t in d.items():
-                    tensors.append((d, name, t, None if t is None else t.data_ptr(), None if t is None else t._version))
-            for name, child in m._modules.items():
-                modules.append((m._modules, name, child, len(m._modules)))
-        return tensors, modules
-
-    def _weights_changed(self) -> bool:
-        """Staleness check of the native plan's operands, once per cycle, EXACT and immediate for every way the weights
-        can change: load_state_dict / .to() (dirty flag set by hooks), a replaced Parameter or buffer
-        (``net.fc.weight = nn.Parameter(..)``: the slot holds another object), a swapped, added or removed sub-module
-        (``net.layers.layer3.tcn.bn = ...``: the ``_modules`` slot holds another object / the dict changed size), an
-        in-place edit (``p.add_(..)``: version counter) and ``p.data = ...`` (storage pointer)."""
-        if self.__dict__.pop("_weights_dirty", False):
-            return True
-        tensors, modules = self._plan_keep[1]
-        for d, name, t, ptr, ver in tensors:
-            cur = d.get(name)
-            if cur is not t or (t is not None and (cur._version != ver or cur.data_ptr() != ptr)):
-                return True
-        for d, name, child, size in modules:
-            if d.get(name) is not child or len(d) != size:
-                return True
-        return False
-
-    def refold(self):
-        super().refold()
-        self._mark_weights_dirty()
-
-    def _layer_structs(self, device):
-        """(ctypes array of csk_co_layer, objects to keep alive) from the blocks' packed operands and state."""
-        arr, keep = (native.CoLayer * 10)(), []
-        for i in range(10):
-            blk = self.layers[f"layer{i + 1}"]
-            g, t, st = blk.gcn._packed_ops(device), blk._packed_ops(device), blk._state
-            keep += [g, t]
-            L = arr[i]
-            L.c_in, L.c_out, L.stride = blk.in_channels, blk.out_channels, blk.stride
-            L.res_kind = {"none": 0, "identity": 1, "conv": 2}[blk.kind]
-            L.gcn_res_mode, L.ell_w = g["res_mode"], g["ell_w"]
-            for j in range(3):
-                L.ell_cnt[j] = int(g["ell_cnt_host"][j])
-            L.gcn_w, L.gcn_bias = g["w"].data_ptr(), g["bias"].data_ptr()
-            L.ell_src = g["ell_src"].data_ptr()
-            L.ell_val = g["ell_val"].data_ptr() if g["ell_val"] is not None else None
-            L.tcn_w, L.tcn_bias = t["w"].data_ptr(), t["bias"].data_ptr()
-            L.tcn_w_res = t["w_res"].data_ptr() if t["w_res"] is not None else None
-            L.y_ring, L.out_ring = st.y.data_ptr(), st.out.data_ptr()
-            L.tcn_ksplit = st.ksplit
-            L.y_slots, L.out_slots = st.y.shape[0], st.out.shape[0]
-            L.partial_emits = st.max_emit if (st.partial is not None and st.ksplit > 1) else 0
-            L.gcn_ksplit, L.gcn_partial_frames = st.gcn_ksplit, (st.max_in if st.gcn_ksplit > 1 else 0)
-            L.tcn_partial = st.partial.data_ptr() if st.partial is not None else None
-            L.agcn_inter = L.agcn_adj_frames = 0
-            if type(blk.gcn) is not GraphConvolution:      # adaptive graph conv: adjacency per skeleton frame (agcn.py)
-                a = blk.gcn.plan_operands(device)
-                adj = self.__dict__.get("_agcn_adj")
-                need = self.max_cycle * self._n * self.input_shape[3] * 3 * self.input_shape[2] ** 2      # [cycle frames][skeletons][3][V][V]
-                if adj is None or adj.numel() < need or adj.device != st.y.device:
-                    adj = self.__dict__["_agcn_adj"] = torch.empty((need,), device=st.y.device, dtype=torch.float32)
-                L.agcn_inter, L.agcn_adj_frames = a["inter"], self.max_cycle
-                L.agcn_w_pairs, L.agcn_b_pairs, L.agcn_a_sum = a["w_pairs"].data_ptr(), a["b_pairs"].data_ptr(), a["a_sum"].data_ptr()
-                L.agcn_adj = adj.data_ptr()
-                L.ell_val = None
-        ops = self._packed_ops(device)
-        fcw, fcb = self.fc.weight.detach(), self.fc.bias.detach()
-        keep += [ops, fcw, fcb]
-        return arr, keep, ops, fcw, fcb
-
-    def _build_plan(self, device):
-        """csk_co_plan (include/cskel.h): one C call per cycle instead of ~25 (CoAGCN: ~45) ctypes calls.  Built for stacks of
-        plain GraphConvolution blocks and of adaptive graph convs in the shapes the fused embedding + attention entry
-        covers (``plan_operands``); other graph convs keep the Python engine below.  No plan is built while any block has a
-        step precision other than "f32" (set_step_precision): ``csk_co_layer`` carries no split weight images, so that mode
-        runs on the Python engine (``_python_cycle``); plan support would change the struct and is out of scope."""
-        self._destroy_plan()
-        if not self.use_native_plan:
-            return
-        if any(self.layers[f"layer{i + 1}"].step_precision != "f32" for i in range(10)):
-            return
-        for i in range(10):
-            gcn = self.layers[f"layer{i + 1}"].gcn
-            if type(gcn) is GraphConvolution:
-                continue
-            if getattr(gcn, "plan_operands", None) is None or gcn.plan_operands(device) is None:
-                return
-        c, _, v, m = self.input_shape
-        arr, keep, ops, fcw, fcb = self._layer_structs(device)
-        plan = native.lib().csk_co_plan_create(10, ctypes.byref(arr), native.ptr(self._xin0), self._xin0.shape[0], self._n, c, v, m, self._p,
-                                               native.ptr(ops["scale"]), native.ptr(ops["shift"]), self.num_classes,
-                                               native.ptr(fcw), native.ptr(fcb), self.pool_size, self.pool_padding,
-                                               native.ptr(self._pool_ring), native.ptr(self._pooled))
-        if not plan:
-            raise RuntimeError("csk_co_plan_create: " + native.lib().csk_last_error().decode())
-        self.__dict__["_plan"] = plan
-        self._install_dirty_hooks()
-        self.__dict__["_plan_keep"] = (keep, self._weight_slots())
-        self.__dict__.pop("_weights_dirty", None)
-        fuse = all(self.layers[f"layer{i + 1}"].fuse_step for i in range(10))
-        native.check(native.lib().csk_co_plan_set_fusion(plan, int(fuse)), "csk_co_plan_set_fusion")
-
-    def _refresh_plan_weights(self, device):
-        """Weights were reloaded / edited in place: refold and hand the new operands to the plan; the
-        continual state and its counters are untouched (same semantics as the reference, where weights and
-        state buffers are independent)."""
-        arr, keep, ops, fcw, fcb = self._layer_structs(device)
-        rc = native.lib().csk_co_plan_update_weights(self._plan, 10, ctypes.byref(arr), native.ptr(ops["scale"]),
-                                                     native.ptr(ops["shift"]), native.ptr(fcw), native.ptr(fcb))
-        native.check(rc, "csk_co_plan_update_weights")
-        self.__dict__["_plan_keep"] = (keep, self._weight_slots())
-
-    def _destroy_plan(self):
-        plan = self.__dict__.pop("_plan", None)
-        if plan:
-            native.lib().csk_co_plan_destroy(plan)
-        self.__dict__.pop("_plan_keep", None)
-
-    def __del__(self):
-        try:
-            self._destroy_plan()
-        except Exception:
-            pass
 
     def state_bytes(self):
         """Persistent continual state (input ring, per-block rings, pooling window)."""
-        return sum(self.layers[f"layer{i + 1}"]._state.nbytes() for i in range(10)) + 4 * (
-            self._xin0.numel() + self._pool_ring.numel())
+        return sum(blk._state.nbytes() for blk in self._blocks) + 4 * (self._xin0.numel() + self._pool_ring.numel())
 
     def scratch_bytes(self):
         """Transient scratch, not state: the split-K partial sums (shared by the blocks that split their K loop) and, for
@@ -810,165 +701,12 @@ class CoStGcn(_Folded):
     def clean_state(self):
         if self._n is not None:
             self._xin0.zero_()
-            for i in range(10):
-                self.layers[f"layer{i + 1}"].clean_state()
+            for blk in self._blocks:
+                blk.clean_state()
             self._pool_ring.zero_()
             self._set_counters([0] * 22)
             self._flushed = False
             self._forget_resets()
-
-    # ---- per-stream reset ----------------------------------------------------------------------------
-    # One stream of the slab starts over while the others run on ("Per-stream reset").  Zeroing the stream's
-    # slice of every ring is not enough: in a running slab every launch emits for every stream, so a block whose window is
-    # still filling pushes ReLU(bias + partial window) into the rings below it, where a fresh model pushes nothing.  With
-    # D(L) = cumulative delay through block L in input frames, block L of a stream of age a (frames since its reset) is
-    # live -- would run in a fresh model -- once a >= D(L-1), and emits once a >= D(L).  Every D(L) is a multiple of the
-    # total stride, so a stream reset at a multiple of it and stepped in cycles that do not cross one has every block
-    # wholly live or wholly not in each cycle: after the cycle's launches, what the not-yet-live blocks wrote for the
-    # stream is zeroed again (csk_co_scrub_streams_f32) and its state is a fresh model's.  The step kernels do not change.
-
-    _scrub_warming = True   # private test switch: False leaves the per-cycle scrub out (the naive zero-only reset)
-
-    def _forget_resets(self):
-        """Ages count from the clean state: no stream was reset, nothing warms."""
-        self._reset_at = [0] * (self._n or 0)     # input frame count at which each stream last started over
-        self._cohorts = {}                        # reset frame -> (stream indices, device int32 copy), while they warm
-
-    def _cum_delays(self):
-        """[D(0) .. D(10)]: D(L) = D(L-1) + delay_L * (cumulative stride in front of block L), from the blocks."""
-        d, cum, out = 0, 1, [0]
-        for i in range(10):
-            blk = self.layers[f"layer{i + 1}"]
-            d += blk.delay * cum
-            cum *= blk.stride
-            out.append(d)
-        return out
-
-    def _ready_age(self):
-        """Frames after which a fresh model has returned its first logits: layer 10 emits at frame indices D(10) + j * stride
-        and the pooling window emits from its (pool_size - pool_padding)-th entry on."""
-        return self._cum_delays()[10] + self.stride * max(0, self.pool_size - self.pool_padding - 1) + 1
-
-    def _require_bound(self, what):
-        if self._n is None:
-            raise RuntimeError(f"{what}: no state slab is bound yet (step once, or after set_max_cycle / set_latency_mode step again)")
-
-    def stream_ages(self):
-        """(N,) int64 CPU tensor: frames each stream has received since its reset (``reset_streams``), since
-        ``clean_state()`` / the binding of the slab for streams never reset.  Host-side state, no GPU work."""
-        self._require_bound("stream_ages")
-        return torch.tensor([self._frames - r for r in self._reset_at], dtype=torch.int64)
-
-    def streams_ready(self):
-        """(N,) bool CPU tensor: True where a fresh model fed the stream's frames since its reset would already have returned
-        logits.  ``forward_step`` / ``forward_cycle`` return logits for all N streams; this mask says which rows mean
-        something."""
-        return self.stream_ages() >= self._ready_age()
-
-    def _warming(self):
-        return bool(self._cohorts)
-
-    def _check_reset(self, indices):
-        """Everything ``reset_streams`` refuses, checked on the host before anything is launched; returns the index list."""
-        if isinstance(indices, torch.Tensor) or not isinstance(indices, (list, tuple, range)):
-            raise ValueError("reset_streams takes a sequence of ints (a list, tuple or range), not a tensor: the indices are "
-                             "host-side bookkeeping and reading a device tensor would cost a sync")
-        idx = list(indices)
-        if any(isinstance(i, bool) or not isinstance(i, int) for i in idx):
-            raise ValueError(f"reset_streams takes ints, got {[type(i).__name__ for i in idx]}")
-        self._require_bound("reset_streams")
-        if self._flushed:
-            raise RuntimeError("the state was flushed by forward_steps(pad_end=True); call clean_state() instead")
-        if len(set(idx)) != len(idx):
-            raise ValueError(f"duplicate stream indices in {idx}")
-        if any(not 0 <= i < self._n for i in idx):
-            raise ValueError(f"stream indices {idx} outside a slab of {self._n} streams")
-        if self._frames % self.stride:
-            raise RuntimeError(f"streams can be reset when the frame count is a multiple of {self.stride} (it is {self._frames}): "
-                               "the stride phase of the strided blocks must match a fresh model's")
-        return idx
-
-    def _device_indices(self, idx):
-        host = torch.tensor(idx, dtype=torch.int32).pin_memory()
-        return host.to(self._xin0.device, non_blocking=True)       # stream-ordered copy from pinned memory: no host sync
-
-    def _scrub(self, jobs, dev_idx, count):
-        if not jobs:
-            return
-        if len(jobs) > native.SCRUB_MAX_JOBS:
-            raise RuntimeError(f"{len(jobs)} rings in one scrub launch (limit {native.SCRUB_MAX_JOBS})")
-        arr = (native.ScrubJob * len(jobs))(*jobs)
-        rc = native.lib().csk_co_scrub_streams_f32(ctypes.byref(arr), len(jobs), native.ptr(dev_idx), count, self._n,
-                                                   native.stream_of(self._xin0))
-        native.check(rc, "csk_co_scrub_streams_f32")
-
-    def _ring_job(self, ring, first, count):
-        """Job for slots ``first .. first + count - 1`` (frame / emission numbers, taken modulo the depth) of a block ring."""
-        depth, rows, p = ring.shape
-        mv = self.input_shape[3] * self.input_shape[2]
-        return native.ScrubJob(ring.data_ptr(), p, depth, rows, first % depth, min(count, depth), mv, native.SCRUB_BLOCK_RING)
-
-    def _pool_job(self, first, count):
-        depth, n, c = self._pool_ring.shape
-        return native.ScrubJob(self._pool_ring.data_ptr(), c, depth, n, first % depth, min(count, depth), c, native.SCRUB_POOL_RING)
-
-    def reset_streams(self, indices):
-        """Start the streams ``indices`` (sequence of distinct ints in [0, N)) over while the others run on: from the next
-        frame their features and predictions are bit for bit those of a fresh model fed their frames alone, available
-        ``streams_ready()`` says when.  Allowed when the frame count is a multiple of the total stride (4); while a reset
-        stream warms up, cycles must not cross a multiple of it (1-, 2-, 4-frame cycles aligned to it; ``_cycle``).  One
-        launch on the current stream (every slot of every ring and of the pooling window, for these streams), no host sync."""
-        idx = self._check_reset(indices)
-        if not idx:
-            return
-        dev = self._device_indices(idx)
-        jobs = [self._ring_job(self._xin0, 0, self._xin0.shape[0])]
-        for i in range(10):
-            st = self.layers[f"layer{i + 1}"]._state
-            jobs += [self._ring_job(st.y, 0, st.y.shape[0]), self._ring_job(st.out, 0, st.out.shape[0])]
-        jobs.append(self._pool_job(0, self.pool_size))
-        self._scrub(jobs, dev, len(idx))
-        again = set(idx)
-        for at, (members, _) in list(self._cohorts.items()):       # a stream reset again leaves its earlier cohort
-            left = [i for i in members if i not in again]
-            if len(left) != len(members):
-                if left:
-                    self._cohorts[at] = (left, self._device_indices(left))
-                else:
-                    del self._cohorts[at]
-        at = self._frames
-        if at in self._cohorts:                                    # a second call at the same frame: one cohort
-            idx = self._cohorts[at][0] + idx
-            dev = self._device_indices(idx)
-        self._cohorts[at] = (idx, dev)
-        for i in idx:
-            self._reset_at[i] = at
-
-    def _check_cycle_while_warming(self, r):
-        if self._cohorts and self._frames % self.stride + r > self.stride:
-            raise ValueError(f"a cycle of {r} frames at frame {self._frames} crosses a multiple of {self.stride} while reset streams "
-                             f"are warming up (streams_ready()): step in cycles of 1, 2 or {self.stride} frames aligned to it")
-
-    def _scrub_cycle(self, before):
-        """After the launches of a cycle that moved the counters from ``before`` to their present value: per cohort, zero what
-        the blocks that are not live yet for it wrote -- block L's y slots while age < D(L-1), its output slots while
-        age < D(L), the pooling-window slots while age < D(10) -- one launch per cohort; cohorts that are ready leave."""
-        after, d, ready = self._counters(), self._cum_delays(), self._ready_age()
-        for at, (idx, dev) in list(self._cohorts.items()):
-            age = before[0] - at
-            if age < d[10] and self._scrub_warming:
-                jobs = []
-                for i in range(10):
-                    st = self.layers[f"layer{i + 1}"]._state
-                    if age < d[i] and after[2 + 2 * i] > before[2 + 2 * i]:
-                        jobs.append(self._ring_job(st.y, before[2 + 2 * i], after[2 + 2 * i] - before[2 + 2 * i]))
-                    if age < d[i + 1] and after[3 + 2 * i] > before[3 + 2 * i]:
-                        jobs.append(self._ring_job(st.out, before[3 + 2 * i], after[3 + 2 * i] - before[3 + 2 * i]))
-                if after[1] > before[1]:
-                    jobs.append(self._pool_job(before[1], after[1] - before[1]))
-                self._scrub(jobs, dev, len(idx))
-            if after[0] - at >= ready:
-                del self._cohorts[at]
 
     # ---- stepping ------------------------------------------------------------------------------------
     def _cycle(self, frames, peek=False):
@@ -998,12 +736,12 @@ class CoStGcn(_Folded):
         if self._flushed:
             raise RuntimeError("the state was flushed by forward_steps(pad_end=True): the end padding has consumed ring slots "
                                "and advanced the blocks past the input frame count; call clean_state() before stepping on")
-        native_plan = self.use_native_plan and self.__dict__.get("_plan")
+        engine = self._plan_cycle if self.use_native_plan and self.__dict__.get("_plan") else self._python_cycle
         if not self._cohorts or peek:              # nothing warms: the cycle is the one that runs without any reset
-            return self._plan_cycle(frames) if native_plan else self._python_cycle(frames)
+            return engine(frames)
         self._check_cycle_while_warming(len(frames))
         before = self._counters()
-        res = self._plan_cycle(frames) if native_plan else self._python_cycle(frames)
+        res = engine(frames)
         self._scrub_cycle(before)
         return res
 
@@ -1014,31 +752,20 @@ class CoStGcn(_Folded):
     def _set_counters(self, snap):
         self._ctr[:] = snap
 
+    def _position(self):
+        """The stepping position beyond the tensors: counters, the flushed mark and the streams' ages (co_reset.py)."""
+        return self._counters(), self._flushed, list(self._reset_at), dict(self._cohorts)
+
+    def _set_position(self, position):
+        self._ctr[:], self._flushed, self._reset_at, self._cohorts = position
+
     def _state_tensors(self):
-        ts = [self._xin0, self._pool_ring, self._pooled]
-        for i in range(10):
-            st = self.layers[f"layer{i + 1}"]._state
-            ts += [st.y, st.out]
-        return ts
+        return [self._xin0, self._pool_ring, self._pooled] + [t for blk in self._blocks for t in (blk._state.y, blk._state.out)]
 
     def _ensure_bound(self, x_t):
         native.require_device_f32(x_t, "CoStGcn frame")
         if self._n != x_t.shape[0] or self._xin0.device != x_t.device:
             self._bind(x_t.shape[0], x_t.device)
-
-    def _plan_cycle(self, frames):
-        if self._weights_changed():
-            self._refresh_plan_weights(frames[0].device)
-        n = frames[0].shape[0]
-        ptrs = (ctypes.c_void_p * len(frames))(*[x_t.data_ptr() for x_t in frames])
-        logits = torch.empty((MAX_CYCLE, n, self.num_classes), device=frames[0].device, dtype=torch.float32)
-        slot, nf, nl = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
-        rc = native.lib().csk_co_plan_cycle(self._plan, self._ctr, 22, ptrs, len(frames), native.ptr(logits), ctypes.byref(slot),
-                                            ctypes.byref(nf), ctypes.byref(nl), native.stream_of(frames[0]))
-        native.check(rc, "csk_co_plan_cycle")      # a failed cycle leaves the counters as they were (include/cskel.h)
-        if nf.value == 0:
-            return None, 0, []
-        return slot.value, nf.value, [logits[j] for j in range(nl.value)]
 
     def _python_cycle(self, frames):
         """Same protocol driven from Python (any graph-conv module with a ``stage`` method)."""
@@ -1052,35 +779,34 @@ class CoStGcn(_Folded):
                                                     n, c, v, m, self._p, native.stream_of(frames[0]))
         native.check(rc, "csk_input_norm_frames_f32")
         self._frames += len(frames)
-        r, res = len(frames), None
-        for i in range(10):
-            res = self.layers[f"layer{i + 1}"].engine_advance(r, n * m, v)
+        r = len(frames)
+        for blk in self._blocks:
+            res = blk.engine_advance(r, n * m, v)
             if res is None:
                 return None, 0, []
             r = res[1]
-        outs, depth = [], self.layers["layer10"]._state.out.shape[0]
-        for j in range(res[1]):
-            o = self._head_step((res[0] + j) % depth, n)
-            if o is not None:
-                outs.append(o)
-        return res[0], res[1], outs
+        return res[0], res[1], self._emit_heads(res[0], res[1], n)
+
+    def _emit_heads(self, slot0, n_emit, n):
+        """Head steps of ``n_emit`` layer-10 emissions from output-ring slot ``slot0`` on (None: zero features) -> the logits released."""
+        depth = self.layers["layer10"]._state.out.shape[0]
+        outs = (self._head_step(None if slot0 is None else (slot0 + j) % depth, n) for j in range(n_emit))
+        return [o for o in outs if o is not None]
 
     def _head_step(self, slot, n):
         """spatial_pool -> co.AvgPool1d window -> co.Linear (base.py:84-101)."""
         _, _, v, m = self.input_shape
         st10 = self.layers["layer10"]._state
-        lib = native.lib()
         head = self._feats % self.pool_size
-        stream = native.stream_of(st10.out)
         self._feats += 1
         emit = self._feats >= self.pool_size - self.pool_padding
         count = min(self._feats, self.pool_size)
         logits = torch.empty((n, self.num_classes), device=st10.out.device, dtype=torch.float32) if emit else None
         # slot None: end padding of the pooling window (a zero feature enters it)
-        native.check(lib.csk_co_head_step_f32(
+        native.check(native.lib().csk_co_head_step_f32(
             native.ptr(st10.out[slot]) if slot is not None else None, native.ptr(self._pool_ring), native.ptr(self._pooled),
             native.ptr(self.fc.weight.detach()), native.ptr(self.fc.bias.detach()), native.ptr(logits), n, 256, m * v, self._p,
-            self.pool_size, head, count, int(emit), self.num_classes, stream), "csk_co_head_step_f32")
+            self.pool_size, head, count, int(emit), self.num_classes, native.stream_of(st10.out)), "csk_co_head_step_f32")
         return logits
 
     def features_step(self, x_t):
@@ -1095,13 +821,10 @@ class CoStGcn(_Folded):
         as well), so restoring the counters restores the state."""
         if update_state:
             outs = self._cycle([x_t])[2]
-            return outs[-1] if outs else None
-        self._ensure_bound(x_t)
-        snap = self._counters()
-        try:
-            outs = self._cycle([x_t], peek=True)[2]
-        finally:
-            self._set_counters(snap)
+        else:
+            self._ensure_bound(x_t)
+            with _snapshot((), self._counters, self._set_counters):
+                outs = self._cycle([x_t], peek=True)[2]
         return outs[-1] if outs else None
 
     def forward_cycle(self, frames):
@@ -1114,18 +837,10 @@ class CoStGcn(_Folded):
         through to every module as in the reference (base.py:187-190): each block's temporal conv is flushed with its
         ``padding`` zero frames, first block first, so that the stack emits what the clip stack computes for the same
         frames, and the temporal average pool is flushed with ``pool_padding`` zero features."""
-        if not update_state:                       # several frames overwrite live window slots: keep a copy of the slab
+        if not update_state:
             self._ensure_bound(x[:, :, 0].contiguous())
-            snap, keep, flushed = self._counters(), [t.clone() for t in self._state_tensors()], self._flushed
-            ages = (list(self._reset_at), dict(self._cohorts))      # the streams' ages are part of the stepping position
-            try:
+            with _snapshot(self._state_tensors(), self._position, self._set_position):
                 return self.forward_steps(x, pad_end, True)
-            finally:
-                for t, k in zip(self._state_tensors(), keep):
-                    t.copy_(k)
-                self._set_counters(snap)
-                self._flushed = flushed
-                self._reset_at, self._cohorts = ages
         if pad_end and self._cohorts:
             raise RuntimeError("forward_steps(pad_end=True) while reset streams are warming up (streams_ready()): the end padding "
                                "flushes every block for every stream, live for the stream or not")
@@ -1149,28 +864,20 @@ class CoStGcn(_Folded):
         either; a caller that wants to go on uses ``update_state=False``, which runs the flush on a snapshot)."""
         n = self._n
         _, _, v, m = self.input_shape
-        outs, depth = [], self.layers["layer10"]._state.out.shape[0]
-        for i in range(10):
-            blk = self.layers[f"layer{i + 1}"]
+        outs, blks = [], self._blocks
+        for i, blk in enumerate(blks):
             left = blk.padding
             while left:                                # at most max_in frames per launch (ring depths); order is unchanged
                 r = min(left, blk._state.max_in)
                 left -= r
                 res = blk.engine_advance(r, n * m, v, flush=True)
-                for j in range(i + 1, 10):             # what block i released travels down the rest of the stack
+                for below in blks[i + 1:]:             # what block i released travels down the rest of the stack
                     if res is None:
                         break
-                    res = self.layers[f"layer{j + 1}"].engine_advance(res[1], n * m, v)
+                    res = below.engine_advance(res[1], n * m, v)
                 if res is not None:
-                    for jj in range(res[1]):
-                        o = self._head_step((res[0] + jj) % depth, n)
-                        if o is not None:
-                            outs.append(o)
-        for _ in range(self.pool_padding):         # co.AvgPool1d end padding: zero features enter the window
-            o = self._head_step(None, n)
-            if o is not None:
-                outs.append(o)
-        return outs
+                    outs += self._emit_heads(res[0], res[1], n)
+        return outs + self._emit_heads(None, self.pool_padding, n)     # co.AvgPool1d end padding: zero features enter the window
 
     def forward(self, x, forward_mode="clip"):
         """CoModelBase.forward (base.py:166-181).  'clip': whole-clip computation with the continual head
@@ -1205,8 +912,8 @@ class CoStGcn(_Folded):
         rc = native.lib().csk_input_norm_f32(native.ptr(x), native.ptr(ops["scale"]), native.ptr(ops["shift"]),
                                              native.ptr(h), n, c, t, v, m, c * t * v, t * v, native.stream_of(x))
         native.check(rc, "csk_input_norm_f32")
-        for i in range(10):
-            h = SpatioTemporalBlock.forward(self.layers[f"layer{i + 1}"], h)
+        for blk in self._blocks:
+            h = SpatioTemporalBlock.forward(blk, h)
         return h
 
     def warm_up(self, n, device, frames=None):

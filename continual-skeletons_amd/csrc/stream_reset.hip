@@ -1,7 +1,7 @@
 // stream_reset.hip -- zero the state of SOME streams of the continual slab (csk_co_scrub_streams_f32, include/cskel.h).
 // One launch takes a table of jobs (ring, run of slots) and a device list of stream indices and zeroes, in every row of
 // every slot of each run, the segments of those streams -- nothing else: not the neighbouring streams, not the P-padding
-// behind the last one.  Two uses (continual.py): the full reset of a stream (all slots of every ring) and the per-cycle
+// behind the last one.  Two uses (co_reset.py): the full reset of a stream (all slots of every ring) and the per-cycle
 // scrub of what the not-yet-live blocks wrote for a warming stream (the slots one cycle wrote).  HBM-bound stores only.
 #include "mfma_core.h"
 

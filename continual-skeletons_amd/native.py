@@ -73,6 +73,7 @@ class ScrubJob(C.Structure):
                 ("slot0", C.c_int32), ("n_slots", C.c_int32), ("seg", C.c_int32), ("kind", C.c_int32)]
 
 
+CO_MAX_CYCLE = 8        # CSK_CO_MAX_CYCLE: frames one cycle may carry = logits slices csk_co_plan_cycle may write
 SCRUB_MAX_JOBS = 24
 SCRUB_BLOCK_RING, SCRUB_POOL_RING = 0, 1
 

@@ -495,7 +495,7 @@ int csk_co_plan_cycle(csk_co_plan *plan, int64_t *counters, int n_counters, cons
  * One launch covers up to CSK_CO_SCRUB_MAX_JOBS jobs (a whole model is 21 block rings and the pooling ring) for the
  * n_streams indices of the DEVICE array `streams` (values in [0, n_total), n_total = N; an index outside writes nothing).
  * jobs is a HOST array.  The same entry serves the full reset (every slot of every ring) and the per-cycle scrub of a
- * warming stream (the slots one cycle wrote; continual.py).  Segments need 4-byte alignment only; the store width follows
+ * warming stream (the slots one cycle wrote; co_reset.py).  Segments need 4-byte alignment only; the store width follows
  * the address.  n_streams == 0 and empty runs (n_slots == 0) are accepted and launch nothing.
  * ------------------------------------------------------------------------------------------------ */
 #define CSK_CO_SCRUB_MAX_JOBS 24

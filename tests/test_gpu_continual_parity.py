@@ -386,6 +386,35 @@ def test_update_state_false_peeks_without_advancing():
                 assert torch.equal(got, want) and torch.equal(peek, want), t
 
 
+@pytest.mark.parametrize("pad_end", [False, True])
+@pytest.mark.parametrize("kind", ["conv", "block"])
+def test_multi_frame_peek_restores_rings_and_counters_bitwise(kind, pad_end):
+    """forward_steps(update_state=False) of the bare continual temporal conv and of a stand-alone block (4 -> 8 channels,
+    stride 2, conv residual), from a state 5 frames in: every ring and counter is afterwards bit for bit what it was, and the
+    output is what the same call with update_state=True returns from that state."""
+    if kind == "conv":
+        m = pkg.CoTemporalConvolution(4, 8, padding="equal", stride=2).eval().to(DEV)
+    else:
+        m = pkg.CoSpatioTemporalBlock(4, 8, A, stride=2, padding="equal").eval().to(DEV)
+
+    def state():
+        if kind == "conv":
+            return [m._ring.clone()], m._s
+        st = m._state
+        return [st.y.clone(), st.out.clone(), st.xin.clone()], (st.s, st.e)
+
+    x = torch.rand(1, 4, 17, 25, device=DEV)
+    m.forward_steps(x[:, :, :5].contiguous())
+    rings, counters = state()
+    assert counters in (5, (5, 1))
+    peek = m.forward_steps(x[:, :, 5:].contiguous(), pad_end=pad_end, update_state=False)
+    rings_after, counters_after = state()
+    assert counters_after == counters and all(torch.equal(a, b) for a, b in zip(rings, rings_after))
+    real = m.forward_steps(x[:, :, 5:].contiguous(), pad_end=pad_end)
+    assert peek.shape[2] == (8 if pad_end else 6) and torch.equal(peek, real)
+    assert state()[1] != counters and not all(torch.equal(a, b) for a, b in zip(rings, state()[0]))     # the real run moved both
+
+
 @pytest.mark.parametrize("native_plan", [True, False])
 def test_latency_mode_split_k_matches_oracle_and_default(native_plan):
     """set_latency_mode (split-K in the TCN steps for a handful of streams): same predictions as the oracle and as
