@@ -1,5 +1,6 @@
 // executor.hip -- native step executor for the continual stack (host code only; launches go through the C ABI
-// entry points of gcn.hip / step.hip / head.hip).  Mirrors continual.py:CoSpatioTemporalBlock.engine_advance and
+// entry points of gcn.hip / step.hip / step16.hip / head.hip).  Mirrors continual.py:CoSpatioTemporalBlock.engine_advance
+// (advance_block: the two stages; run_blocks: the fused cycles, one csk_co_stack_step_f32 call per run of blocks) and
 // CoStGcn._python_cycle / _head_step one to one; the Python versions remain the reference for the protocol.  The stepping
 // position (frames, features, per-layer received / emitted) belongs to the caller: a cycle works on a copy of the caller's
 // counters and stores it back when every launch of the cycle was issued, so either driver can run any cycle.
@@ -26,24 +27,23 @@ struct csk_co_plan {
     int64_t P;
     const float *bn_scale, *bn_shift, *fc_w, *fc_b;
     float *pool_ring, *pooled;
-    bool fuse = true;          // csk_co_block_step_f32 for the blocks that qualify
+    bool fuse = true;          // one fused call for the blocks that qualify (run_blocks)
     int max_cycle = CSK_CO_MAX_CYCLE;   // frames one cycle may carry = what the rings were sized for (xin0_slots - 4, at most 8)
 };
 
+// csk_co_plan_create returns a pointer: a refusal leaves its message and no plan
+
+#define CREATE_FAIL(...) do { snprintf(csk_err_buf(), 256, __VA_ARGS__); return nullptr; } while (0)
 extern "C" csk_co_plan *csk_co_plan_create(int n_layers, const csk_co_layer *layers, float *xin0, int xin0_slots, int N, int C,
                                            int V, int M, int64_t P, const float *bn_scale, const float *bn_shift, int classes,
                                            const float *fc_w, const float *fc_b, int pool_size, int pool_padding,
                                            float *pool_ring, float *pooled) {
     if (n_layers <= 0 || !layers || !xin0 || N <= 0 || C <= 0 || V < 2 || M <= 0 || P < (int64_t)N * M * V || (P & 3) ||
         !bn_scale || !bn_shift || classes <= 0 || !fc_w || !fc_b || pool_size <= 0 || pool_padding < 0 ||
-        pool_padding >= pool_size || !pool_ring || !pooled) {
-        snprintf(csk_err_buf(), 256, "co_plan_create: bad argument");
-        return nullptr;
-    }
-    if (xin0_slots < CSK_CO_IN_SLOTS(1)) {
-        snprintf(csk_err_buf(), 256, "co_plan_create: the input ring needs >= %d slots, got %d", CSK_CO_IN_SLOTS(1), xin0_slots);
-        return nullptr;
-    }
+        pool_padding >= pool_size || !pool_ring || !pooled)
+        CREATE_FAIL("co_plan_create: bad argument");
+    if (xin0_slots < CSK_CO_IN_SLOTS(1))
+        CREATE_FAIL("co_plan_create: the input ring needs >= %d slots, got %d", CSK_CO_IN_SLOTS(1), xin0_slots);
     // the largest cycle the plan accepts is what the input ring was sized for: xin0_slots = CSK_CO_IN_SLOTS(max_cycle)
     const int max_cycle = xin0_slots - CSK_CO_IN_SLOTS(0) < CSK_CO_MAX_CYCLE ? xin0_slots - CSK_CO_IN_SLOTS(0) : CSK_CO_MAX_CYCLE;
     // ring depths against the frames one launch of each layer can receive / emit (include/cskel.h: CSK_CO_Y_SLOTS, CSK_CO_IN_SLOTS)
@@ -52,39 +52,27 @@ extern "C" csk_co_plan *csk_co_plan_create(int n_layers, const csk_co_layer *lay
         if (l.stride < 1 || l.stride > 2) break;                              // reported by the per-layer checks below
         const int max_emit = max_in / l.stride > 0 ? max_in / l.stride : 1;
         const int want_out = i + 1 < n_layers ? CSK_CO_IN_SLOTS(max_emit) : max_emit;
-        if (l.y_slots < CSK_CO_Y_SLOTS(max_in) || l.out_slots < want_out) {
-            snprintf(csk_err_buf(), 256, "co_plan_create: layer %d rings too shallow: y_slots %d (need >= %d), out_slots %d (need >= %d)", i,
-                     l.y_slots, CSK_CO_Y_SLOTS(max_in), l.out_slots, want_out);
-            return nullptr;
-        }
-        if (l.gcn_ksplit > 1 && (l.gcn_partial_frames < 1 || !l.tcn_partial || l.agcn_inter > 0)) {
-            snprintf(csk_err_buf(), 256, "co_plan_create: layer %d splits its graph conv but has no partial-sum buffer (or an adaptive graph conv)", i);
-            return nullptr;
-        }
-        if (l.tcn_ksplit > 1 && l.partial_emits < 1) {
-            snprintf(csk_err_buf(), 256, "co_plan_create: layer %d splits its K loop but partial_emits is %d", i, l.partial_emits);
-            return nullptr;
-        }
-        if (l.agcn_inter > 0 && l.agcn_adj_frames < 1) {
-            snprintf(csk_err_buf(), 256, "co_plan_create: layer %d has an adaptive graph conv but agcn_adj_frames is %d", i, l.agcn_adj_frames);
-            return nullptr;
-        }
+        if (l.y_slots < CSK_CO_Y_SLOTS(max_in) || l.out_slots < want_out)
+            CREATE_FAIL("co_plan_create: layer %d rings too shallow: y_slots %d (need >= %d), out_slots %d (need >= %d)", i,
+                        l.y_slots, CSK_CO_Y_SLOTS(max_in), l.out_slots, want_out);
+        if (l.gcn_ksplit > 1 && (l.gcn_partial_frames < 1 || !l.tcn_partial || l.agcn_inter > 0))
+            CREATE_FAIL("co_plan_create: layer %d splits its graph conv but has no partial-sum buffer (or an adaptive graph conv)", i);
+        if (l.tcn_ksplit > 1 && l.partial_emits < 1)
+            CREATE_FAIL("co_plan_create: layer %d splits its K loop but partial_emits is %d", i, l.partial_emits);
+        if (l.agcn_inter > 0 && l.agcn_adj_frames < 1)
+            CREATE_FAIL("co_plan_create: layer %d has an adaptive graph conv but agcn_adj_frames is %d", i, l.agcn_adj_frames);
         max_in = max_emit;
     }
     for (int i = 0; i < n_layers; ++i) {
         const csk_co_layer &l = layers[i];
         if (l.agcn_inter < 0 || (l.agcn_inter > 0 && (!l.agcn_w_pairs || !l.agcn_b_pairs || !l.agcn_a_sum || !l.agcn_adj ||
-                                                      l.ell_w != V || l.ell_cnt[0] != V || l.ell_cnt[1] != V || l.ell_cnt[2] != V))) {
-            snprintf(csk_err_buf(), 256, "co_plan_create: bad adaptive graph conv operands in layer %d", i);
-            return nullptr;
-        }
+                                                      l.ell_w != V || l.ell_cnt[0] != V || l.ell_cnt[1] != V || l.ell_cnt[2] != V)))
+            CREATE_FAIL("co_plan_create: bad adaptive graph conv operands in layer %d", i);
         if (l.c_in <= 0 || l.c_out <= 0 || l.stride < 1 || l.stride > 2 || !l.gcn_w || !l.gcn_bias || !l.ell_src ||
             (!l.ell_val && l.agcn_inter == 0) || !l.tcn_w || !l.tcn_bias || !l.y_ring || !l.out_ring ||
             (l.res_kind == CSK_RES_CONV && !l.tcn_w_res) || (i > 0 && l.c_in != layers[i - 1].c_out) ||
-            (l.tcn_ksplit > 1 && !l.tcn_partial)) {
-            snprintf(csk_err_buf(), 256, "co_plan_create: bad layer %d", i);
-            return nullptr;
-        }
+            (l.tcn_ksplit > 1 && !l.tcn_partial))
+            CREATE_FAIL("co_plan_create: bad layer %d", i);
     }
     csk_co_plan *p = new csk_co_plan();
     p->max_cycle = max_cycle;
@@ -95,6 +83,8 @@ extern "C" csk_co_plan *csk_co_plan_create(int n_layers, const csk_co_layer *lay
     p->pool_ring = pool_ring; p->pooled = pooled;
     return p;
 }
+
+#undef CREATE_FAIL
 
 extern "C" void csk_co_plan_destroy(csk_co_plan *plan) { delete plan; }
 
@@ -129,33 +119,32 @@ static bool fusable_cycle(const csk_co_layer &l, const BlockCounters &c, int r, 
            l.gcn_ksplit <= 1 && l.ell_cnt[0] <= 1 && l.ell_cnt[1] <= 1 && l.ell_cnt[2] <= 4 && ((64 + V - 2) / V + 1) * V <= 128;
 }
 
-// one block: r frames are already in xin[(s .. s+r-1) % HIST] (HIST = depth of the input ring = the upstream layer's
-// out_slots); returns emissions via *slot0 / *n_emit
+// the arguments of a fused 4-frame cycle of layer l at position c, its new frames in xin[(c.s .. c.s + 3) % in_slots]
+static csk_co_block_args co_block_args(const csk_co_layer &l, const BlockCounters &c, const float *xin, int in_slots) {
+    return {xin, in_slots, (int)(c.s % in_slots), l.c_in, l.gcn_w, l.gcn_bias, l.ell_src, l.ell_val,
+            {l.ell_cnt[0], l.ell_cnt[1], l.ell_cnt[2]}, l.ell_w, l.gcn_res_mode, l.y_ring, l.y_slots, (int)(c.s % l.y_slots),
+            l.tcn_w, l.tcn_bias, l.res_kind, (int)((c.s - 4) % in_slots), l.out_ring, l.out_slots, (int)(c.e % l.out_slots), l.c_out};
+}
+
+// Of the steps s0 .. s0 + r - 1, those that emit are the s >= delay with (s - delay) % stride == 0: the first of them and how
+// many (*n = 0: none).  continual.py:emissions
+static int64_t emissions(int64_t s0, int r, int delay, int stride, int *n) {
+    int64_t first = s0 > delay ? s0 : delay;
+    first += (stride - (first - delay) % stride) % stride;
+    *n = first < s0 + r ? (int)((s0 + r - 1 - first) / stride) + 1 : 0;
+    return first;
+}
+
+// one block in two stages: r frames are already in xin[(s .. s+r-1) % HIST] (HIST = depth of the input ring = the upstream
+// layer's out_slots); returns emissions via *slot0 / *n_emit
 static int advance_block(const csk_co_layer &l, BlockCounters &c, const float *xin, int HIST, int r, int n_frames, int V,
-                         int64_t P, int *slot0, int *n_emit, bool fuse, void *stream) {
+                         int64_t P, int *slot0, int *n_emit, void *stream) {
     constexpr int K = 9, DELAY = 4, LAG = 4;      // padding="equal": delay = k-1-p = 4; residual lag (k-1)/2
-    const int YRING = l.y_slots, OUT = l.out_slots;
-    const long s0 = c.s;
-    if (r + K - 1 > YRING || r + LAG > HIST)
-        CSK_FAIL("co_plan_cycle: %d frames do not fit the rings of a layer (y ring %d slots, input ring %d)", r, YRING, HIST);
-    // one fused launch for a whole emitting 4-frame cycle of a 64-row block (continual.py:_fusable)
-    if (fuse && fusable_cycle(l, c, r, V)) {
-        *slot0 = (int)(c.e % OUT);
-        const int rc = csk_co_block_step_f32(xin, HIST, (int)(s0 % HIST), l.c_in, l.gcn_w, l.gcn_bias,
-                                         l.ell_src, l.ell_val, l.ell_cnt, l.ell_w, l.gcn_res_mode, l.y_ring, YRING,
-                                         (int)(s0 % YRING), l.tcn_w, l.tcn_bias, l.res_kind,
-                                         (int)((s0 - LAG) % HIST), l.out_ring, OUT, *slot0, l.c_out, n_frames, V, P,
-                                         stream);
-        if (rc) return rc;
-        c.s += 4; c.e += 4;
-        *n_emit = 4;
-        return 0;
-    }
+    const int YRING = l.y_slots, OUT = l.out_slots;      // (run_blocks has checked that r frames fit YRING and HIST)
+    const int64_t s0 = c.s;
     for (int f = 0; f < r;) {                      // per-frame graph conv, one launch per non-wrapping slot run
-        const long s = s0 + f;
-        int run = r - f;
-        if (run > HIST - (int)(s % HIST)) run = HIST - (int)(s % HIST);
-        if (run > YRING - (int)(s % YRING)) run = YRING - (int)(s % YRING);
+        const int64_t s = s0 + f;
+        const int run = ring_run(r - f, (int)(s % HIST), HIST, (int)(s % YRING), YRING);
         const float *xs = xin + (s % HIST) * (int64_t)l.c_in * P;
         float *ys = l.y_ring + (s % YRING) * (int64_t)l.c_out * P;
         int rc;
@@ -182,13 +171,11 @@ static int advance_block(const csk_co_layer &l, BlockCounters &c, const float *x
         if (rc) return rc;
         f += run;
     }
-    long first = -1;
-    for (long s = s0; s < s0 + r; ++s)
-        if (s >= DELAY && (s - DELAY) % l.stride == 0) { first = s; break; }
+    int ne;
+    const int64_t first = emissions(s0, r, DELAY, l.stride, &ne);
     c.s += r;
     *n_emit = 0;
-    if (first < 0) return 0;
-    const int ne = (int)((s0 + r - 1 - first) / l.stride) + 1;
+    if (ne == 0) return 0;
     if (ne > OUT) CSK_FAIL("co_plan_cycle: %d emissions do not fit an output ring of %d slots", ne, OUT);
     if (l.tcn_ksplit > 1 && ne > l.partial_emits)
         CSK_FAIL("co_plan_cycle: %d emissions exceed the split-K scratch of the layer (%d emissions)", ne, l.partial_emits);
@@ -209,43 +196,42 @@ static int run_blocks(const csk_co_plan *p, std::vector<BlockCounters> &cnt, int
     const float *xin = p->xin0;
     int rr = r, in_slots = p->xin0_slots;
     *n_last = 0;
+    auto fusable = [&](size_t k, int r) { return p->fuse && k < p->layers.size() && fusable_cycle(p->layers[k], cnt[k], r, p->V); };
+    // identity gcn_residual: what the fused stack kernel covers
+    auto stackable = [&](size_t k, int r) { return fusable(k, r) && p->layers[k].gcn_res_mode == CSK_RES_IDENTITY; };
     for (size_t i = 0; i < p->layers.size(); ++i) {
-        // consecutive blocks that each advance a whole emitting cycle: ONE launch for the run (csk_co_stack_step_f32)
-        auto stackable = [&](size_t k, int r) {             // identity gcn_residual: what the fused stack kernel covers
-            return fusable_cycle(p->layers[k], cnt[k], r, p->V) && p->layers[k].gcn_res_mode == CSK_RES_IDENTITY;
-        };
-        if (p->fuse && i + 1 < p->layers.size() && stackable(i, rr) && stackable(i + 1, 4)) {
+        const csk_co_layer &l = p->layers[i];
+        // n consecutive blocks from i on that each advance a whole emitting 4-frame cycle go in ONE call.  A run grows past its
+        // first block only over stackable blocks: layer 1 (conv gcn_residual) and a block without such a neighbour are runs of one.
+        size_t n = fusable(i, rr) ? 1 : 0;
+        if (n && stackable(i, rr))
+            while (n < CSK_CO_STACK_MAX && stackable(i + n, 4)) ++n;
+        // (two refusal texts for rings that are too shallow: a run of several blocks names the layer, below)
+        if (n < 2 && (rr + 8 > l.y_slots || rr + 4 > in_slots))
+            CSK_FAIL("co_plan_cycle: %d frames do not fit the rings of a layer (y ring %d slots, input ring %d)", rr, l.y_slots, in_slots);
+        if (n) {
             csk_co_block_args args[CSK_CO_STACK_MAX];
-            int n = 0;
-            size_t j = i;
-            for (; j < p->layers.size() && n < CSK_CO_STACK_MAX && stackable(j, 4); ++j, ++n) {
-                const csk_co_layer &l = p->layers[j];
-                const long s0 = cnt[j].s;
-                if (4 + 8 > l.y_slots || 4 + 4 > in_slots) CSK_FAIL("co_plan_cycle: 4 frames do not fit the rings of layer %d", (int)j);
-                csk_co_block_args &a = args[n];
-                a.xin = xin; a.xin_slots = in_slots; a.xin_slot0 = (int)(s0 % in_slots); a.c_in = l.c_in; a.gcn_w = l.gcn_w;
-                a.gcn_bias = l.gcn_bias; a.ell_src = l.ell_src; a.ell_val = l.ell_val;
-                a.ell_cnt[0] = l.ell_cnt[0]; a.ell_cnt[1] = l.ell_cnt[1]; a.ell_cnt[2] = l.ell_cnt[2];
-                a.ell_w = l.ell_w; a.gcn_res_mode = l.gcn_res_mode; a.y_ring = l.y_ring; a.y_slots = l.y_slots; a.y_slot0 = (int)(s0 % l.y_slots);
-                a.tcn_w = l.tcn_w; a.tcn_bias = l.tcn_bias; a.res_mode = l.res_kind; a.x_res_slot0 = (int)((s0 - 4) % in_slots);
-                a.out = l.out_ring; a.out_slots = l.out_slots; a.out_slot0 = (int)(cnt[j].e % l.out_slots); a.c_out = l.c_out;
-                xin = l.out_ring;
-                in_slots = l.out_slots;
+            for (size_t k = 0; k < n; ++k) {
+                const csk_co_layer &b = p->layers[i + k];
+                if (4 + 8 > b.y_slots || 4 + 4 > in_slots) CSK_FAIL("co_plan_cycle: 4 frames do not fit the rings of layer %d", (int)(i + k));
+                args[k] = co_block_args(b, cnt[i + k], xin, in_slots);
+                xin = b.out_ring;
+                in_slots = b.out_slots;
             }
-            if (const int rc = csk_co_stack_step_f32(n, args, p->N * p->M, p->V, p->P, stream)) return rc;
-            for (size_t k = i; k < j; ++k) { cnt[k].s += 4; cnt[k].e += 4; }
+            if (const int rc = csk_co_stack_step_f32((int)n, args, p->N * p->M, p->V, p->P, stream)) return rc;
+            for (size_t k = 0; k < n; ++k) { cnt[i + k].s += 4; cnt[i + k].e += 4; }
             *slot0 = args[n - 1].out_slot0;
             rr = 4;
-            i = j - 1;
+            i += n - 1;
             continue;
         }
         int ne = 0;
-        const int rc = advance_block(p->layers[i], cnt[i], xin, in_slots, rr, p->N * p->M, p->V, p->P, slot0, &ne, p->fuse, stream);
+        const int rc = advance_block(l, cnt[i], xin, in_slots, rr, p->N * p->M, p->V, p->P, slot0, &ne, stream);
         if (rc) return rc;
         if (ne == 0) return 0;
         rr = ne;
-        xin = p->layers[i].out_ring;
-        in_slots = p->layers[i].out_slots;
+        xin = l.out_ring;
+        in_slots = l.out_slots;
     }
     *n_last = rr;
     return 0;

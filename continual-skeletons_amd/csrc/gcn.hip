@@ -785,25 +785,14 @@ static int gcn_stage_impl(const float *x, float *y, const float *w, const float 
     if (ell_w < 1 || ell_w > V) CSK_FAIL("gcn_stage: ell_w must be in [1, V]");
     if (res_mode != CSK_RES_IDENTITY && res_mode != CSK_RES_CONV) CSK_FAIL("gcn_stage: res_mode must be identity or conv");
     if (res_mode == CSK_RES_IDENTITY && c_in != c_out) CSK_FAIL("gcn_stage: identity residual needs c_in == c_out");
-    GcnParams p;
-    p.x = x; p.w = w; p.bias = bias; p.y = y; p.ell_src = ell_src; p.ell_val = ell_val;
-    for (int i = 0; i < 3; ++i) {
+    for (int i = 0; i < 3; ++i)
         if (ell_cnt[i] < 0 || ell_cnt[i] > ell_w) CSK_FAIL("gcn_stage: ell_cnt[%d] out of range", i);
-        p.ell_cnt[i] = ell_cnt[i];
-    }
-    p.ell_w = ell_w; p.adj_seg_stride = adj_seg_stride;
-    p.x_ring_slots = p.y_ring_slots = 1 << 30; p.x_ring_slot0 = p.y_ring_slot0 = 0;
-    p.x_seg_stride = x_seg_stride; p.x_chan_stride = x_chan_stride;
-    p.y_seg_stride = y_seg_stride; p.y_chan_stride = y_chan_stride;
-    p.Cin = c_in; p.CinPad = round_up(c_in, CSK_CPAD); p.Cout = c_out; p.Mpad = round_up(c_out, CSK_MT);
-    p.frames = frames; p.V = V; p.R = res_mode == CSK_RES_CONV ? 4 : 3; p.res_mode = res_mode;
+    GcnParams p = gcn_params(x, y, w, bias, ell_src, ell_val, ell_cnt, ell_w, adj_seg_stride, c_in, c_out, frames, V, x_seg_stride,
+                             x_chan_stride, y_seg_stride, y_chan_stride, res_mode, partial);
     // per-segment adjacencies are dense by contract (include/cskel.h): ell_w == V, ell_cnt == {V,V,V}, src[e] == e
     p.dense = adj_seg_stride != 0 && ell_w == V && ell_cnt[0] == V && ell_cnt[1] == V && ell_cnt[2] == V;
     p.adj_per_frame = adj_per_frame != 0;
-    // 32-bit lane byte offsets: 4 * (4 * row_stride + position) must stay below 2^32
-    p.fast_epi = x_chan_stride < (1ll << 27) && y_chan_stride < (1ll << 27);
     if (p.adj_per_frame && !p.dense) CSK_FAIL("gcn_stage: per-frame adjacency must be dense (ell_w == V, ell_cnt == V)");
-    p.vmagic = vmagic_of(V);
     const bool big = (p.Mpad % 128) == 0;
     const int MT = big ? 128 : 64, NT = 16384 / MT;
     const int max_dt = (NT + V - 2) / V;
@@ -819,14 +808,9 @@ static int gcn_stage_impl(const float *x, float *y, const float *w, const float 
     // sparse-graph fast path: shared adjacency with <= 1/1/4 non-zeros per column, activation tile <= 320 positions
     const bool sparse = adj_seg_stride == 0 && ell_cnt[0] <= 1 && ell_cnt[1] <= 1 && ell_cnt[2] <= 4 && p.ldb <= (big ? 192 : 320) &&
                         !csk_diag_flag("CSK_GCN_GENERAL");
-    // split-K (latency mode): every split owns >= 1 real channel; fewer splits than asked for if the channel count does not
-    // allow more; the factor is a function of (c_in, ksplit) only, so a frame's sums do not depend on the launch size
-    p.ksplit = 1; p.cper = p.CinPad; p.part = partial;
-    if (ksplit > 1) {
-        if (!sparse) CSK_FAIL("gcn_stage_splitk: split-K is built for the skeleton-sparse kernel (shared adjacency, <= 1/1/4 non-zeros per column)");
-        p.cper = round_up((p.CinPad + ksplit - 1) / ksplit, 8);
-        p.ksplit = (c_in + p.cper - 1) / p.cper;
-    }
+    // split-K (latency mode)
+    if (ksplit > 1 && !sparse) CSK_FAIL("gcn_stage_splitk: split-K is built for the skeleton-sparse kernel (shared adjacency, <= 1/1/4 non-zeros per column)");
+    p.ksplit = split_ranges(p.CinPad, c_in, ksplit, 8, &p.cper);
     if (sparse && p.ksplit == 1) {     // slot-balanced 16x16x4 tiles where they pack the chip better (step16.hip; same sums)
         const int rc = csk_launch_gcn16(p, n_seg, stream);
         if (rc != -2) return rc;
@@ -920,14 +904,10 @@ extern "C" int csk_conv1x1_f32(const float *x, float *y, const float *w, const f
     if (!x || !y || !w || !bias) CSK_FAIL("conv1x1: null pointer");
     if (n_seg <= 0 || c_in <= 0 || c_out <= 0 || frames <= 0 || V < 2 || V > 64) CSK_FAIL("conv1x1: bad dims");
     if ((int64_t)frames * V >= (1 << 26)) CSK_FAIL("conv1x1: frames*V too large for 32-bit position arithmetic");
-    GcnParams p = {};
-    p.x = x; p.w = w; p.bias = bias; p.y = y; p.ell_src = nullptr; p.ell_val = nullptr;
-    p.ell_cnt[0] = p.ell_cnt[1] = p.ell_cnt[2] = 0; p.ell_w = 1; p.adj_seg_stride = 0;
-    p.x_seg_stride = x_seg_stride; p.x_chan_stride = x_chan_stride; p.y_seg_stride = y_seg_stride; p.y_chan_stride = y_chan_stride;
-    p.Cin = c_in; p.CinPad = round_up(c_in, CSK_CPAD); p.Cout = c_out; p.Mpad = round_up(c_out, CSK_MT);
-    p.frames = frames; p.V = V; p.R = 1; p.res_mode = CSK_RES_NONE;
-    p.fast_epi = x_chan_stride < (1ll << 27) && y_chan_stride < (1ll << 27);
-    p.vmagic = vmagic_of(V);
+    const int32_t no_adjacency[3] = {0, 0, 0};
+    GcnParams p = gcn_params(x, y, w, bias, nullptr, nullptr, no_adjacency, 1, 0, c_in, c_out, frames, V, x_seg_stride, x_chan_stride,
+                             y_seg_stride, y_chan_stride, CSK_RES_NONE, nullptr);
+    p.R = 1;                                               // one operand subset: the conv itself
     const bool big = (p.Mpad % 128) == 0;
     const int MT = big ? 128 : 64, NT = 16384 / MT;
     const int max_dt = (NT + V - 2) / V;

@@ -2,6 +2,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "mfma_core.h"
+
 struct GcnParams {
     const float *x, *w, *bias;
     float *y;
@@ -23,6 +25,26 @@ struct GcnParams {
     // step16.hip: segment s of the launch is slot (ring_slot0 + s) % ring_slots of x / y (plain calls: no wrap, 1 << 30 slots)
     int x_ring_slots, x_ring_slot0, y_ring_slots, y_ring_slot0;
 };
+
+// The fields every launcher (gcn.hip, step16.hip) derives from the operands, in the argument order of csk_gcn_stage_f32: a plain,
+// unsplit call.  The launcher adds its own: tile geometry, dense / adj_per_frame / lds_frames, ring slots, a split.
+inline GcnParams gcn_params(const float *x, float *y, const float *w, const float *bias, const int32_t *ell_src, const float *ell_val,
+                            const int32_t *ell_cnt, int ell_w, int64_t adj_seg_stride, int c_in, int c_out, int frames, int V, int64_t x_seg_stride,
+                            int64_t x_chan_stride, int64_t y_seg_stride, int64_t y_chan_stride, int res_mode, float *part) {
+    GcnParams p = {};
+    p.x = x; p.w = w; p.bias = bias; p.y = y; p.ell_src = ell_src; p.ell_val = ell_val;
+    for (int i = 0; i < 3; ++i) p.ell_cnt[i] = ell_cnt[i];
+    p.ell_w = ell_w; p.adj_seg_stride = adj_seg_stride;
+    p.x_seg_stride = x_seg_stride; p.x_chan_stride = x_chan_stride; p.y_seg_stride = y_seg_stride; p.y_chan_stride = y_chan_stride;
+    p.Cin = c_in; p.CinPad = round_up(c_in, CSK_CPAD); p.Cout = c_out; p.Mpad = round_up(c_out, CSK_MT);
+    p.frames = frames; p.V = V; p.R = res_mode == CSK_RES_CONV ? 4 : 3; p.res_mode = res_mode;
+    p.vmagic = vmagic_of(V);
+    // 32-bit lane byte offsets: 4 * (4 * row_stride + position) must stay below 2^32
+    p.fast_epi = x_chan_stride < (1ll << 27) && y_chan_stride < (1ll << 27);
+    p.x_ring_slots = p.y_ring_slots = 1 << 30; p.x_ring_slot0 = p.y_ring_slot0 = 0;
+    p.ksplit = 1; p.cper = p.CinPad; p.part = part;
+    return p;
+}
 
 // gcn_dense.hip: dense (per-segment or per-frame) adjacency with an even joint count V <= 18; returns -2 when the shape is
 // not one it is built for (the caller then uses the kernels of gcn.hip), otherwise the launch status

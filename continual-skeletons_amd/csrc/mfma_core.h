@@ -22,6 +22,20 @@ char *csk_err_buf();   // thread-local message buffer (defined in runtime.hip)
 
 static inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
 
+// Split-K ranges (ksplit >= 1 asked for) of a K loop over Cpad channel rows, c of them real: *cper = channels per range (whole
+// chunks), returns the ranges.  Every range owns >= 1 real channel: fewer than asked for if the channel count does not allow more.
+static inline int split_ranges(int Cpad, int c, int ksplit, int chunk, int *cper) {
+    *cper = round_up((Cpad + ksplit - 1) / ksplit, chunk);
+    return ksplit > 1 ? (c + *cper - 1) / *cper : 1;
+}
+
+// `left` frames from slots slot_a / slot_b of two rings on: how many the first run holds that wraps in neither ring, so that
+// one launch can take it with a constant slot stride (continual.py:ring_runs)
+static inline int ring_run(int left, int slot_a, int depth_a, int slot_b, int depth_b) {
+    const int a = depth_a - slot_a, b = depth_b - slot_b, room = a < b ? a : b;
+    return left < room ? left : room;
+}
+
 // Raise a kernel's dynamic-LDS cap once (and again only if a larger tile is requested): steady-state launches
 // then consist of hipLaunchKernel alone.  Returns hipSuccess (0) or the error.
 int csk_ensure_lds(const void *kernel, size_t bytes);

@@ -387,18 +387,10 @@ extern "C" int csk_tcn_step_f32(const float *ring, int slots, int head, int head
         if (res_mode == CSK_RES_CONV && !w_res) CSK_FAIL("tcn_step: conv residual without w_res");
     }
     if (((uintptr_t)ring | (uintptr_t)(x_res ? x_res : ring)) & 15) CSK_FAIL("tcn_step: state pointers must be 16-byte aligned");
-    StepParams p;
-    p.ring = ring; p.w = w; p.xres = x_res ? x_res : ring; p.wres = w_res; p.bias = bias; p.out = out;
-    p.C = c; p.Cpad = round_up(c, CSK_CPAD); p.Cout = c_out; p.Mpad = round_up(c_out, CSK_MT);
-    p.K = k; p.slots = slots; p.head = head; p.head_step = head_step; p.res_mode = res_mode;
-    p.Cres = c_res > 0 ? c_res : 1; p.CresPad = round_up(p.Cres, CSK_CPAD); p.relu = relu; p.P = P;
-    // 32-bit lane byte offsets: 4 * (4 * row_stride + position) must stay below 2^32
-    p.fast_epi = P < (1ll << 27);
-    p.xres_slots = x_res ? x_res_slots : 1; p.xres_slot0 = x_res ? x_res_slot0 : 0; p.xres_step = x_res_step;
-    p.out_slots = out_slots; p.out_slot0 = out_slot0;
-    // split-K: every split owns >= 1 real channel; fewer splits than asked for if the channel count does not allow more
-    p.cper = round_up((p.Cpad + ksplit - 1) / ksplit, KC);
-    p.ksplit = ksplit > 1 ? (c + p.cper - 1) / p.cper : 1;
+    // without x_res: the post-GCN ring as a one-slot stand-in
+    StepParams p = step_params(ring, slots, head, head_step, w, x_res ? x_res : ring, x_res ? x_res_slots : 1, x_res ? x_res_slot0 : 0,
+                               x_res_step, w_res, bias, out, out_slots, out_slot0, c, c_out, P, k, res_mode, c_res, relu);
+    p.ksplit = split_ranges(p.Cpad, c, ksplit, KC, &p.cper);
     p.part = partial;
     if (p.ksplit > 1 && ((uintptr_t)partial & 15)) CSK_FAIL("tcn_step: partial-sum buffer must be 16-byte aligned");
     // every k = 9, unsplit launch whose rings fit 32-bit byte offsets runs on the slot-balanced 16x16x4 tiles (step16.hip),

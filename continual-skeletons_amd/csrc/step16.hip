@@ -431,13 +431,8 @@ int csk_launch_tcn_step16(StepParams p, int n_emit, void *stream) {
     const int E = p.head_step == 2 ? (n_emit % 2 == 0 ? 2 : 1) : (n_emit % 4 == 0 ? 4 : n_emit % 2 == 0 ? 2 : 1);
     const int HS = E > 1 ? p.head_step : 1;
     const int64_t mt = p.Mpad / 64;
-    int best_nb = 0;
-    double best = 0;
-    for (int nb : {25, 18}) {
-        const int np = 16 * nb / E;
-        const double c = cost_model(((p.P + np - 1) / np) * mt * (n_emit / E), 16.0 * nb);
-        if (!best_nb || c < best) { best = c; best_nb = nb; }
-    }
+    const int best_nb = pick_nb([&](int nb) { const int np = 16 * nb / E; return ((p.P + np - 1) / np) * mt * (n_emit / E); },
+                                [](int) { return true; });
     hipStream_t s = (hipStream_t)stream;
 #define CSK_L16(NB_) (E == 4 ? launch16<NB_, 4, 1>(p, n_emit, s) : E == 2 ? (HS == 2 ? launch16<NB_, 2, 2>(p, n_emit, s) : launch16<NB_, 2, 1>(p, n_emit, s)) : launch16<NB_, 1, 1>(p, n_emit, s))
     return best_nb == 25 ? CSK_L16(25) : CSK_L16(18);
@@ -456,20 +451,14 @@ int csk_launch_gcn16(GcnParams p, int n_seg, void *stream) {
     if ((int64_t)F * p.x_seg_stride * 4 >= (1ll << 32) || (int64_t)F * p.y_seg_stride * 4 >= (1ll << 32)) return -2;
     const int Q = p.frames * p.V;
     const int64_t mt = p.Mpad / 64;
-    int best_nb = 0;
-    double best = 0;
-    for (int nb : {25, 18}) {
-        const int npg = 16 * nb / F;
-        if (npg % p.V) continue;                              // tiles hold whole skeletons
-        const double c = cost_model((int64_t)((Q + npg - 1) / npg) * mt * (n_seg / F), 16.0 * nb);
-        if (!best_nb || c < best) { best = c; best_nb = nb; }
-    }
+    const auto tiles = [&](int nb) { const int npg = 16 * nb / F; return (int64_t)((Q + npg - 1) / npg) * mt * (n_seg / F); };
+    const int best_nb = pick_nb(tiles, [&](int nb) { return (16 * nb / F) % p.V == 0; });      // tiles hold whole skeletons
     if (!best_nb) return -2;
     if (mode != 2) {
         const bool big = (p.Mpad % 128) == 0;
         const int nt32 = big ? 128 : 256;
         const double c32 = cost_model((int64_t)((Q + nt32 - 1) / nt32) * (big ? p.Mpad / 128 : p.Mpad / 64) * n_seg, 256.0);
-        if (best >= 0.97 * c32) return -2;                   // not clearly better: keep the 32x32x2 tiles
+        if (cost_model(tiles(best_nb), 16.0 * best_nb) >= 0.97 * c32) return -2;   // not clearly better: keep the 32x32x2 tiles
     }
     hipStream_t s = (hipStream_t)stream;
 #define CSK_G16(NB_) (F == 4 ? launch_gcn16<NB_, 4>(p, n_seg, s) : F == 2 ? launch_gcn16<NB_, 2>(p, n_seg, s) : launch_gcn16<NB_, 1>(p, n_seg, s))
@@ -482,14 +471,8 @@ int csk_launch_gcn16(GcnParams p, int n_seg, void *stream) {
 int csk_launch_co_stack16(int n_blocks, const csk_co_block_args *b, int n_skel, int V, int64_t P, void *stream) {
     if (n_blocks < 1 || n_blocks > CSK_CO_STACK_MAX || P < 8 || (P & 3)) return -2;
     const int64_t Q = (int64_t)n_skel * V;
-    int best_nb = 0;
-    double best = 0;
-    for (int nb : {25, 18}) {
-        const int np = 16 * nb / 4;
-        if (np % V) continue;                                 // tiles hold whole skeletons
-        const double c = cost_model((P + np - 1) / np, 16.0 * nb);
-        if (!best_nb || c < best) { best = c; best_nb = nb; }
-    }
+    const int best_nb = pick_nb([&](int nb) { return (P + 4 * nb - 1) / (4 * nb); },
+                                [&](int nb) { return (4 * nb) % V == 0; });                     // tiles hold whole skeletons
     if (!best_nb) return -2;
     const int NP = 16 * best_nb / 4;
     CoStackParams sp;
@@ -504,24 +487,16 @@ int csk_launch_co_stack16(int n_blocks, const csk_co_block_args *b, int n_skel, 
         if ((int64_t)a.xin_slots * a.c_in * P * 4 >= (1ll << 32) || (int64_t)a.y_slots * a.c_out * P * 4 >= (1ll << 32) ||
             (int64_t)a.out_slots * a.c_out * P * 4 >= (1ll << 32))
             return -2;
+        // what co_block_cycle hands the two stage entries, but ring slots for slot runs and (no residual) the input ring as xres
         GcnParams &g = sp.b[i].g;
-        g = GcnParams{};
-        g.x = a.xin; g.w = a.gcn_w; g.bias = a.gcn_bias; g.y = a.y_ring; g.ell_src = a.ell_src; g.ell_val = a.ell_val;
-        for (int k = 0; k < 3; ++k) g.ell_cnt[k] = a.ell_cnt[k];
-        g.ell_w = a.ell_w; g.adj_seg_stride = 0;
-        g.x_seg_stride = (int64_t)a.c_in * P; g.x_chan_stride = P; g.y_seg_stride = (int64_t)a.c_out * P; g.y_chan_stride = P;
-        g.Cin = a.c_in; g.CinPad = round_up(a.c_in, CSK_CPAD); g.Cout = a.c_out; g.Mpad = round_up(a.c_out, CSK_MT);
-        g.frames = n_skel; g.V = V; g.R = a.gcn_res_mode == CSK_RES_CONV ? 4 : 3; g.res_mode = a.gcn_res_mode;
-        g.vmagic = vmagic_of(V); g.mtiles = 1; g.qtiles = (unsigned)((Q + NP - 1) / NP); g.ksplit = 1; g.cper = g.CinPad; g.part = nullptr;
+        g = gcn_params(a.xin, a.y_ring, a.gcn_w, a.gcn_bias, a.ell_src, a.ell_val, a.ell_cnt, a.ell_w, 0, a.c_in, a.c_out, n_skel, V,
+                       (int64_t)a.c_in * P, P, (int64_t)a.c_out * P, P, a.gcn_res_mode, nullptr);
+        g.mtiles = 1; g.qtiles = (unsigned)((Q + NP - 1) / NP);
         g.x_ring_slots = a.xin_slots; g.x_ring_slot0 = a.xin_slot0; g.y_ring_slots = a.y_slots; g.y_ring_slot0 = a.y_slot0;
         StepParams &t = sp.b[i].t;
-        t = StepParams{};
-        t.ring = a.y_ring; t.w = a.tcn_w; t.xres = a.xin; t.wres = nullptr; t.bias = a.tcn_bias; t.out = a.out;
-        t.C = a.c_out; t.Cpad = round_up(a.c_out, CSK_CPAD); t.Cout = a.c_out; t.Mpad = round_up(a.c_out, CSK_MT);
-        t.K = 9; t.slots = a.y_slots; t.head = a.y_slot0; t.head_step = 1; t.res_mode = a.res_mode;
-        t.Cres = a.res_mode ? a.c_in : 1; t.CresPad = round_up(t.Cres, CSK_CPAD); t.relu = 1; t.P = P; t.fast_epi = 1;
-        t.xres_slots = a.xin_slots; t.xres_slot0 = a.x_res_slot0; t.xres_step = 1; t.out_slots = a.out_slots; t.out_slot0 = a.out_slot0;
-        t.ksplit = 1; t.cper = t.Cpad; t.part = nullptr; t.gx = (unsigned)((P + NP - 1) / NP); t.gy = 1; t.gz = 1;
+        t = step_params(a.y_ring, a.y_slots, a.y_slot0, 1, a.tcn_w, a.xin, a.xin_slots, a.x_res_slot0, 1, nullptr, a.tcn_bias, a.out,
+                        a.out_slots, a.out_slot0, a.c_out, a.c_out, P, 9, a.res_mode, a.res_mode ? a.c_in : 0, 1);
+        t.gx = (unsigned)((P + NP - 1) / NP); t.gy = 1; t.gz = 1;
     }
     void (*kern)(CoStackParams) = best_nb == 25 ? co_stack16_kernel<25> : co_stack16_kernel<18>;
     const int NT = 16 * best_nb;
@@ -569,9 +544,7 @@ static int co_block_cycle(const csk_co_block_args &a, int n_skel, int V, int64_t
     if (rc1 != -2) return rc1;
     for (int f = 0; f < 4;) {
         const int xs = (a.xin_slot0 + f) % a.xin_slots, ys = (a.y_slot0 + f) % a.y_slots;
-        int run = 4 - f;
-        if (run > a.xin_slots - xs) run = a.xin_slots - xs;
-        if (run > a.y_slots - ys) run = a.y_slots - ys;
+        const int run = ring_run(4 - f, xs, a.xin_slots, ys, a.y_slots);
         if (const int rc = csk_gcn_stage_f32(a.xin + (int64_t)xs * a.c_in * P, a.y_ring + (int64_t)ys * a.c_out * P, a.gcn_w, a.gcn_bias,
                                              a.ell_src, a.ell_val, a.ell_cnt, a.ell_w, 0, 0, run, a.c_in, a.c_out, n_skel, V,
                                              (int64_t)a.c_in * P, P, (int64_t)a.c_out * P, P, a.gcn_res_mode, stream))
@@ -590,14 +563,10 @@ extern "C" int csk_co_block_step_f32(const float *xin, int xin_slots, int xin_sl
                                      float *out, int out_slots, int out_slot0, int c_out, int n_skel, int V, int64_t P,
                                      void *stream) {
     if (!ell_cnt) CSK_FAIL("co_block_step: null pointer");
-    csk_co_block_args a;
-    a.xin = xin; a.xin_slots = xin_slots; a.xin_slot0 = xin_slot0; a.c_in = c_in; a.gcn_w = gcn_w; a.gcn_bias = gcn_bias;
-    a.ell_src = ell_src; a.ell_val = ell_val; a.ell_cnt[0] = ell_cnt[0]; a.ell_cnt[1] = ell_cnt[1]; a.ell_cnt[2] = ell_cnt[2];
-    a.ell_w = ell_w; a.gcn_res_mode = gcn_res_mode; a.y_ring = y_ring; a.y_slots = y_slots; a.y_slot0 = y_slot0; a.tcn_w = tcn_w;
-    a.tcn_bias = tcn_bias; a.res_mode = res_mode; a.x_res_slot0 = x_res_slot0; a.out = out; a.out_slots = out_slots;
-    a.out_slot0 = out_slot0; a.c_out = c_out;
-    if (const int rc = check_co_block(a, n_skel, V, P)) return rc;
-    return co_block_cycle(a, n_skel, V, P, stream);
+    const csk_co_block_args a = {xin, xin_slots, xin_slot0, c_in, gcn_w, gcn_bias, ell_src, ell_val, {ell_cnt[0], ell_cnt[1], ell_cnt[2]},
+                                 ell_w, gcn_res_mode, y_ring, y_slots, y_slot0, tcn_w, tcn_bias, res_mode, x_res_slot0,
+                                 out, out_slots, out_slot0, c_out};
+    return csk_co_stack_step_f32(1, &a, n_skel, V, P, stream);      // one block: its checks, then co_block_cycle
 }
 
 extern "C" int csk_co_stack_step_f32(int n_blocks, const csk_co_block_args *b, int n_skel, int V, int64_t P, void *stream) {

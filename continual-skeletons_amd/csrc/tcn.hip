@@ -363,9 +363,7 @@ static int tcn_stage_impl(const float *y, const float *w, const float *x_res, co
     p.Tin = t_in; p.Tout = t_out; p.V = V; p.K = k; p.stride = stride; p.pad = pad;
     p.res_mode = res_mode; p.Cres = c_res > 0 ? c_res : 1; p.CresPad = round_up(p.Cres, CSK_CPAD);
     p.Tres = t_res > 0 ? t_res : 1; p.res_off = res_off; p.relu = relu; p.vmagic = vmagic_of(V);
-    // split-K: every range owns >= 1 real channel; fewer ranges than asked for if the channel count does not allow more
-    p.cper = round_up((p.Cpad + ksplit - 1) / ksplit, KC);
-    p.ksplit = ksplit > 1 ? (c + p.cper - 1) / p.cper : 1;
+    p.ksplit = split_ranges(p.Cpad, c, ksplit, KC, &p.cper);
     p.part = partial;
     // 32-bit lane byte offsets: 4 * (4 * row_stride + position) must stay below 2^32
     p.fast_epi = (int64_t)p.Tres * V < (1ll << 27) && (int64_t)t_out * V < (1ll << 27);
@@ -376,7 +374,7 @@ static int tcn_stage_impl(const float *y, const float *w, const float *x_res, co
     // (the 64-row kernel stages 14 sweeps: at V = 64, stride 2 it keeps 128 of its 256 columns where the 128-row kernel
     // keeps 1 of 128) and the better MFMA-column utilisation wins; a shape that loses more than half the columns either
     // way says so once on stderr.
-    // the 16x16x4 tile family (tcn16.hip) for the shapes it is built for; bitwise the same sums (-2: not taken)
+    // the 16x16x4 tile family (tcn16.hip) for the shapes it is built for; stride 1 bitwise the same sums, stride 2 in its own summation order (-2: not taken)
     if (p.ksplit == 1) {
         const int rc = csk_launch_tcn_stage16(p, n_seg, stream);
         if (rc != -2) return rc;

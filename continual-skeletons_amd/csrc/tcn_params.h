@@ -16,5 +16,6 @@ struct TcnParams {
 };
 
 // tcn16.hip: the 16x16x4 tile family for the 9-tap temporal conv at V = 25 / 18 and stride 1 / 2; -2 when the shape is not one
-// it is built for (the caller launches the 32x32x2 kernels).  Bitwise the same sums (same (chunk, tap, channel) order).
+// it is built for (the caller launches the 32x32x2 kernels).  Stride 1: bitwise the sums of tcn_stage_kernel (same (8-channel
+// chunk, tap, channel) order).  Stride 2 walks 4-channel chunks: another fp32 summation order, taken by the shape alone.
 int csk_launch_tcn_stage16(TcnParams p, int n_seg, void *stream);

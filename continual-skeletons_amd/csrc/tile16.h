@@ -12,6 +12,19 @@ namespace {
 // times the columns a 64-row tile carries (padding included).
 constexpr int64_t CUS = 256;
 inline double cost_model(int64_t tiles64, double tile_cols) { return (double)((tiles64 + CUS - 1) / CUS) * tile_cols; }
+// The tile width in 16-position column blocks (25: NTU, 18: Kinetics) that packs the chip better, among the widths ok(nb)
+// admits: a launch is tiles(nb) workgroups of 16 nb columns.  0: no width admitted.
+template <class Tiles, class Ok>
+inline int pick_nb(Tiles tiles, Ok ok) {
+    int best_nb = 0;
+    double best = 0;
+    for (int nb : {25, 18}) {
+        if (!ok(nb)) continue;
+        const double c = cost_model(tiles(nb), 16.0 * nb);
+        if (!best_nb || c < best) { best = c; best_nb = nb; }
+    }
+    return best_nb;
+}
 
 constexpr int imax(int a, int b) { return a > b ? a : b; }
 constexpr int row16(int n) { return ((n - 16 + 31) / 32) * 32 + 16; }   // smallest stride >= n that is 16 (mod 32)
