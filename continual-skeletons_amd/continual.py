@@ -32,6 +32,7 @@ from . import blocks, fold, native
 from .blocks import GraphConvolution, SpatioTemporalBlock, TemporalConvolution, _Folded, init_weights, unity, zero
 from .co_plan import NativePlan
 from .co_reset import StreamReset
+from .modality import ContinualModality
 from .models import layer_table, per_layer
 
 MAX_CYCLE = native.CO_MAX_CYCLE
@@ -554,7 +555,7 @@ def co_geometry(c_in=3):
     return r, p, s
 
 
-class CoStGcn(NativePlan, StreamReset, _Folded):
+class CoStGcn(NativePlan, StreamReset, ContinualModality, _Folded):
     """CoST-GCN: models/cost_gcn/cost_gcn.py:21-41 + CoModelBase (models/base.py:68-227) without the Ride shell.
 
     ``forward_step(x_t: (N, C, V, M))`` -> logits (N, classes) on the steps where the whole stack (10 blocks,
@@ -562,7 +563,8 @@ class CoStGcn(NativePlan, StreamReset, _Folded):
     -> (N, classes, n_predictions).  ``forward(x)`` = clip mode of CoModelBase.forward (base.py:166-181).
     state_dict keys equal the reference's (``layers.layerK.0.1.gcn...``); a regular StGcn state_dict loads too
     (what ``map_state_dict`` does in the reference, base.py:200-224).  This class binds the state slab and steps on it; the
-    native plan (co_plan.py: NativePlan) and the per-stream reset (co_reset.py: StreamReset) are base classes.
+    native plan (co_plan.py: NativePlan), the per-stream reset (co_reset.py: StreamReset) and the input modality
+    (modality.py: ContinualModality -- bone / motion frames derived from the joint frames in front of every cycle) are base classes.
     """
 
     # False: drive every launch from Python (same kernels, same results).  Read on every cycle: both engines step on the one
@@ -654,6 +656,7 @@ class CoStGcn(NativePlan, StreamReset, _Folded):
         self._pooled = torch.empty((n, 256), device=device, dtype=torch.float32)
         self._flushed = False
         self._forget_resets()
+        self._bind_modality(n, device)
         self._build_plan(device)
 
     _frames = _counter(0, "input frames received")
@@ -689,14 +692,17 @@ class CoStGcn(NativePlan, StreamReset, _Folded):
         self._n = None
 
     def state_bytes(self):
-        """Persistent continual state (input ring, per-block rings, pooling window)."""
-        return sum(blk._state.nbytes() for blk in self._blocks) + 4 * (self._xin0.numel() + self._pool_ring.numel())
+        """Persistent continual state (input ring, per-block rings, pooling window; previous frame and flags of a motion modality)."""
+        return (sum(blk._state.nbytes() for blk in self._blocks) + 4 * (self._xin0.numel() + self._pool_ring.numel())
+                + 4 * sum(t.numel() for t in self._modality_tensors()))
 
     def scratch_bytes(self):
         """Transient scratch, not state: the split-K partial sums (shared by the blocks that split their K loop) and, for
-        adaptive graph convs, the per-skeleton-frame adjacencies of a launch (shared by all blocks)."""
-        adj = self.__dict__.get("_agcn_adj")
-        return 4 * ((self._scratch.numel() if self._scratch is not None else 0) + (adj.numel() if adj is not None else 0))
+        adaptive graph convs, the per-skeleton-frame adjacencies of a launch (shared by all blocks); with a bone / motion input
+        modality, the derived frames of a cycle."""
+        adj, mod = self.__dict__.get("_agcn_adj"), self._mod_scratch
+        return 4 * ((self._scratch.numel() if self._scratch is not None else 0) + (adj.numel() if adj is not None else 0)
+                    + (mod.numel() if mod is not None else 0))
 
     def clean_state(self):
         if self._n is not None:
@@ -704,6 +710,7 @@ class CoStGcn(NativePlan, StreamReset, _Folded):
             for blk in self._blocks:
                 blk.clean_state()
             self._pool_ring.zero_()
+            self._clean_modality()
             self._set_counters([0] * 22)
             self._flushed = False
             self._forget_resets()
@@ -715,7 +722,8 @@ class CoStGcn(NativePlan, StreamReset, _Folded):
         (None, 0) if none) and the list of predictions.  While reset streams warm up (``reset_streams``) the cycle must not
         cross a multiple of the total stride, and what the not-yet-live blocks wrote for them is zeroed after its launches;
         ``peek``: the caller puts the counters back (one step, update_state=False) -- the next real step rewrites and scrubs
-        the same slots, so a peek does neither."""
+        the same slots, so a peek does neither.  The engines step on ``_derive_frames(frames)``: the frames themselves for
+        the joint modality, else the bone / motion frames of the pre-pass (a peek leaves its previous-frame state alone)."""
         self._require_eval()
         frames = list(frames)
         if not 1 <= len(frames) <= self.max_cycle:
@@ -738,10 +746,10 @@ class CoStGcn(NativePlan, StreamReset, _Folded):
                                "and advanced the blocks past the input frame count; call clean_state() before stepping on")
         engine = self._plan_cycle if self.use_native_plan and self.__dict__.get("_plan") else self._python_cycle
         if not self._cohorts or peek:              # nothing warms: the cycle is the one that runs without any reset
-            return engine(frames)
+            return engine(self._derive_frames(frames, update=not peek))
         self._check_cycle_while_warming(len(frames))
         before = self._counters()
-        res = engine(frames)
+        res = engine(self._derive_frames(frames))
         self._scrub_cycle(before)
         return res
 
@@ -760,7 +768,8 @@ class CoStGcn(NativePlan, StreamReset, _Folded):
         self._ctr[:], self._flushed, self._reset_at, self._cohorts = position
 
     def _state_tensors(self):
-        return [self._xin0, self._pool_ring, self._pooled] + [t for blk in self._blocks for t in (blk._state.y, blk._state.out)]
+        return ([self._xin0, self._pool_ring, self._pooled] + [t for blk in self._blocks for t in (blk._state.y, blk._state.out)]
+                + self._modality_tensors())
 
     def _ensure_bound(self, x_t):
         native.require_device_f32(x_t, "CoStGcn frame")
@@ -906,6 +915,7 @@ class CoStGcn(NativePlan, StreamReset, _Folded):
 
     def _clip_features(self, x):
         native.require_device_f32(x, "CoStGcn input")
+        x = self._derive_clip(x)           # bone / motion clip (forward difference, as the reference's files); joint: x itself
         n, c, t, v, m = x.shape
         ops = self._packed_ops(x.device)
         h = torch.empty((n * m, c, t, v), device=x.device, dtype=torch.float32)

@@ -105,3 +105,60 @@ def multi_stream_eval(labels: str, pred1: str, pred2: str = None, pred3: str = N
     targets = load_labels(labels)
     accs = topk_accuracies(preds, targets, (1, 3, 5), method)
     return {f"top{k}acc": v for k, v in zip((1, 3, 5), accs)}
+
+
+class OnlineEnsemble:
+    """The multi-stream ensemble of ``multi_stream_eval`` run online: 2-4 continual models (``CoStGcn`` and siblings), each
+    with its own input modality (``set_input_modality``: joint + bone (+ motion) are the published ensembles), stepped on
+    the same joint frames; their logits are fused by ``csk_fuse_rank_f32`` exactly as ``aggregate_preds`` fuses stored
+    predictions.  The members must emit on the same steps, so they must agree in ``delay``, ``pool_size`` /
+    ``pool_padding``, class count and (once bound) stream count.  A thin wrapper: no kernel and no state of its own."""
+
+    def __init__(self, nets, method: str = "add"):
+        nets = list(nets)
+        if method not in ("add", "maximum"):
+            raise ValueError("method must be 'add' or 'maximum'")
+        if not 2 <= len(nets) <= 4:
+            raise ValueError(f"an online ensemble fuses 2..4 models, got {len(nets)}")
+        for what in ("delay", "pool_size", "pool_padding", "num_classes"):
+            values = [getattr(net, what) for net in nets]
+            if len(set(values)) != 1:
+                raise ValueError(f"the members of an online ensemble must agree in {what} (they emit in lock step), got {values}")
+        bound = {net._n for net in nets if net._n is not None}
+        if len(bound) > 1:
+            raise ValueError(f"the members of an online ensemble must hold the same number of streams, got slabs of {sorted(bound)}")
+        self.nets, self.method = nets, method
+
+    def _fuse(self, outs):
+        """One prediction per member (or None from every member) -> the fused prediction (or None)."""
+        if all(o is None for o in outs):
+            return None
+        if any(o is None for o in outs):
+            raise RuntimeError("the members of the ensemble are out of step: some returned logits and some did not "
+                               "(step them through the ensemble only, from a clean state)")
+        return aggregate_preds(list(outs), self.method)
+
+    def forward_step(self, x_t, update_state=True):
+        """(N, C, V, M) joint frame -> fused logits (N, classes) on predicting steps, else None."""
+        return self._fuse([net.forward_step(x_t, update_state) for net in self.nets])
+
+    def forward_cycle(self, frames):
+        """Up to 8 joint frames -> the list of fused predictions of the cycle, or None if it emitted none."""
+        outs = [net.forward_cycle(frames) for net in self.nets]
+        if len({len(o) for o in outs}) != 1:
+            raise RuntimeError("the members of the ensemble are out of step: they emitted different numbers of predictions")
+        return [self._fuse(per_step) for per_step in zip(*outs)] or None
+
+    def reset_streams(self, indices):
+        for net in self.nets:           # every member checks before any launches: they step in lock step, so they agree
+            net._check_reset(indices)
+        for net in self.nets:
+            net.reset_streams(indices)
+
+    def streams_ready(self):
+        """(N,) bool CPU tensor: the members agree (same delay and pooling), so this is the first one's."""
+        return self.nets[0].streams_ready()
+
+    def clean_state(self):
+        for net in self.nets:
+            net.clean_state()

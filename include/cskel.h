@@ -397,6 +397,43 @@ int csk_input_norm_frames_f32(const float *const *frames, float *const *dst, int
                               int N, int C, int V, int M, int64_t P, void *stream);
 
 /*
+ * Bone / motion input modalities derived from the joint tensor (the reference derives them offline over whole datasets:
+ * datasets/data_preparation/bone_data_prep.py:158-163, motion_data_prep.py:28-30).  x (N, C, T, V, M) as the models take
+ * it; p(v) = parents[v], the 0-based parent joint, p(root) = root.  All C channels alike.  Every subtraction below is one
+ * fp32 rounding, in the order written, so the result equals the reference's numpy arithmetic bit for bit:
+ *   CSK_MODALITY_BONE          b[t, v] = x[t, v] - x[t, p(v)]                      (both read from the original x)
+ *   CSK_MODALITY_JOINT_MOTION  m[t] = x[t+1] - x[t] for t < T-1,  m[T-1] = 0
+ *   CSK_MODALITY_BONE_MOTION   (x[t+1, v] - x[t+1, p(v)]) - (x[t, v] - x[t, p(v)]) for t < T-1,  0 at T-1
+ * (CSK_MODALITY_JOINT names the input itself: nothing to derive, the entries refuse it.)
+ * parents is a HOST array of V ints (may be NULL for CSK_MODALITY_JOINT_MOTION): the entry refuses an index outside
+ * [0, V) before it launches anything -- which it could not do without a synchronisation if the table lived on the
+ * device -- and hands the table to the kernel by value.  out: same shape as x, another buffer.  One pass, 16-byte
+ * accesses when x and out are 16-byte aligned.  V <= 64, V * M <= 512.
+ * Returns -2 (csk_last_error set, nothing launched) for an unknown mode or a parent index outside [0, V).
+ */
+#define CSK_MODALITY_JOINT 0
+#define CSK_MODALITY_BONE 1
+#define CSK_MODALITY_JOINT_MOTION 2
+#define CSK_MODALITY_BONE_MOTION 3
+int csk_derive_modality_f32(const float *x, float *out, int mode, const int32_t *parents, int N, int C, int T, int V, int M,
+                            void *stream);
+
+/*
+ * The same for the r = 1..8 frames of a launch cycle of the continual path in one launch, in the causal (backward) form
+ *   m'[s] = x[s] - x[s-1],  0 on a stream's first frame        (m'[s] = m[s-1] of the clip form)
+ * frames[i] (N, C, V, M) -> dst[i], same shape; frames / dst are HOST arrays of device pointers, as for
+ * csk_input_norm_frames_f32; every dst[i] is a buffer of its own.  Frame i >= 1 is differenced against frame i-1 of the
+ * cycle, frame 0 against prev (N, C, V, M), the raw (joint) frame the last updating call ended with; a stream n whose
+ * has_prev[n] is 0 gets 0 for frame 0 (int32 per stream, on the device).  update != 0: the launch then stores frames[r-1]
+ * into prev and sets has_prev[n] = 1 for all n -- after every read of them, by the workgroup that read them; update == 0
+ * leaves both bitwise untouched (forward_step(update_state=False)).  CSK_MODALITY_BONE has no state: prev / has_prev are
+ * not used (may be NULL).  parents, modes and limits as above.  No allocation, no synchronisation, graph-capture safe.
+ * Returns -2 (csk_last_error set, nothing launched) for an unknown mode, a parent index outside [0, V), or r outside 1..8.
+ */
+int csk_derive_modality_frames_f32(const float *const *frames, float *const *dst, int r, int mode, const int32_t *parents,
+                                   float *prev, int32_t *has_prev, int update, int N, int C, int V, int M, void *stream);
+
+/*
  * Multi-stream logit fusion + top-k support, scripts/multi_stream_eval.py:33-60: fused = left fold of add
  * (use_max = 0) or maximum (1) over n_streams <= 4 prediction arrays (host array of device pointers); element
  * (n, c) of every array at n*sample_stride + c*class_stride (a (N, classes, steps) array with the reference's
