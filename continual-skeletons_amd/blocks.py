@@ -341,11 +341,12 @@ class TemporalConvolution(_Folded):
 
 
 def tcn_stage(y, w, bias, c_out, k, stride, pad, relu=True, res_mode=0, x_res=None, w_res=None, res_off=0, out=None,
-              split=False, ksplit=1, scratch=None, w_wino=None):
+              split=False, ksplit=1, scratch=None, w_wino=None, w_wino_ext=None):
     """csk_tcn_stage_f32, or with split=True csk_tcn_stage_bf16x3 (w / w_res are then the split operand images), or with
     ksplit > 1 csk_tcn_stage_splitk_f32 (clip latency mode: K loop cut into channel ranges, partial sums in split order), or
     with the Winograd image w_wino (fold.pack_conv_weight_wino) csk_tcn_stage_wino_f32 (the Winograd kernel where the layer's
-    shape allows it, csk_tcn_stage_f32 otherwise)."""
+    shape allows it, csk_tcn_stage_f32 otherwise), or with the image w_wino_ext csk_tcn_stage_wino_ext_f32 (stride 2:
+    fold.pack_conv_weight_wino_s2, the polyphase Winograd kernel; stride 1 without residual: fold.pack_conv_weight_wino)."""
     n, c, t_in, v = y.shape
     if t_in + 2 * pad < k:
         raise RuntimeError(f"temporal extent {t_in} (+2*{pad}) shorter than kernel {k}")
@@ -364,6 +365,17 @@ def tcn_stage(y, w, bias, c_out, k, stride, pad, relu=True, res_mode=0, x_res=No
             n, c, c_out, t_in, v, k, stride, pad, res_mode, c_res, t_res, res_off, int(relu), ksplit, native.ptr(part),
             native.stream_of(y))
         native.check(rc, "csk_tcn_stage_splitk_f32")
+        return out
+    if w_wino_ext is not None and not split:
+        rows = 13 if stride == 2 else 12                       # the entry is not told the image's size
+        if w_wino_ext.dim() != 3 or w_wino_ext.shape[0] != rows or tuple(w_wino_ext.shape[1:]) != tuple(w.shape[1:]):
+            raise RuntimeError(f"tcn_stage: w_wino_ext must be the [{rows}][c_pad][c_out_pad] image of a stride-{stride} conv, "
+                               f"got {tuple(w_wino_ext.shape)}")
+        rc = native.lib().csk_tcn_stage_wino_ext_f32(
+            native.ptr(y), native.ptr(w), native.ptr(x_res), native.ptr(w_res), native.ptr(bias), native.ptr(out),
+            n, c, c_out, t_in, v, k, stride, pad, res_mode, c_res, t_res, res_off, int(relu), native.ptr(w_wino_ext),
+            native.stream_of(y))
+        native.check(rc, "csk_tcn_stage_wino_ext_f32")
         return out
     if w_wino is not None and not split:
         rc = native.lib().csk_tcn_stage_wino_f32(
@@ -419,7 +431,7 @@ class SpatioTemporalBlock(_Folded):
     def _fold(self):
         sd = self.state_dict()
         return fold.fold_block_tail(sd, "", has_conv_residual=isinstance(self.residual, TemporalConvolution),
-                                    split=self.precision == "bf16x3", stride=self.stride)
+                                    split=self.precision == "bf16x3", stride=self.stride, no_residual=self.residual is zero)
 
     def forward(self, x, out=None):
         """``out`` (optional, native tail only): preallocated (N, C_out, T_out, V) tensor to write into."""
@@ -444,10 +456,14 @@ class SpatioTemporalBlock(_Folded):
         if self.precision == "bf16x3":
             return tcn_stage(y, ops["w_split"], ops["bias"], ops["c_out"], ops["k"], self.stride, self.tcn.padding, relu=True,
                              res_mode=mode, x_res=xr, w_res=ops["w_res_split"], res_off=shrink, out=out, split=True)
+        # the stride-1 block without residual keeps the direct kernels: csk_block_few_channels_f32 is bit for bit this block's
+        # two launches (tests/test_gpu_clip_parity.py), and it computes the direct sums; tcn_stage(w_wino_ext=) offers the
+        # Winograd form of that shape to callers that do not need those bits
         ks = max(1, min(self.clip_split_k, -(-ops["c"] // 8))) if (self.clip_split_k > 1 and ops["k"] == 9 and y.shape[0] <= self.clip_split_max_seq) else 1
         return tcn_stage(y, ops["w"], ops["bias"], ops["c_out"], ops["k"], self.stride, self.tcn.padding, relu=True,
                          res_mode=mode, x_res=xr, w_res=ops["w_res"], res_off=shrink, out=out, ksplit=ks,
-                         scratch=_scratch_of(self) if ks > 1 else None, w_wino=ops["w_wino"] if ks == 1 else None)
+                         scratch=_scratch_of(self) if ks > 1 else None, w_wino=ops["w_wino"] if ks == 1 else None,
+                         w_wino_ext=ops["w_wino_ext"] if (ks == 1 and not (self.residual is zero and self.stride == 1)) else None)
 
 
 def _few_channels_fusable(self, x) -> bool:

@@ -18,6 +18,21 @@
 // K loop: 8-channel chunks as in tcn_stage_kernel (tcn.hip), the next chunk's loads trickled in three thirds in front of the
 // three group segments.  The weights stream from the host-transformed image, the staging types are those of mfma_core.h.
 // T odd: the last pair's second frame (t = T) is computed from zero padding and not stored.
+//
+// csk_tcn_stage_wino_ext_f32 adds two forms for the blocks the entry above leaves to the direct kernels:
+//   form A  stride 1, no residual: the kernel above without the residual load (RES = false).  Offered by the entry; the host
+//           layer's blocks keep the direct kernels for this shape (blocks.py: bitwise pin against csk_block_few_channels_f32).
+//   form B  stride 2 (pad 4), conv residual or none: with the phase streams e[n] = y[2 n], o[n] = y[2 n + 1]
+//              out[t] = sum_{a=0..4} w[2 a] e[t + a - 2] + sum_{a=0..3} w[2 a + 1] o[t + a - 2]
+//           a 5-tap and a 4-tap stride-1 conv, cut into four groups for F(2, 3) (same points, accumulator sets and output
+//           transform): E0 = even taps a = 0..2 (4 products), E1 = even taps a = 3, 4, O0 = odd taps a = 0, 1, O1 = odd taps
+//           a = 2, 3 -- the 2-tap groups have a zero third tap, so their point-inf product is skipped and d3 never read (3
+//           products each): 13 K-blocks per output pair and channel instead of 18.  No de-interleaving: in the raw staged row
+//           column (pair j, joint v) reads phase sample i of a group at raw frame 4 j - 4 + F + 2 i (F = 0, 6, 1, 5 for E0, E1,
+//           O0, O1) -- column stride 4 V, tap stride 2 V.  The 1 x 1 stride-2 conv residual res[t] = wres . x[2 t] runs as extra
+//           chunks over x after the main loop, a 1-tap group with d2 := d1: acc0 += wres (d0 - d1), acc1 += wres d1 (d0 = x[4 j],
+//           d1 = x[4 j + 2]), which the output transform turns into out(2 j) += wres d0, out(2 j + 1) += wres d1.
+//   weights (host, fold.pack_conv_weight_wino_s2): 13 rows E0 (4), E1 (3), O0 (3), O1 (3); the residual streams the direct w_res.
 #include "mfma_core.h"
 #include "tcn_params.h"
 
@@ -75,10 +90,57 @@ __device__ __forceinline__ void wino_group(const float *__restrict__ Wl, const f
     }
 }
 
+// ---- epilogue: output transform, + bias (+ identity residual, RES), ReLU.  C/D map: column = lane & 31 (this lane's pair column),
+// row = (g & 3) + 8 (g >> 2) + 4 (lane >> 5).  Row base pointers are wave-uniform (64-bit); a lane adds one 32-bit byte offset
+// (4 kh rows + its position; T V < 2^26 keeps it below 2^32).  Every tile has all 64 rows (c_out % 64 == 0, host gate).
+// p.Tout = output frames; (jc, vc) = this lane's pair column.
+template <int VT, bool RES>
+__device__ __forceinline__ void wino_epilogue(const TcnParams &p, const f32x16 (&acc)[4][2], int m0, int q0, int qend, int seg,
+                                              int wave, int l31, int kh, int jc, int vc) {
+    const int T = p.Tout, TV = T * VT;
+    const bool qv = q0 + wave * 32 + l31 < qend;
+    const bool odd_ok = 2 * jc + 1 < T;                              // the pair's second frame exists (T odd: not the last pair)
+    const unsigned p0 = (unsigned)(2 * jc * VT + vc);
+    const unsigned b0 = 4u * (4u * (unsigned)kh * (unsigned)TV + p0);
+    const unsigned b1 = odd_ok ? b0 + 4u * VT : b0;                  // phantom frame: re-read frame 2 j (value unused)
+    const unsigned kh16 = 16u * (unsigned)kh;
+    const float *rseg = RES ? p.xres + (int64_t)seg * p.Cout * TV : nullptr;
+    float *oseg = p.out + (int64_t)seg * p.Cout * TV;
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi) {
+        const int rb = m0 + mi * 32;
+        float o0[16], o1[16];
+#pragma unroll
+        for (int g = 0; g < 16; ++g) {
+            const int row = rb + (g & 3) + 8 * (g >> 2);
+            const float bias = ld_lane(p.bias + row, kh16);
+            const float m1 = acc[1][mi][g], m2 = acc[2][mi][g];
+            float v0 = acc[0][mi][g] + m1 + m2 + bias;
+            float v1 = m1 - m2 - acc[3][mi][g] + bias;
+            if (RES) {
+                const float *rrow = rseg + (int64_t)row * TV;
+                v0 += ld_lane(rrow, b0);
+                v1 += ld_lane(rrow, b1);
+            }
+            if (p.relu) { v0 = relu_nan(v0); v1 = relu_nan(v1); }
+            o0[g] = v0;
+            o1[g] = v1;
+        }
+        if (qv) {
+#pragma unroll
+            for (int g = 0; g < 16; ++g) {
+                float *orow = oseg + (int64_t)(rb + (g & 3) + 8 * (g >> 2)) * TV;
+                st_lane(orow, b0, o0[g]);
+                if (odd_ok) st_lane(orow, b1, o1[g]);
+            }
+        }
+    }
+}
+
 }  // namespace
 
 // p.Tout = T (frames in and out), p.nt = pair columns per segment ((T + 1) / 2 * V), p.w = the transformed weight image
-template <int VT>
+template <int VT, bool RES = true>
 __global__ __launch_bounds__(NTHREADS, 2) void tcn_stage_wino_kernel(const TcnParams p) {
     constexpr int LDB = wino_ldb<VT>();
     constexpr int NJ = (LDB + 63) / 64;
@@ -167,66 +229,294 @@ __global__ __launch_bounds__(NTHREADS, 2) void tcn_stage_wino_kernel(const TcnPa
         }
     }
 
-    // ---- epilogue: output transform, + bias + identity residual, ReLU.  C/D map: column = lane & 31 (this lane's pair column),
-    // row = (g & 3) + 8 (g >> 2) + 4 (lane >> 5).  Row base pointers are wave-uniform (64-bit); a lane adds one 32-bit byte offset
-    // (4 kh rows + its position; T V < 2^26 keeps it below 2^32).  Every tile has all 64 rows (c_out % 64 == 0, host gate).
-    const bool qv = q0 + wave * 32 + l31 < qend;
-    const bool odd_ok = 2 * jc + 1 < T;                              // the pair's second frame exists (T odd: not the last pair)
-    const unsigned p0 = (unsigned)(2 * jc * VT + vc);
-    const unsigned b0 = 4u * (4u * (unsigned)kh * (unsigned)TV + p0);
-    const unsigned b1 = odd_ok ? b0 + 4u * VT : b0;                  // phantom frame: re-read frame 2 j (value unused)
-    const unsigned kh16 = 16u * (unsigned)kh;
-    const float *rseg = p.xres + (int64_t)seg * p.Cout * TV;
-    float *oseg = p.out + (int64_t)seg * p.Cout * TV;
+    wino_epilogue<VT, RES>(p, acc, m0, q0, qend, seg, wave, l31, kh, jc, vc);
+}
+
+// ------------------------------------------------------------------------------------------------
+// form B: stride 2 by polyphase F(2, 3) groups (header comment)
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int W2TAPS = 13;     // (group, point) products per channel: E0 4, E1 3, O0 3, O1 3
+
+// LDS row of one staged channel: the raw frames 4 ja - 4 .. 4 jb + 6 of a tile whose pair columns span pairs ja .. jb
+template <int VT>
+constexpr int wino2_ldb() { return ((4 * ((WNT + VT - 2) / VT) + 11) * VT + 3) / 4 * 4; }
+
+// Weight staging of a 13-row chunk of the 64-row tile: 13 * KC * 16 = 1664 f32x4 = 6.5 per thread; slot u of a thread is image
+// row 2 u + tid / 128 (WStage12x64); the upper half of the threads has no slot 6 and repeats its slot 5 (same value to the
+// same address, as WStage9x64 does)
+struct WStage13x64 {
+    unsigned goff0, loff0, gstride, u6;
+    f32x4 v[7];
+    __device__ __forceinline__ void setup(int Cpad, int Mpad, int tid) {
+        goff0 = (unsigned)(((tid >> 7) * Cpad + ((tid >> 4) & 7)) * Mpad + (tid & 15) * 4);
+        loff0 = (unsigned)(tid * 4);
+        gstride = (unsigned)(2 * Cpad * Mpad);
+        u6 = tid >= 128 ? 5u : 6u;
+    }
+    __device__ __forceinline__ void issue_slot(int u, const float *__restrict__ chunk_base) {
+        if (u < 6) v[u] = *reinterpret_cast<const f32x4 *>(chunk_base + (size_t)u * gstride + goff0);
+        else v[6] = *reinterpret_cast<const f32x4 *>(chunk_base + (size_t)u6 * gstride + goff0);
+    }
+    __device__ __forceinline__ void issue(const float *__restrict__ chunk_base) {
 #pragma unroll
-    for (int mi = 0; mi < 2; ++mi) {
-        const int rb = m0 + mi * 32;
-        float o0[16], o1[16];
+        for (int u = 0; u < 7; ++u) issue_slot(u, chunk_base);
+    }
+    __device__ __forceinline__ void commit(float *__restrict__ Wl) const {
 #pragma unroll
-        for (int g = 0; g < 16; ++g) {
-            const int row = rb + (g & 3) + 8 * (g >> 2);
-            const float *rrow = rseg + (int64_t)row * TV;
-            const float bias = ld_lane(p.bias + row, kh16);
-            const float m1 = acc[1][mi][g], m2 = acc[2][mi][g];
-            float v0 = acc[0][mi][g] + m1 + m2 + bias + ld_lane(rrow, b0);
-            float v1 = m1 - m2 - acc[3][mi][g] + bias + ld_lane(rrow, b1);
-            if (p.relu) { v0 = relu_nan(v0); v1 = relu_nan(v1); }
-            o0[g] = v0;
-            o1[g] = v1;
-        }
-        if (qv) {
+        for (int u = 0; u < 6; ++u) *reinterpret_cast<f32x4 *>(Wl + u * (NTHREADS * 4) + loff0) = v[u];
+        *reinterpret_cast<f32x4 *>(Wl + u6 * (NTHREADS * 4) + loff0) = v[6];
+    }
+};
+
+// Residual weights: one 8-channel chunk of the direct w_res image for the 64-row tile = 128 f32x4, one per thread of the lower
+// half; the upper half repeats it (same value to the same address)
+struct WStageRes64 {
+    unsigned goff0, loff0;
+    f32x4 v;
+    __device__ __forceinline__ void setup(int Mpad, int tid) {
+        goff0 = (unsigned)(((tid >> 4) & 7) * Mpad + (tid & 15) * 4);
+        loff0 = (unsigned)((tid & 127) * 4);
+    }
+    __device__ __forceinline__ void issue(const float *__restrict__ chunk_base) {
+        v = *reinterpret_cast<const f32x4 *>(chunk_base + goff0);
+    }
+    __device__ __forceinline__ void commit(float *__restrict__ Wl) const { *reinterpret_cast<f32x4 *>(Wl + loff0) = v; }
+};
+
+// One group segment of a chunk for one wave: image rows ROW0 .. ROW0 + NP - 1, phase samples d_i at raw frame F + 2 i of the
+// lane's column; NP = 3: the group's third tap is zero -- no point-inf product, d3 not read
+template <int VT, int ROW0, int F, int NP>
+__device__ __forceinline__ void wino2_group(const float *__restrict__ Wl, const float *__restrict__ Bl, int off, int l31, int kh,
+                                            f32x16 (&acc)[4][2]) {
+    constexpr int LDB = wino2_ldb<VT>();
+    const float *br = Bl + kh * LDB + off + F * VT;
+    const float *wr = Wl + ROW0 * (KC * WMT) + kh * WMT + l31;
 #pragma unroll
-            for (int g = 0; g < 16; ++g) {
-                float *orow = oseg + (int64_t)(rb + (g & 3) + 8 * (g >> 2)) * TV;
-                st_lane(orow, b0, o0[g]);
-                if (odd_ok) st_lane(orow, b1, o1[g]);
-            }
+    for (int s = 0; s < KC / 2; ++s) {
+        const float d0 = br[2 * s * LDB], d1 = br[2 * s * LDB + 2 * VT], d2 = br[2 * s * LDB + 4 * VT];
+        const float d3 = NP == 4 ? br[2 * s * LDB + 6 * VT] : 0.f;
+        const float b[4] = {d0 - d2, d1 + d2, d2 - d1, d1 - d3};
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            const float a0 = wr[i * (KC * WMT) + 2 * s * WMT], a1 = wr[i * (KC * WMT) + 2 * s * WMT + 32];
+            acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b[i], acc[i][0], 0, 0, 0);
+            acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b[i], acc[i][1], 0, 0, 0);
         }
     }
 }
 
-// -2: the shape is not one the Winograd kernel is built for (the caller runs the direct kernels); 0 / error code otherwise
+// One residual chunk: the staged row starts at raw frame 4 ja of x; d0 = x[4 j], d1 = x[4 j + 2]
+template <int VT>
+__device__ __forceinline__ void wino2_res_chunk(const float *__restrict__ Wl, const float *__restrict__ Bl, int off, int l31, int kh,
+                                                f32x16 (&acc)[4][2]) {
+    constexpr int LDB = wino2_ldb<VT>();
+    const float *br = Bl + kh * LDB + off;
+    const float *wr = Wl + kh * WMT + l31;
+#pragma unroll
+    for (int s = 0; s < KC / 2; ++s) {
+        const float d0 = br[2 * s * LDB], d1 = br[2 * s * LDB + 2 * VT];
+        const float a0 = wr[2 * s * WMT], a1 = wr[2 * s * WMT + 32];
+        const float b0 = d0 - d1;
+        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
+        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[0][1], 0, 0, 0);
+        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, d1, acc[1][0], 0, 0, 0);
+        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, d1, acc[1][1], 0, 0, 0);
+    }
+}
+
+}  // namespace
+
+// p.Tin = input frames, p.Tout = output frames ((Tin - 1) / 2 + 1), p.nt = pair columns per segment ((Tout + 1) / 2 * V),
+// p.w = the 13-row image, p.wres / p.xres = direct residual image and block input (RESCONV) with p.Tres == p.Tin
+template <int VT, bool RESCONV>
+__global__ __launch_bounds__(NTHREADS, 2) void tcn_stage_wino_s2_kernel(const TcnParams p) {
+    constexpr int LDB = wino2_ldb<VT>();
+    constexpr int NJ = (LDB + 63) / 64;
+    constexpr int NJR = ((4 * ((WNT + VT - 2) / VT) + 3) * VT + 63) / 64;     // residual rows: raw frames 4 ja .. 4 jb + 2
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float *Wl = smem;
+    float *Bl = smem + W2TAPS * KC * WMT;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l31 = lane & 31, kh = lane >> 5;
+    const unsigned wid = xcd_contiguous_id(blockIdx.x, gridDim.x);
+    const int m0 = (int)(wid % p.mtiles) * WMT, q0 = (int)((wid / p.mtiles) % p.qtiles) * WNT;
+    const int seg = (int)(wid / (p.mtiles * p.qtiles));
+    const int TVin = p.Tin * VT, QP = p.nt;
+    const int qend = min(q0 + WNT, QP);
+    const int ja = div_magic(q0, p.vmagic), jb = div_magic(qend - 1, p.vmagic);
+
+    // this lane's pair column (clamped into the tile; lanes past its end compute a copy of the last column and store nothing)
+    const int qc = min(q0 + wave * 32 + l31, qend - 1);
+    const int jc = div_magic(qc, p.vmagic), vc = qc - jc * VT;
+    const int off = 4 * (jc - ja) * VT + vc;
+
+    f32x16 acc[4][2];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+            for (int g = 0; g < 16; ++g) acc[i][mi][g] = 0.f;
+
+    {
+        const int fa = 4 * ja - 4;                                   // first raw frame of the tile (pad 4)
+        const int span = (4 * (jb - ja) + 11) * VT;
+        const int64_t cs = (int64_t)TVin;
+        const float *seg_base = p.y + (int64_t)seg * p.C * cs;       // 64-bit segment base; 32-bit offsets inside it
+        const float *wbase = p.w + m0;
+        WStage13x64 ws;
+        ws.setup(p.Cpad, p.Mpad, tid);
+        auto kloop = [&](auto &bx) {
+            ws.issue(wbase);
+            bx.issue(seg_base, p.C, cs, 0, wave);
+            for (int c0 = 0; c0 + KC < p.Cpad; c0 += KC) {
+                __syncthreads();                     // previous chunk's LDS reads are done
+                ws.commit(Wl);
+                bx.commit(Bl, LDB, wave);
+                __syncthreads();
+                const float *wnext = wbase + (size_t)(c0 + KC) * p.Mpad;
+                const int cn = c0 + KC;
+                ws.issue_slot(0, wnext);
+                ws.issue_slot(1, wnext);
+                bx.template issue_third<0>(seg_base, p.C, cs, cn, wave);
+                __builtin_amdgcn_s_setprio(1);
+                wino2_group<VT, 0, 0, 4>(Wl, Bl, off, l31, kh, acc);
+                __builtin_amdgcn_s_setprio(0);
+                ws.issue_slot(2, wnext);
+                ws.issue_slot(3, wnext);
+                bx.template issue_third<1>(seg_base, p.C, cs, cn, wave);
+                __builtin_amdgcn_s_setprio(1);
+                wino2_group<VT, 4, 6, 3>(Wl, Bl, off, l31, kh, acc);
+                __builtin_amdgcn_s_setprio(0);
+                ws.issue_slot(4, wnext);
+                ws.issue_slot(5, wnext);
+                bx.template issue_third<2>(seg_base, p.C, cs, cn, wave);
+                __builtin_amdgcn_s_setprio(1);
+                wino2_group<VT, 7, 1, 3>(Wl, Bl, off, l31, kh, acc);
+                __builtin_amdgcn_s_setprio(0);
+                ws.issue_slot(6, wnext);
+                __builtin_amdgcn_s_setprio(1);
+                wino2_group<VT, 10, 5, 3>(Wl, Bl, off, l31, kh, acc);
+                __builtin_amdgcn_s_setprio(0);
+            }
+            __syncthreads();                         // peeled last chunk
+            ws.commit(Wl);
+            bx.commit(Bl, LDB, wave);
+            __syncthreads();
+            wino2_group<VT, 0, 0, 4>(Wl, Bl, off, l31, kh, acc);
+            wino2_group<VT, 4, 6, 3>(Wl, Bl, off, l31, kh, acc);
+            wino2_group<VT, 7, 1, 3>(Wl, Bl, off, l31, kh, acc);
+            wino2_group<VT, 10, 5, 3>(Wl, Bl, off, l31, kh, acc);
+        };
+        // tiles whose staged span lies inside the sequence: 16-byte staging; the others (zero padding at either end) element-wise
+        const bool interior = fa >= 0 && fa * VT + 4 * ((span + 3) / 4) <= TVin;   // uniform
+        if (interior) {
+            BStage4<(NJ + 3) / 4> b4;
+            b4.setup(fa * VT, span, lane);
+            kloop(b4);
+        } else {
+            BStage<NJ> bs;
+            bs.setup(fa * VT, span, TVin, lane);
+            kloop(bs);
+        }
+    }
+
+    if (RESCONV) {
+        // conv residual: 8-channel chunks of x (element-wise staging: frames past the end read as zero), the next chunk's
+        // loads issued in front of the current chunk's products
+        const int span = (4 * (jb - ja) + 3) * VT;
+        const int64_t cs = (int64_t)p.Tres * VT;
+        const float *seg_base = p.xres + (int64_t)seg * p.Cres * cs;
+        const float *wbase = p.wres + m0;
+        const int cend = (p.Cres + KC - 1) / KC * KC;                // <= CresPad: rows of the image
+        WStageRes64 wr;
+        wr.setup(p.Mpad, tid);
+        BStage<NJR> bs;
+        bs.setup(4 * ja * VT, span, p.Tres * VT, lane);
+        wr.issue(wbase);
+        bs.issue(seg_base, p.Cres, cs, 0, wave);
+        for (int c0 = 0; c0 + KC < cend; c0 += KC) {
+            __syncthreads();
+            wr.commit(Wl);
+            bs.commit(Bl, LDB, wave);
+            __syncthreads();
+            wr.issue(wbase + (size_t)(c0 + KC) * p.Mpad);
+            bs.issue(seg_base, p.Cres, cs, c0 + KC, wave);
+            wino2_res_chunk<VT>(Wl, Bl, off, l31, kh, acc);
+        }
+        __syncthreads();
+        wr.commit(Wl);
+        bs.commit(Bl, LDB, wave);
+        __syncthreads();
+        wino2_res_chunk<VT>(Wl, Bl, off, l31, kh, acc);
+    }
+
+    wino_epilogue<VT, false>(p, acc, m0, q0, qend, seg, wave, l31, kh, jc, vc);
+}
+
+// -2: the shape is not one the Winograd kernel is built for (the caller runs the direct kernels); 0 / error code otherwise.
+// res_none: form A of csk_tcn_stage_wino_ext_f32 (no residual) instead of the identity-residual form.
 static int tcn_stage_wino_launch(const float *y, const float *w_wino, const float *x_res, const float *bias, float *out, int n_seg,
                                  int c, int c_out, int t_in, int V, int k, int stride, int pad, int res_mode, int c_res, int t_res,
-                                 int res_off, int relu, void *stream) {
-    if (!w_wino || !y || !x_res || !bias || !out) return -2;
-    if (k != 9 || stride != 1 || pad != 4 || res_mode != CSK_RES_IDENTITY || res_off != 0) return -2;
-    if ((V != 25 && V != 18) || c_out % WMT != 0 || c_res != c_out || t_res != t_in || c < 1 || n_seg < 1 || t_in < 1) return -2;
+                                 int res_off, int relu, void *stream, bool res_none = false) {
+    if (!w_wino || !y || !bias || !out) return -2;
+    if (k != 9 || stride != 1 || pad != 4) return -2;
+    if (res_none ? res_mode != CSK_RES_NONE : (res_mode != CSK_RES_IDENTITY || res_off != 0 || !x_res || c_res != c_out || t_res != t_in))
+        return -2;
+    if ((V != 25 && V != 18) || c_out % WMT != 0 || c < 1 || n_seg < 1 || t_in < 1) return -2;
     if ((int64_t)t_in * V >= (1 << 26)) return -2;                    // 32-bit position / lane byte offsets inside a segment
     if (csk_diag_flag("CSK_TCN_WINO")) return -2;                     // diagnostic A/B switch: the direct kernels
     const int qp = (t_in + 1) / 2 * V;
     const int qtiles = (qp + WNT - 1) / WNT, mtiles = c_out / WMT;
     if ((int64_t)qtiles * mtiles * n_seg >= (1ll << 31)) return -2;
     TcnParams p = {};
-    p.y = y; p.w = w_wino; p.xres = x_res; p.wres = nullptr; p.bias = bias; p.out = out;
+    p.y = y; p.w = w_wino; p.xres = res_none ? nullptr : x_res; p.wres = nullptr; p.bias = bias; p.out = out;
     p.C = c; p.Cpad = round_up(c, CSK_CPAD); p.Cout = c_out; p.Mpad = round_up(c_out, CSK_MT);
     p.Tin = t_in; p.Tout = t_in; p.V = V; p.K = k; p.stride = 1; p.pad = pad;
-    p.res_mode = res_mode; p.Cres = c_res; p.CresPad = round_up(c_res, CSK_CPAD); p.Tres = t_res; p.res_off = 0; p.relu = relu;
+    p.res_mode = res_mode; p.Cres = res_none ? 0 : c_res; p.CresPad = round_up(p.Cres, CSK_CPAD); p.Tres = res_none ? 0 : t_res;
+    p.res_off = 0; p.relu = relu;
     p.vmagic = vmagic_of(V); p.mtiles = (unsigned)mtiles; p.qtiles = (unsigned)qtiles; p.nt = qp;
-    void (*kern)(TcnParams) = V == 25 ? tcn_stage_wino_kernel<25> : tcn_stage_wino_kernel<18>;
+    void (*kern)(TcnParams) = res_none ? (V == 25 ? tcn_stage_wino_kernel<25, false> : tcn_stage_wino_kernel<18, false>)
+                                       : (V == 25 ? tcn_stage_wino_kernel<25> : tcn_stage_wino_kernel<18>);
     const int ldb = V == 25 ? wino_ldb<25>() : wino_ldb<18>();
     p.ldb = ldb;
     const size_t lds = (size_t)(WTAPS * KC * WMT + KC * ldb) * sizeof(float);
+    if (const int e = csk_ensure_lds((const void *)kern, lds)) return e;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(qtiles * mtiles * n_seg)), dim3(NTHREADS), lds, (hipStream_t)stream, p);
+    return (int)hipGetLastError();
+}
+
+// form B of csk_tcn_stage_wino_ext_f32; -2 as above
+static int tcn_stage_wino_s2_launch(const float *y, const float *w_s2, const float *x_res, const float *w_res, const float *bias,
+                                    float *out, int n_seg, int c, int c_out, int t_in, int V, int k, int stride, int pad,
+                                    int res_mode, int c_res, int t_res, int res_off, int relu, void *stream) {
+    if (!w_s2 || !y || !bias || !out) return -2;
+    if (k != 9 || stride != 2 || pad != 4 || res_off != 0) return -2;
+    const bool conv = res_mode == CSK_RES_CONV;
+    if (!conv && res_mode != CSK_RES_NONE) return -2;
+    if (conv && (!x_res || !w_res || c_res < 1 || t_res != t_in)) return -2;
+    if ((V != 25 && V != 18) || c_out % WMT != 0 || c < 1 || n_seg < 1 || t_in < 1) return -2;
+    if ((int64_t)t_in * V >= (1 << 26)) return -2;                    // 32-bit position / lane byte offsets inside a segment
+    if (csk_diag_flag("CSK_TCN_WINO")) return -2;                     // diagnostic A/B switch: the direct kernels
+    const int t_out = (t_in - 1) / 2 + 1;
+    const int qp = (t_out + 1) / 2 * V;
+    const int qtiles = (qp + WNT - 1) / WNT, mtiles = c_out / WMT;
+    if ((int64_t)qtiles * mtiles * n_seg >= (1ll << 31)) return -2;
+    TcnParams p = {};
+    p.y = y; p.w = w_s2; p.xres = conv ? x_res : nullptr; p.wres = conv ? w_res : nullptr; p.bias = bias; p.out = out;
+    p.C = c; p.Cpad = round_up(c, CSK_CPAD); p.Cout = c_out; p.Mpad = round_up(c_out, CSK_MT);
+    p.Tin = t_in; p.Tout = t_out; p.V = V; p.K = k; p.stride = 2; p.pad = pad;
+    p.res_mode = res_mode; p.Cres = conv ? c_res : 0; p.CresPad = round_up(p.Cres, CSK_CPAD); p.Tres = conv ? t_res : 0;
+    p.res_off = 0; p.relu = relu;
+    p.vmagic = vmagic_of(V); p.mtiles = (unsigned)mtiles; p.qtiles = (unsigned)qtiles; p.nt = qp;
+    void (*kern)(TcnParams) = conv ? (V == 25 ? tcn_stage_wino_s2_kernel<25, true> : tcn_stage_wino_s2_kernel<18, true>)
+                                   : (V == 25 ? tcn_stage_wino_s2_kernel<25, false> : tcn_stage_wino_s2_kernel<18, false>);
+    const int ldb = V == 25 ? wino2_ldb<25>() : wino2_ldb<18>();
+    p.ldb = ldb;
+    const size_t lds = (size_t)(W2TAPS * KC * WMT + KC * ldb) * sizeof(float);
     if (const int e = csk_ensure_lds((const void *)kern, lds)) return e;
     hipLaunchKernelGGL(kern, dim3((unsigned)(qtiles * mtiles * n_seg)), dim3(NTHREADS), lds, (hipStream_t)stream, p);
     return (int)hipGetLastError();
@@ -237,6 +527,22 @@ extern "C" int csk_tcn_stage_wino_f32(const float *y, const float *w, const floa
                                       int res_mode, int c_res, int t_res, int res_off, int relu, const float *w_wino, void *stream) {
     const int rc = tcn_stage_wino_launch(y, w_wino, x_res, bias, out, n_seg, c, c_out, t_in, V, k, stride, pad, res_mode, c_res,
                                          t_res, res_off, relu, stream);
+    if (rc != -2) return rc;
+    return csk_tcn_stage_f32(y, w, x_res, w_res, bias, out, n_seg, c, c_out, t_in, V, k, stride, pad, res_mode, c_res, t_res,
+                             res_off, relu, stream);
+}
+
+extern "C" int csk_tcn_stage_wino_ext_f32(const float *y, const float *w, const float *x_res, const float *w_res, const float *bias,
+                                          float *out, int n_seg, int c, int c_out, int t_in, int V, int k, int stride, int pad,
+                                          int res_mode, int c_res, int t_res, int res_off, int relu, const float *w_wino_ext,
+                                          void *stream) {
+    int rc = -2;
+    if (stride == 1)
+        rc = tcn_stage_wino_launch(y, w_wino_ext, nullptr, bias, out, n_seg, c, c_out, t_in, V, k, stride, pad, res_mode, c_res,
+                                   t_res, res_off, relu, stream, true);
+    else if (stride == 2)
+        rc = tcn_stage_wino_s2_launch(y, w_wino_ext, x_res, w_res, bias, out, n_seg, c, c_out, t_in, V, k, stride, pad, res_mode,
+                                      c_res, t_res, res_off, relu, stream);
     if (rc != -2) return rc;
     return csk_tcn_stage_f32(y, w, x_res, w_res, bias, out, n_seg, c, c_out, t_in, V, k, stride, pad, res_mode, c_res, t_res,
                              res_off, relu, stream);

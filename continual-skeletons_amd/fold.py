@@ -55,6 +55,34 @@ def pack_conv_weight_wino(weight: torch.Tensor, scale: torch.Tensor) -> torch.Te
     return out.float().contiguous()
 
 
+# The stride-2 image: the 9 taps as polyphase groups (first tap, taps) -- E0, E1 on the even phase y[2 n], O0, O1 on the odd phase
+WINO_S2_GROUPS = ((0, 3), (6, 2), (1, 2), (5, 2))
+
+
+def pack_conv_weight_wino_s2(weight: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """(C_out, C_in, 9, 1) conv weight * per-output scale -> the polyphase image of csk_tcn_stage_wino_ext_f32's stride-2 form
+    (include/cskel.h), packed [13][C_in_pad][C_out_pad] fp32.  With e[n] = y[2 n], o[n] = y[2 n + 1] the stride-2 conv is a 5-tap
+    conv on e (taps 0, 2, 4, 6, 8) plus a 4-tap conv on o (taps 1, 3, 5, 7), cut into the groups E0 = (w0, w2, w4), E1 = (w6, w8, 0),
+    O0 = (w1, w3, 0), O1 = (w5, w7, 0); each goes through the F(2, 3) weight transform G.  A 2-tap group's point-inf row is zero
+    and is left out: rows 0-3 E0, 4-6 E1, 7-9 O0, 10-12 O1.  Formed in float64 from the BN-folded weight, rounded to fp32 once."""
+    if weight.dim() == 4:
+        weight = weight[:, :, :, 0]
+    co, ci, k = weight.shape
+    if k != 9:
+        raise ValueError(f"the Winograd image is built for the 9 x 1 temporal conv, got k = {k}")
+    w = weight.double() * scale[:, None, None]                                       # (co, ci, 9)
+    g = torch.tensor(WINO_G, dtype=torch.float64)                                    # (4, 3)
+    rows = []
+    for first, ntaps in WINO_S2_GROUPS:
+        taps = torch.zeros((co, ci, 3), dtype=torch.float64)
+        taps[:, :, :ntaps] = w[:, :, first: first + 2 * ntaps: 2]
+        rows.append(torch.einsum("ir,ocr->ico", g, taps)[: ntaps + 1])               # 3 taps: 4 points; 2 taps: 3 points
+    u = torch.cat(rows, 0)                                                           # (13, ci, co)
+    out = torch.zeros((13, _ceil_to(ci, KC), _ceil_to(co, MT)), dtype=torch.float64)
+    out[:, :ci, :co] = u
+    return out.float().contiguous()
+
+
 SPLIT_KS = 16     # channels per K step of the bf16x3 split kernels (csrc/tcn_split.hip)
 
 
@@ -150,15 +178,17 @@ def fold_graph_conv(sd: Dict[str, torch.Tensor], p: str = "", split: bool = Fals
     return out
 
 
-def fold_temporal_conv(sd: Dict[str, torch.Tensor], p: str = "", wino: bool = False) -> dict:
+def fold_temporal_conv(sd: Dict[str, torch.Tensor], p: str = "", wino: bool = False, wino_s2: bool = False) -> dict:
     """Packed weight + bias of a TemporalConvolution (models/base.py:279-304); wino: also the Winograd image ``w_wino``
-    (9-tap convs; None otherwise)."""
+    (9-tap convs; None otherwise); wino_s2: also the stride-2 polyphase image ``w_wino_s2`` (the same)."""
     s, t = bn_affine(sd[p + "bn.weight"].cpu(), sd[p + "bn.bias"].cpu(), sd[p + "bn.running_mean"].cpu(),
                      sd[p + "bn.running_var"].cpu())
     wt = sd[p + "t_conv.weight"].detach().cpu()
     bias = s * sd[p + "t_conv.bias"].detach().cpu().double() + t
     w_wino = pack_conv_weight_wino(wt, s) if wino and wt.shape[2] == 9 else None
-    return dict(w=pack_conv_weight(wt, s), bias=bias, c_in=wt.shape[1], c_out=wt.shape[0], k=wt.shape[2], w_wino=w_wino)
+    w_wino_s2 = pack_conv_weight_wino_s2(wt, s) if wino_s2 and wt.shape[2] == 9 else None
+    return dict(w=pack_conv_weight(wt, s), bias=bias, c_in=wt.shape[1], c_out=wt.shape[0], k=wt.shape[2], w_wino=w_wino,
+                w_wino_s2=w_wino_s2)
 
 
 def fold_temporal_conv_split(sd: Dict[str, torch.Tensor], p: str = "", stride: int = 1) -> torch.Tensor:
@@ -169,13 +199,17 @@ def fold_temporal_conv_split(sd: Dict[str, torch.Tensor], p: str = "", stride: i
 
 
 def fold_block_tail(sd: Dict[str, torch.Tensor], p: str = "", has_conv_residual: Optional[bool] = None,
-                    split: bool = False, stride: int = 1) -> dict:
+                    split: bool = False, stride: int = 1, no_residual: bool = False) -> dict:
     """Operands of csk_tcn_stage_f32 for a whole SpatioTemporalBlock tail: tcn (+ conv residual).  split: also the
     bf16x3 operand images ``w_split`` / ``w_res_split`` (precision mode "bf16x3", 9-tap convs only).  ``w_wino``: the
-    Winograd image of csk_tcn_stage_wino_f32 for 9-tap stride-1 convs (None otherwise)."""
-    main = fold_temporal_conv(sd, p + "tcn.", wino=stride == 1)
+    Winograd image of csk_tcn_stage_wino_f32 for 9-tap stride-1 convs (None otherwise).  ``w_wino_ext``: the image of
+    csk_tcn_stage_wino_ext_f32 -- the polyphase image for 9-tap stride-2 convs, the stride-1 image for a 9-tap stride-1 block
+    without residual (no_residual), None otherwise.  SpatioTemporalBlock.forward passes the stride-2 image only: the no_residual
+    image is carried for callers of blocks.tcn_stage(w_wino_ext=), no model runs it (blocks.py)."""
+    main = fold_temporal_conv(sd, p + "tcn.", wino=stride == 1, wino_s2=stride == 2)
     out = dict(w=main["w"], k=main["k"], c=main["c_in"], c_out=main["c_out"], w_res=None, c_res=0, w_split=None, w_res_split=None,
-               w_wino=main["w_wino"])
+               w_wino=main["w_wino"],
+               w_wino_ext=main["w_wino_s2"] if stride == 2 else main["w_wino"] if (stride == 1 and no_residual) else None)
     bias = main["bias"]
     if has_conv_residual is None:
         has_conv_residual = (p + "residual.t_conv.weight") in sd

@@ -133,6 +133,29 @@ int csk_tcn_stage_wino_f32(const float *y, const float *w, const float *x_res, c
                            int res_mode, int c_res, int t_res, int res_off, int relu, const float *w_wino, void *stream);
 
 /*
+ * csk_tcn_stage_f32 with the Winograd forms for the blocks csk_tcn_stage_wino_f32 leaves to the direct kernels (k = 9, pad 4,
+ * res_off 0, V in {25, 18}, c_out % 64 == 0, w_wino_ext != NULL; a function of the layer, never of n_seg or t_in):
+ *  stride 1, res_mode NONE: the F(2, 3) kernel of csk_tcn_stage_wino_f32 without the residual load;
+ *           w_wino_ext = the [12][c_pad][c_out_pad] image of fold.pack_conv_weight_wino.
+ *  stride 2, res_mode NONE or CONV (t_res == t_in): with e[n] = y[2 n], o[n] = y[2 n + 1] the conv is a 5-tap conv on e (taps
+ *           0, 2, 4, 6, 8) plus a 4-tap conv on o (taps 1, 3, 5, 7), cut into the groups E0 = (w0, w2, w4), E1 = (w6, w8, 0),
+ *           O0 = (w1, w3, 0), O1 = (w5, w7, 0), each an F(2, 3); the point-inf product of a 2-tap group is zero and skipped:
+ *           13 instead of 18 fp32 MFMA K-blocks per output frame pair and channel.  The 1 x 1 stride-2 residual conv adds 2 per
+ *           residual channel, as in the direct form, and streams the direct w_res image.
+ *           w_wino_ext = packed [13][c_pad][c_out_pad] (fold.pack_conv_weight_wino_s2): rows 0-3 G.E0, rows 4-6 / 7-9 / 10-12 the
+ *           first three rows of G.E1 / G.O0 / G.O1; fp64, rounded to fp32 once.  The caller passes the image that belongs to
+ *           `stride`: the entry is not told its size.
+ * Exact fp32 arithmetic; differs from csk_tcn_stage_f32 by the rounding of the transformed weights and operands (about 1e-6
+ * relative).  Any other call runs csk_tcn_stage_f32.  The Python host layer's SpatioTemporalBlock calls this entry for its
+ * stride-2 blocks only; the stride-1 form is for callers that do not need csk_tcn_stage_f32's bits (csk_block_few_channels_f32
+ * is bit for bit the direct two-launch block).
+ */
+int csk_tcn_stage_wino_ext_f32(const float *y, const float *w, const float *x_res, const float *w_res,
+                               const float *bias, float *out,
+                               int n_seg, int c, int c_out, int t_in, int V, int k, int stride, int pad,
+                               int res_mode, int c_res, int t_res, int res_off, int relu, const float *w_wino_ext, void *stream);
+
+/*
  * A whole SpatioTemporalBlock with a FEW input channels and no block residual -- layer 1 of the reference's stacks
  * (models/st_gcn/st_gcn.py:30: StGcnBlock(3, 64, A, residual=False); block body models/base.py:376-387) -- in ONE launch:
  *   out = ReLU( tcn( gcn(x) ) ),  gcn(x) = ReLU( sum_k W'_k . (x . A_k) + b' + conv1x1+BN(x) )   (models/base.py:230-270)
