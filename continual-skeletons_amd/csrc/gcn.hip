@@ -774,21 +774,22 @@ __global__ __launch_bounds__(256) void gcn_reduce_kernel(const GcnParams p) {
 // ------------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------------
-static int gcn_stage_impl(const float *x, float *y, const float *w, const float *bias, const int32_t *ell_src,
-                          const float *ell_val, const int32_t *ell_cnt, int ell_w, int64_t adj_seg_stride,
-                          int adj_per_frame,
-                          int n_seg, int c_in, int c_out, int frames, int V, int64_t x_seg_stride,
-                          int64_t x_chan_stride, int64_t y_seg_stride, int64_t y_chan_stride, int res_mode,
-                          int ksplit, float *partial, void *stream) {
-    if (!x || !y || !w || !bias || !ell_src || !ell_val || !ell_cnt) CSK_FAIL("gcn_stage: null pointer");
+// What every launch of the stage starts from: the argument checks that need no operand (0, or -1 with the message set), the launch
+// parameters with the geometry of the 32x32x2 tiles, *lds_out = the general kernel's LDS tile, *sparse_out = the skeleton-sparse
+// fast path applies.  No pointer but ell_cnt is dereferenced: csk_gcn_stage_f32_tile calls it without operands.
+static int gcn_stage_setup(const float *x, float *y, const float *w, const float *bias, const int32_t *ell_src, const float *ell_val,
+                           const int32_t *ell_cnt, int ell_w, int64_t adj_seg_stride, int adj_per_frame, int n_seg, int c_in, int c_out,
+                           int frames, int V, int64_t x_seg_stride, int64_t x_chan_stride, int64_t y_seg_stride, int64_t y_chan_stride,
+                           int res_mode, int ksplit, float *partial, GcnParams *out, size_t *lds_out, bool *sparse_out) {
     if (n_seg <= 0 || c_in <= 0 || c_out <= 0 || frames <= 0 || V < 2 || V > 64) CSK_FAIL("gcn_stage: bad dims");
     if (ell_w < 1 || ell_w > V) CSK_FAIL("gcn_stage: ell_w must be in [1, V]");
     if (res_mode != CSK_RES_IDENTITY && res_mode != CSK_RES_CONV) CSK_FAIL("gcn_stage: res_mode must be identity or conv");
     if (res_mode == CSK_RES_IDENTITY && c_in != c_out) CSK_FAIL("gcn_stage: identity residual needs c_in == c_out");
     for (int i = 0; i < 3; ++i)
         if (ell_cnt[i] < 0 || ell_cnt[i] > ell_w) CSK_FAIL("gcn_stage: ell_cnt[%d] out of range", i);
-    GcnParams p = gcn_params(x, y, w, bias, ell_src, ell_val, ell_cnt, ell_w, adj_seg_stride, c_in, c_out, frames, V, x_seg_stride,
-                             x_chan_stride, y_seg_stride, y_chan_stride, res_mode, partial);
+    GcnParams &p = *out;
+    p = gcn_params(x, y, w, bias, ell_src, ell_val, ell_cnt, ell_w, adj_seg_stride, c_in, c_out, frames, V, x_seg_stride,
+                   x_chan_stride, y_seg_stride, y_chan_stride, res_mode, partial);
     // per-segment adjacencies are dense by contract (include/cskel.h): ell_w == V, ell_cnt == {V,V,V}, src[e] == e
     p.dense = adj_seg_stride != 0 && ell_w == V && ell_cnt[0] == V && ell_cnt[1] == V && ell_cnt[2] == V;
     p.adj_per_frame = adj_per_frame != 0;
@@ -804,14 +805,37 @@ static int gcn_stage_impl(const float *x, float *y, const float *w, const float 
     if ((int64_t)frames * V >= (1 << 26)) CSK_FAIL("gcn_stage: frames*V too large for 32-bit position arithmetic");
     p.qtiles = (Q + NT - 1) / NT; p.mtiles = p.Mpad / MT;
     if ((int64_t)p.qtiles * p.mtiles * n_seg >= (1ll << 31)) CSK_FAIL("gcn_stage: grid too large");
-    dim3 grid(p.qtiles * p.mtiles * n_seg);
     // sparse-graph fast path: shared adjacency with <= 1/1/4 non-zeros per column, activation tile <= 320 positions
     const bool sparse = adj_seg_stride == 0 && ell_cnt[0] <= 1 && ell_cnt[1] <= 1 && ell_cnt[2] <= 4 && p.ldb <= (big ? 192 : 320) &&
                         !csk_diag_flag("CSK_GCN_GENERAL");
     // split-K (latency mode)
     if (ksplit > 1 && !sparse) CSK_FAIL("gcn_stage_splitk: split-K is built for the skeleton-sparse kernel (shared adjacency, <= 1/1/4 non-zeros per column)");
     p.ksplit = split_ranges(p.CinPad, c_in, ksplit, 8, &p.cper);
-    if (sparse && p.ksplit == 1) {     // slot-balanced 16x16x4 tiles where they pack the chip better (step16.hip; same sums)
+    *lds_out = lds; *sparse_out = sparse;
+    return 0;
+}
+
+// the launch of the slot-balanced 16x16x4 tiles (step16.hip; same sums) is tried for these
+static bool gcn16_candidate(const GcnParams &p, bool sparse) { return sparse && p.ksplit == 1; }
+
+static int gcn_stage_impl(const float *x, float *y, const float *w, const float *bias, const int32_t *ell_src,
+                          const float *ell_val, const int32_t *ell_cnt, int ell_w, int64_t adj_seg_stride,
+                          int adj_per_frame,
+                          int n_seg, int c_in, int c_out, int frames, int V, int64_t x_seg_stride,
+                          int64_t x_chan_stride, int64_t y_seg_stride, int64_t y_chan_stride, int res_mode,
+                          int ksplit, float *partial, void *stream) {
+    if (!x || !y || !w || !bias || !ell_src || !ell_val || !ell_cnt) CSK_FAIL("gcn_stage: null pointer");
+    GcnParams p;
+    size_t lds;
+    bool sparse;
+    if (const int rc = gcn_stage_setup(x, y, w, bias, ell_src, ell_val, ell_cnt, ell_w, adj_seg_stride, adj_per_frame, n_seg, c_in, c_out, frames,
+                                       V, x_seg_stride, x_chan_stride, y_seg_stride, y_chan_stride, res_mode, ksplit, partial, &p, &lds, &sparse))
+        return rc;
+    const bool big = (p.Mpad % 128) == 0;
+    const int MT = big ? 128 : 64, NT = 16384 / MT;
+    const int Q = frames * V;
+    dim3 grid(p.qtiles * p.mtiles * n_seg);
+    if (gcn16_candidate(p, sparse)) {     // slot-balanced 16x16x4 tiles where they pack the chip better (step16.hip; same sums)
         const int rc = csk_launch_gcn16(p, n_seg, stream);
         if (rc != -2) return rc;
     }
@@ -882,6 +906,20 @@ extern "C" int csk_gcn_stage_f32(const float *x, float *y, const float *w, const
                                  void *stream) {
     return gcn_stage_impl(x, y, w, bias, ell_src, ell_val, ell_cnt, ell_w, adj_seg_stride, adj_per_frame, n_seg, c_in, c_out, frames,
                           V, x_seg_stride, x_chan_stride, y_seg_stride, y_chan_stride, res_mode, 1, nullptr, stream);
+}
+
+extern "C" int csk_gcn_stage_f32_tile(const float *x, const float *y, const int32_t *ell_cnt, int ell_w, int64_t adj_seg_stride,
+                                      int adj_per_frame, int n_seg, int c_in, int c_out, int frames, int V, int64_t x_seg_stride,
+                                      int64_t x_chan_stride, int64_t y_seg_stride, int64_t y_chan_stride, int res_mode) {
+    if (!ell_cnt) CSK_FAIL("gcn_stage: null pointer");
+    GcnParams p;
+    size_t lds;
+    bool sparse;
+    if (const int rc = gcn_stage_setup(x, const_cast<float *>(y), nullptr, nullptr, nullptr, nullptr, ell_cnt, ell_w, adj_seg_stride, adj_per_frame,
+                                       n_seg, c_in, c_out, frames, V, x_seg_stride, x_chan_stride, y_seg_stride, y_chan_stride, res_mode, 1,
+                                       nullptr, &p, &lds, &sparse))
+        return rc;
+    return gcn16_candidate(p, sparse) ? csk_gcn16_tile(p, n_seg) : 0;
 }
 
 extern "C" int csk_gcn_stage_splitk_f32(const float *x, float *y, const float *w, const float *bias, const int32_t *ell_src,

@@ -53,3 +53,6 @@ int csk_launch_gcn_dense2(GcnParams p, int n_seg, void *stream);
 // step16.hip: the slot-balanced 16x16x4 tiles for skeleton-sparse adjacencies on 16-byte-aligned layouts; -2 when the shape is
 // not supported or the 32x32x2 kernels pack the chip as well (bitwise the same results either way)
 int csk_launch_gcn16(GcnParams p, int n_seg, void *stream);
+// the instantiation that launch runs, NB * 1000 + F * 100 + CONVRES * 10 of gcn16_kernel; 0 where it returns -2.  Host arithmetic:
+// of p.x / p.y only the alignment is read (csk_gcn_stage_f32_tile)
+int csk_gcn16_tile(const GcnParams &p, int n_seg);

@@ -367,23 +367,36 @@ __global__ void co_window_mean_kernel(const float *__restrict__ ring, float *__r
 // ------------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------------
+// What csk_tcn_step_f32 requires of the launch SHAPE (no pointer, no slot index): 0, or -1 with the message set.  x_res_slots is
+// read for a launch with a residual only.  Shared with csk_tcn_step_f32_tile.
+static int check_step_shape(int slots, int head_step, int n_emit, int x_res_slots, int out_slots, int c, int c_out, int64_t P, int k,
+                            int res_mode, int c_res, int ksplit) {
+    if (ksplit < 1 || ksplit > 32) CSK_FAIL("tcn_step: ksplit must be in [1, 32] and needs a partial-sum buffer");
+    if (c <= 0 || c_out <= 0 || P < 4 || (P & 3)) CSK_FAIL("tcn_step: bad dims (P must be a positive multiple of 4)");
+    if (k < 1 || k > 9 || slots < k) CSK_FAIL("tcn_step: bad k/slots/head");
+    if (n_emit < 1 || n_emit > 64 || head_step < 0 || out_slots < n_emit) CSK_FAIL("tcn_step: bad emission geometry");
+    if (slots < k - 1 + (n_emit - 1) * head_step + 1) CSK_FAIL("tcn_step: ring too shallow for %d emissions", n_emit);
+    if (P >= (1ll << 31) - 256) CSK_FAIL("tcn_step: P too large");
+    if (res_mode != CSK_RES_NONE) {
+        if (x_res_slots < 1) CSK_FAIL("tcn_step: bad residual ring geometry");
+        if (res_mode == CSK_RES_IDENTITY && c_res != c_out) CSK_FAIL("tcn_step: identity residual needs c_res == c_out");
+    }
+    return 0;
+}
+
 extern "C" int csk_tcn_step_f32(const float *ring, int slots, int head, int head_step, int n_emit, const float *w,
                                 const float *x_res, int x_res_slots, int x_res_slot0, int x_res_step,
                                 const float *w_res, const float *bias, float *out, int out_slots, int out_slot0,
                                 int c, int c_out, int64_t P, int k, int res_mode, int c_res, int relu, int ksplit,
                                 float *partial, void *stream) {
     if (!ring || !w || !bias || !out) CSK_FAIL("tcn_step: null pointer");
-    if (ksplit < 1 || ksplit > 32 || (ksplit > 1 && !partial)) CSK_FAIL("tcn_step: ksplit must be in [1, 32] and needs a partial-sum buffer");
-    if (c <= 0 || c_out <= 0 || P < 4 || (P & 3)) CSK_FAIL("tcn_step: bad dims (P must be a positive multiple of 4)");
-    if (k < 1 || k > 9 || slots < k || head < 0 || head >= slots) CSK_FAIL("tcn_step: bad k/slots/head");
-    if (n_emit < 1 || n_emit > 64 || head_step < 0 || out_slots < n_emit || out_slot0 < 0 || out_slot0 >= out_slots)
-        CSK_FAIL("tcn_step: bad emission geometry");
-    if (slots < k - 1 + (n_emit - 1) * head_step + 1) CSK_FAIL("tcn_step: ring too shallow for %d emissions", n_emit);
-    if (P >= (1ll << 31) - 256) CSK_FAIL("tcn_step: P too large");
+    if (res_mode != CSK_RES_NONE && !x_res) CSK_FAIL("tcn_step: residual requested without x_res");
+    if (const int rc = check_step_shape(slots, head_step, n_emit, x_res_slots, out_slots, c, c_out, P, k, res_mode, c_res, ksplit)) return rc;
+    if (ksplit > 1 && !partial) CSK_FAIL("tcn_step: ksplit must be in [1, 32] and needs a partial-sum buffer");
+    if (head < 0 || head >= slots) CSK_FAIL("tcn_step: bad k/slots/head");
+    if (out_slot0 < 0 || out_slot0 >= out_slots) CSK_FAIL("tcn_step: bad emission geometry");
     if (res_mode != CSK_RES_NONE) {
-        if (!x_res) CSK_FAIL("tcn_step: residual requested without x_res");
-        if (x_res_slots < 1 || x_res_slot0 < 0 || x_res_slot0 >= x_res_slots || x_res_step < 0) CSK_FAIL("tcn_step: bad residual ring geometry");
-        if (res_mode == CSK_RES_IDENTITY && c_res != c_out) CSK_FAIL("tcn_step: identity residual needs c_res == c_out");
+        if (x_res_slot0 < 0 || x_res_slot0 >= x_res_slots || x_res_step < 0) CSK_FAIL("tcn_step: bad residual ring geometry");
         if (res_mode == CSK_RES_CONV && !w_res) CSK_FAIL("tcn_step: conv residual without w_res");
     }
     if (((uintptr_t)ring | (uintptr_t)(x_res ? x_res : ring)) & 15) CSK_FAIL("tcn_step: state pointers must be 16-byte aligned");
@@ -440,6 +453,17 @@ extern "C" int csk_tcn_step_f32(const float *ring, int slots, int head, int head
         hipLaunchKernelGGL(step_reduce_kernel, dim3((unsigned)((work + 255) / 256), n_emit), dim3(256), 0, s, p);
     }
     return (int)hipGetLastError();
+}
+
+extern "C" int csk_tcn_step_f32_tile(int slots, int head_step, int n_emit, int x_res_slots, int out_slots, int c, int c_out, int64_t P,
+                                     int k, int res_mode, int c_res, int ksplit) {
+    if (const int rc = check_step_shape(slots, head_step, n_emit, x_res_slots, out_slots, c, c_out, P, k, res_mode, c_res, ksplit)) return rc;
+    // the launch parameters of csk_tcn_step_f32 without their pointers and slot indices, which the choice does not read
+    // (x_res_slots <= 0: no x_res, the one-slot stand-in)
+    StepParams p = step_params(nullptr, slots, 0, head_step, nullptr, nullptr, x_res_slots > 0 ? x_res_slots : 1, 0, head_step, nullptr,
+                               nullptr, nullptr, out_slots, 0, c, c_out, P, k, res_mode, c_res, 1);
+    p.ksplit = split_ranges(p.Cpad, c, ksplit, KC, &p.cper);
+    return csk_tcn_step16_tile(p, n_emit);
 }
 
 extern "C" int csk_co_spatial_pool_f32(const float *h, float *feat, int N, int C, int MV, int64_t P, void *stream) {

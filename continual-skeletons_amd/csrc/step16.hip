@@ -401,13 +401,10 @@ int launch_gcn16(GcnParams p, int n_seg, hipStream_t s) {
 }
 
 template <int NB, int E, int HS>
-int launch16(StepParams p, int n_emit, hipStream_t s) {
+int launch16(StepParams p, int n_emit, bool tail, hipStream_t s) {
     typedef G16<NB, E, HS> G;
     p.gx = (unsigned)((p.P + G::NP - 1) / G::NP); p.gy = (unsigned)(p.Mpad / 64); p.gz = (unsigned)(n_emit / E);
     if ((int64_t)p.gx * p.gy * p.gz >= (1ll << 31)) CSK_FAIL("tcn_step: grid too large");
-    // the fast instantiation walks Cpad (CresPad) channel rows: it is only for operands without padding rows -- a channel count
-    // that is a multiple of the chunk but not of CSK_CPAD (C = 4, 8: test shapes) would read up to 12 rows past the last ring slot
-    const bool tail = p.Cpad != p.C || (p.res_mode == CSK_RES_CONV && p.CresPad != p.Cres);
     void (*kern)(StepParams) = tail ? tcn_step16_kernel<NB, E, HS, true> : tcn_step16_kernel<NB, E, HS, false>;
     const size_t lds = (size_t)G::LDS_FLOATS * sizeof(float);
     if (const int e = csk_ensure_lds((const void *)kern, lds)) return e;
@@ -422,44 +419,66 @@ int launch16(StepParams p, int n_emit, hipStream_t s) {
 // a different fp32 summation order -- so WHICH family runs must not depend on the launch size (a stream's results must not
 // depend on how many streams share the slab, nor on how many frames a launch carries): every k = 9, unsplit launch whose
 // rings fit 32-bit byte offsets takes this family; only the tile WIDTH (NB) follows the launch shape.
-int csk_launch_tcn_step16(StepParams p, int n_emit, void *stream) {
-    if (p.K != 9 || p.ksplit != 1 || p.head_step < 1 || p.head_step > 2) return -2;
+// The instantiation tcn_step16_kernel<NB, E, HS, TAIL> of a launch as NB * 1000 + E * 100 + HS * 10 + TAIL, 0: not a launch of
+// this family.  The ONE copy of the rule: the launcher below switches on it, csk_tcn_step_f32_tile reports it.
+int csk_tcn_step16_tile(const StepParams &p, int n_emit) {
+    if (p.K != 9 || p.ksplit != 1 || p.head_step < 1 || p.head_step > 2) return 0;
     // 32-bit byte offsets inside the rings
     const int64_t ring_bytes = (int64_t)p.slots * p.C * p.P * 4, xres_bytes = (int64_t)p.xres_slots * p.Cres * p.P * 4;
     const int64_t out_bytes = (int64_t)p.out_slots * p.Cout * p.P * 4;
-    if (ring_bytes >= (1ll << 32) || xres_bytes >= (1ll << 32) || out_bytes >= (1ll << 32) || p.P < 8) return -2;
+    if (ring_bytes >= (1ll << 32) || xres_bytes >= (1ll << 32) || out_bytes >= (1ll << 32) || p.P < 8) return 0;
     const int E = p.head_step == 2 ? (n_emit % 2 == 0 ? 2 : 1) : (n_emit % 4 == 0 ? 4 : n_emit % 2 == 0 ? 2 : 1);
     const int HS = E > 1 ? p.head_step : 1;
     const int64_t mt = p.Mpad / 64;
     const int best_nb = pick_nb([&](int nb) { const int np = 16 * nb / E; return ((p.P + np - 1) / np) * mt * (n_emit / E); },
                                 [](int) { return true; });
+    // the fast instantiation walks Cpad (CresPad) channel rows: it is only for operands without padding rows -- a channel count
+    // that is a multiple of the chunk but not of CSK_CPAD (C = 4, 8: test shapes) would read up to 12 rows past the last ring slot
+    const bool tail = p.Cpad != p.C || (p.res_mode == CSK_RES_CONV && p.CresPad != p.Cres);
+    return best_nb * 1000 + E * 100 + HS * 10 + (tail ? 1 : 0);
+}
+
+int csk_launch_tcn_step16(StepParams p, int n_emit, void *stream) {
+    const int tile = csk_tcn_step16_tile(p, n_emit);
+    if (!tile) return -2;
+    const int best_nb = tile / 1000, E = tile / 100 % 10, HS = tile / 10 % 10;
+    const bool tail = tile % 10 != 0;
     hipStream_t s = (hipStream_t)stream;
-#define CSK_L16(NB_) (E == 4 ? launch16<NB_, 4, 1>(p, n_emit, s) : E == 2 ? (HS == 2 ? launch16<NB_, 2, 2>(p, n_emit, s) : launch16<NB_, 2, 1>(p, n_emit, s)) : launch16<NB_, 1, 1>(p, n_emit, s))
+#define CSK_L16(NB_) (E == 4 ? launch16<NB_, 4, 1>(p, n_emit, tail, s) : E == 2 ? (HS == 2 ? launch16<NB_, 2, 2>(p, n_emit, tail, s) : launch16<NB_, 2, 1>(p, n_emit, tail, s)) : launch16<NB_, 1, 1>(p, n_emit, tail, s))
     return best_nb == 25 ? CSK_L16(25) : CSK_L16(18);
 #undef CSK_L16
 }
 
 // Graph conv: bitwise the sums of gcn_stage_sparse2_kernel, so the choice IS a throughput policy of the launch shape: taken
 // where the cost model says the launch packs the chip better (CSK_GCN16=2 under CSK_DIAG=1: whenever the shape is supported).
-int csk_launch_gcn16(GcnParams p, int n_seg, void *stream) {
+// The instantiation gcn16_kernel<NB, F, CONVRES, 8> as NB * 1000 + F * 100 + CONVRES * 10, 0: the launch keeps the 32x32x2 tiles.
+// The ONE copy of the rule: the launcher below switches on it, csk_gcn_stage_f32_tile reports it.
+int csk_gcn16_tile(const GcnParams &p, int n_seg) {
     const int mode = csk_diag_int("CSK_GCN16");
-    if (mode == 1) return -2;
-    if (p.adj_seg_stride != 0 || p.ksplit != 1 || p.ell_cnt[0] > 1 || p.ell_cnt[1] > 1 || p.ell_cnt[2] > 4) return -2;
-    if ((p.x_seg_stride | p.x_chan_stride | p.y_seg_stride | p.y_chan_stride) & 3) return -2;
-    if (((uintptr_t)p.x | (uintptr_t)p.y) & 15) return -2;
+    if (mode == 1) return 0;
+    if (p.adj_seg_stride != 0 || p.ksplit != 1 || p.ell_cnt[0] > 1 || p.ell_cnt[1] > 1 || p.ell_cnt[2] > 4) return 0;
+    if ((p.x_seg_stride | p.x_chan_stride | p.y_seg_stride | p.y_chan_stride) & 3) return 0;
+    if (((uintptr_t)p.x | (uintptr_t)p.y) & 15) return 0;
     const int F = n_seg % 4 == 0 ? 4 : n_seg % 2 == 0 ? 2 : 1;
-    if ((int64_t)F * p.x_seg_stride * 4 >= (1ll << 32) || (int64_t)F * p.y_seg_stride * 4 >= (1ll << 32)) return -2;
+    if ((int64_t)F * p.x_seg_stride * 4 >= (1ll << 32) || (int64_t)F * p.y_seg_stride * 4 >= (1ll << 32)) return 0;
     const int Q = p.frames * p.V;
     const int64_t mt = p.Mpad / 64;
     const auto tiles = [&](int nb) { const int npg = 16 * nb / F; return (int64_t)((Q + npg - 1) / npg) * mt * (n_seg / F); };
     const int best_nb = pick_nb(tiles, [&](int nb) { return (16 * nb / F) % p.V == 0; });      // tiles hold whole skeletons
-    if (!best_nb) return -2;
+    if (!best_nb) return 0;
     if (mode != 2) {
         const bool big = (p.Mpad % 128) == 0;
         const int nt32 = big ? 128 : 256;
         const double c32 = cost_model((int64_t)((Q + nt32 - 1) / nt32) * (big ? p.Mpad / 128 : p.Mpad / 64) * n_seg, 256.0);
-        if (cost_model(tiles(best_nb), 16.0 * best_nb) >= 0.97 * c32) return -2;   // not clearly better: keep the 32x32x2 tiles
+        if (cost_model(tiles(best_nb), 16.0 * best_nb) >= 0.97 * c32) return 0;   // not clearly better: keep the 32x32x2 tiles
     }
+    return best_nb * 1000 + F * 100 + (p.R == 4 ? 10 : 0);
+}
+
+int csk_launch_gcn16(GcnParams p, int n_seg, void *stream) {
+    const int tile = csk_gcn16_tile(p, n_seg);
+    if (!tile) return -2;
+    const int best_nb = tile / 1000, F = tile / 100 % 10;
     hipStream_t s = (hipStream_t)stream;
 #define CSK_G16(NB_) (F == 4 ? launch_gcn16<NB_, 4>(p, n_seg, s) : F == 2 ? launch_gcn16<NB_, 2>(p, n_seg, s) : launch_gcn16<NB_, 1>(p, n_seg, s))
     return best_nb == 25 ? CSK_G16(25) : CSK_G16(18);

@@ -43,5 +43,8 @@ inline StepParams step_params(const float *ring, int slots, int head, int head_s
 // the 32x32x2 kernel walks 8; so does the stride-2 tcn_stage16_kernel), so it takes a launch by (k, ksplit, ring size) only,
 // never by the launch size.
 int csk_launch_tcn_step16(StepParams p, int n_emit, void *stream);
+// the instantiation that launch runs, NB * 1000 + E * 100 + HS * 10 + TAIL of tcn_step16_kernel; 0 where it returns -2.  Host
+// arithmetic on the shape fields of p only (csk_tcn_step_f32_tile)
+int csk_tcn_step16_tile(const StepParams &p, int n_emit);
 // fused stack of 64-channel blocks (csk_co_block_step_f32 / csk_co_stack_step_f32); -2: shape not supported
 int csk_launch_co_stack16(int n_blocks, const csk_co_block_args *blocks, int n_skel, int V, int64_t P, void *stream);

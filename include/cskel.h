@@ -83,6 +83,18 @@ int csk_gcn_stage_f32(const float *x, float *y, const float *w, const float *bia
                       int res_mode, void *stream);
 
 /*
+ * The tile family csk_gcn_stage_f32 picks for a launch: 0 = the 32x32x2 kernels (csrc/gcn.hip), else the instantiation of the
+ * slot-balanced 16x16x4 graph conv (csrc/step16.hip) as NB * 1000 + F * 100 + CONVRES * 10 -- NB column blocks of 16 positions
+ * per tile (25 or 18), F segments per tile (4, 2 or 1), CONVRES 1 for the conv gcn_residual.  Arguments as the stage's own; of
+ * x and y only the alignment is read, they are never dereferenced.  Host arithmetic only (no GPU); -1 on bad dims.  For tests
+ * and tools: results do not depend on the family (bitwise the same sums).
+ */
+int csk_gcn_stage_f32_tile(const float *x, const float *y, const int32_t *ell_cnt, int ell_w, int64_t adj_seg_stride,
+                           int adj_per_frame, int n_seg, int c_in, int c_out, int frames, int V,
+                           int64_t x_seg_stride, int64_t x_chan_stride, int64_t y_seg_stride, int64_t y_chan_stride,
+                           int res_mode);
+
+/*
  * The same stage with its K loop split over workgroups (latency mode: a handful of streams, where one workgroup per tile
  * would walk all 3 * c_in / 8 K-chunks alone -- 41 us at c_in = 256): the channel axis is cut into up to ksplit ranges
  * computed by separate workgroups into `partial` ([n_seg * ksplit][c_out][y_chan_stride] floats) and summed in split
@@ -321,6 +333,17 @@ int csk_tcn_step_f32(const float *ring, int slots, int head, int head_step, int 
                      const float *w_res, const float *bias, float *out, int out_slots, int out_slot0,
                      int c, int c_out, int64_t P, int k, int res_mode, int c_res, int relu, int ksplit, float *partial,
                      void *stream);
+
+/*
+ * The kernel csk_tcn_step_f32 picks for a launch shape: 0 = the 32x32x2 kernels of csrc/step.hip (split-K, k != 9, P < 8, a ring
+ * of 4 GB or more), else the instantiation of the slot-balanced 16x16x4 step (csrc/step16.hip) as
+ * NB * 1000 + E * 100 + HS * 10 + TAIL -- NB column blocks of 16 positions per tile (25 or 18), E emissions folded into a tile
+ * (4, 2 or 1), HS the head_step the tile is built for, TAIL 1 when a channel count is not whole CSK_CPAD blocks.  Arguments as
+ * the step's own; x_res_slots <= 0 stands for x_res == NULL.  Host arithmetic only (no GPU); -1 on bad dims.  For tests and
+ * tools: only NB follows the launch size, and an output's summation order does not depend on it.
+ */
+int csk_tcn_step_f32_tile(int slots, int head_step, int n_emit, int x_res_slots, int out_slots, int c, int c_out, int64_t P,
+                          int k, int res_mode, int c_res, int ksplit);
 
 /*
  * OPT-IN step precision "bf16x3" of csk_tcn_step_f32 (same reference method, models/base.py:307-334, 390-446; same rings,
