@@ -30,8 +30,9 @@ from .continual import (  # noqa: F401
 )
 from .agcn import AdaptiveGraphConvolution, AGcn, CoAdaptiveGraphConvolution, CoAGcn  # noqa: F401
 from .str import CoSTr, GcnUnitAttention, STr  # noqa: F401
-from . import fusion, modality, native, weights  # noqa: F401
+from . import fusion, modality, native, prenorm, weights  # noqa: F401
 from .modality import set_input_modality  # noqa: F401
+from .prenorm import pre_normalize_clip, set_pre_normalization  # noqa: F401
 from .weights import load_pretrained  # noqa: F401
 
 # names used by BASELINE.json:north_star
@@ -46,4 +47,5 @@ __all__ = [
     "AdaptiveGraphConvolution", "CoAdaptiveGraphConvolution", "AGcn", "CoAGcn", "GcnUnitAttention", "STr", "CoSTr",
     "init_weights", "zero", "unity",
     "native", "fusion", "set_precision", "set_clip_latency_mode", "modality", "set_input_modality",
+    "prenorm", "pre_normalize_clip", "set_pre_normalization",
 ]

@@ -115,6 +115,7 @@ class StreamReset:
             jobs += [self._ring_job(st.y, 0, st.y.shape[0]), self._ring_job(st.out, 0, st.out.shape[0])]
         jobs.append(self._pool_job(0, self.pool_size))
         jobs += self._modality_reset_jobs()        # a motion modality: the streams' next frame is a first frame (modality.py)
+        jobs += self._prenorm_reset_jobs()         # pre-normalisation: the next frame latches the rotations anew (prenorm.py)
         self._scrub(jobs, dev, len(idx))
         again = set(idx)
         for at, (members, _) in list(self._cohorts.items()):       # a stream reset again leaves its earlier cohort

@@ -33,6 +33,7 @@ from .blocks import GraphConvolution, SpatioTemporalBlock, TemporalConvolution, 
 from .co_plan import NativePlan
 from .co_reset import StreamReset
 from .modality import ContinualModality
+from .prenorm import ContinualPreNorm
 from .models import layer_table, per_layer
 
 MAX_CYCLE = native.CO_MAX_CYCLE
@@ -555,7 +556,7 @@ def co_geometry(c_in=3):
     return r, p, s
 
 
-class CoStGcn(NativePlan, StreamReset, ContinualModality, _Folded):
+class CoStGcn(NativePlan, StreamReset, ContinualPreNorm, ContinualModality, _Folded):
     """CoST-GCN: models/cost_gcn/cost_gcn.py:21-41 + CoModelBase (models/base.py:68-227) without the Ride shell.
 
     ``forward_step(x_t: (N, C, V, M))`` -> logits (N, classes) on the steps where the whole stack (10 blocks,
@@ -564,7 +565,8 @@ class CoStGcn(NativePlan, StreamReset, ContinualModality, _Folded):
     state_dict keys equal the reference's (``layers.layerK.0.1.gcn...``); a regular StGcn state_dict loads too
     (what ``map_state_dict`` does in the reference, base.py:200-224).  This class binds the state slab and steps on it; the
     native plan (co_plan.py: NativePlan), the per-stream reset (co_reset.py: StreamReset) and the input modality
-    (modality.py: ContinualModality -- bone / motion frames derived from the joint frames in front of every cycle) are base classes.
+    (modality.py: ContinualModality -- bone / motion frames derived from the joint frames in front of every cycle) are base classes,
+    and so is the pre-normalisation of raw joint frames (prenorm.py: ContinualPreNorm), which runs in front of the modality.
     """
 
     # False: drive every launch from Python (same kernels, same results).  Read on every cycle: both engines step on the one
@@ -657,6 +659,7 @@ class CoStGcn(NativePlan, StreamReset, ContinualModality, _Folded):
         self._flushed = False
         self._forget_resets()
         self._bind_modality(n, device)
+        self._bind_prenorm(n, device)
         self._build_plan(device)
 
     _frames = _counter(0, "input frames received")
@@ -692,17 +695,18 @@ class CoStGcn(NativePlan, StreamReset, ContinualModality, _Folded):
         self._n = None
 
     def state_bytes(self):
-        """Persistent continual state (input ring, per-block rings, pooling window; previous frame and flags of a motion modality)."""
+        """Persistent continual state (input ring, per-block rings, pooling window; previous frame and flags of a motion modality;
+        latched rotations and flags of the pre-normalisation)."""
         return (sum(blk._state.nbytes() for blk in self._blocks) + 4 * (self._xin0.numel() + self._pool_ring.numel())
-                + 4 * sum(t.numel() for t in self._modality_tensors()))
+                + 4 * sum(t.numel() for t in self._modality_tensors()) + self._prenorm_state_bytes())
 
     def scratch_bytes(self):
         """Transient scratch, not state: the split-K partial sums (shared by the blocks that split their K loop) and, for
         adaptive graph convs, the per-skeleton-frame adjacencies of a launch (shared by all blocks); with a bone / motion input
-        modality, the derived frames of a cycle."""
-        adj, mod = self.__dict__.get("_agcn_adj"), self._mod_scratch
+        modality, the derived frames of a cycle; with pre-normalisation, its normalised frames."""
+        adj, mod, pn = self.__dict__.get("_agcn_adj"), self._mod_scratch, self._pn_scratch
         return 4 * ((self._scratch.numel() if self._scratch is not None else 0) + (adj.numel() if adj is not None else 0)
-                    + (mod.numel() if mod is not None else 0))
+                    + (mod.numel() if mod is not None else 0) + (pn.numel() if pn is not None else 0))
 
     def clean_state(self):
         if self._n is not None:
@@ -711,6 +715,7 @@ class CoStGcn(NativePlan, StreamReset, ContinualModality, _Folded):
                 blk.clean_state()
             self._pool_ring.zero_()
             self._clean_modality()
+            self._clean_prenorm()
             self._set_counters([0] * 22)
             self._flushed = False
             self._forget_resets()
@@ -723,7 +728,8 @@ class CoStGcn(NativePlan, StreamReset, ContinualModality, _Folded):
         cross a multiple of the total stride, and what the not-yet-live blocks wrote for them is zeroed after its launches;
         ``peek``: the caller puts the counters back (one step, update_state=False) -- the next real step rewrites and scrubs
         the same slots, so a peek does neither.  The engines step on ``_derive_frames(frames)``: the frames themselves for
-        the joint modality, else the bone / motion frames of the pre-pass (a peek leaves its previous-frame state alone)."""
+        the joint modality, else the bone / motion frames of the pre-pass (a peek leaves its previous-frame state alone); with
+        pre-normalisation on, ``_prenorm_frames`` runs first and the modality derives from the normalised frames."""
         self._require_eval()
         frames = list(frames)
         if not 1 <= len(frames) <= self.max_cycle:
@@ -746,10 +752,10 @@ class CoStGcn(NativePlan, StreamReset, ContinualModality, _Folded):
                                "and advanced the blocks past the input frame count; call clean_state() before stepping on")
         engine = self._plan_cycle if self.use_native_plan and self.__dict__.get("_plan") else self._python_cycle
         if not self._cohorts or peek:              # nothing warms: the cycle is the one that runs without any reset
-            return engine(self._derive_frames(frames, update=not peek))
+            return engine(self._derive_frames(self._prenorm_frames(frames, update=not peek), update=not peek))
         self._check_cycle_while_warming(len(frames))
         before = self._counters()
-        res = engine(self._derive_frames(frames))
+        res = engine(self._derive_frames(self._prenorm_frames(frames)))
         self._scrub_cycle(before)
         return res
 
@@ -769,7 +775,7 @@ class CoStGcn(NativePlan, StreamReset, ContinualModality, _Folded):
 
     def _state_tensors(self):
         return ([self._xin0, self._pool_ring, self._pooled] + [t for blk in self._blocks for t in (blk._state.y, blk._state.out)]
-                + self._modality_tensors())
+                + self._modality_tensors() + self._prenorm_tensors())
 
     def _ensure_bound(self, x_t):
         native.require_device_f32(x_t, "CoStGcn frame")
@@ -915,7 +921,8 @@ class CoStGcn(NativePlan, StreamReset, ContinualModality, _Folded):
 
     def _clip_features(self, x):
         native.require_device_f32(x, "CoStGcn input")
-        x = self._derive_clip(x)           # bone / motion clip (forward difference, as the reference's files); joint: x itself
+        # pre-normalised joints (clip form; off: x itself), then the bone / motion clip (forward difference, as the reference's files)
+        x = self._derive_clip(self._prenorm_clip(x))
         n, c, t, v, m = x.shape
         ops = self._packed_ops(x.device)
         h = torch.empty((n * m, c, t, v), device=x.device, dtype=torch.float32)

@@ -11,6 +11,7 @@ import torch.nn as nn
 from . import fold, native
 from .blocks import SpatioTemporalBlock, _Folded, init_weights
 from .modality import InputModality
+from .prenorm import PreNorm
 
 
 def layer_table(c_in):
@@ -31,7 +32,7 @@ def per_layer(factory):
     return [factory] * 10
 
 
-class StGcn(InputModality, _Folded):
+class StGcn(PreNorm, InputModality, _Folded):
     def __init__(self, graph_A, input_shape=(3, 300, 25, 2), num_classes=60, GraphConv=None):
         """graph_A: (3, V, V) adjacency; input_shape = (C, T, V, M) as datasets/datasets.py:128-134.  ``GraphConv``: the
         graph-conv factory of every block, or a sequence of ten (one per layer; None = GraphConvolution) -- S-TR keeps the
@@ -72,7 +73,8 @@ class StGcn(InputModality, _Folded):
         return h
 
     def features(self, x):
-        h = self.input_norm(self._derive_clip(x))      # bone / motion clip first (modality.py); joint: x itself
+        # pre-normalised joints first (prenorm.py; off: x itself), then the bone / motion clip (modality.py; joint: x itself)
+        h = self.input_norm(self._derive_clip(self._prenorm_clip(x)))
         for i in range(len(self.layers)):
             h = self.layers[f"layer{i + 1}"](h)
         return h

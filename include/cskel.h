@@ -27,6 +27,8 @@
 extern "C" {
 #endif
 
+/* Stays 16 while entries are only added: csk_derive_modality_f32 / _frames_f32 and csk_prenorm_f32 / _frames_f32 are additive
+ * (no existing entry, struct or constant changed). */
 #define CSK_ABI_VERSION 16
 #define CSK_KC 8    /* channel-chunk of the K loop of the TCN kernels                                */
 #define CSK_CPAD 16 /* packed weights zero-pad C_in to a multiple of this                             */
@@ -478,6 +480,49 @@ int csk_derive_modality_f32(const float *x, float *out, int mode, const int32_t 
  */
 int csk_derive_modality_frames_f32(const float *const *frames, float *const *dst, int r, int mode, const int32_t *parents,
                                    float *prev, int32_t *has_prev, int update, int N, int C, int V, int M, void *stream);
+
+/*
+ * Pre-normalisation of raw joint frames (the reference runs it offline over whole datasets:
+ * datasets/data_preparation/preprocess.py:14-93 from ntu60_prep.py:179 / ntu120_prep.py:219; rotation.py:10-50).
+ * x (N, 3, T, V, M): C = 3 coordinate channels, persons m, joints v; the main body is m = 0, the centre joint is joint 1.
+ * Per sample, every frame t:
+ *   1. null mask   joint (t, v, m) is null iff (x0 + x1) + x2 == 0 in fp32; a null joint comes out as +0 in all channels
+ *   2. centre      c[t] = x[t, joint 1, person 0];  s1 = x - c[t]            (one fp32 rounding per channel, every person)
+ *   3. z-rotation  d = s1[0, zaxis1, 0] - s1[0, zaxis0, 0]                   (fp32, frame 0, person 0; s1 of a null joint is 0)
+ *                  axis = d x (0,0,1), angle = acos(clip(d/|d| . (0,0,1))), Rz = the quaternion form of rotation.py:10-29 with
+ *                  its identity shortcuts (sum|axis| < 1e-6, |angle| < 1e-6; angle = 0 for sum|d| < 1e-6) -- all in fp64
+ *                  s2 = fp32(Rz . fp64(s1))                                  (three-term fp64 dot, one rounding to fp32)
+ *   4. x-rotation  the same from d' = s2[0, xaxis0, 0] - s2[0, xaxis1, 0] against (1,0,0):  out = fp32(Rx . fp64(s2))
+ * The rounding to fp32 between the two rotations is part of the definition (the reference stores each stage into its fp32
+ * array).  The reference takes the unit vector d/|d| in fp32, so it is matched to ~1 fp32 ulp, not bit for bit.
+ * Deliberately NOT reproduced:
+ *   - the reference's first step (preprocess.py:18-39) pads null frames by compacting and repeating earlier frames; it looks
+ *     ahead, which a causal stream cannot do, and the clip form leaves it out too so that clip and step form agree;
+ *   - the reference's `== 0` tests on whole-person / whole-frame sums also fire when non-zero coordinates cancel exactly;
+ *     here only all-zero data is skipped, where the result is the same up to the sign of zero;
+ *   - a sample / stream whose first frame has an empty main body latches the identity (reset the stream when a body appears).
+ * The reference's defaults are zaxis = (0, 1), xaxis = (8, 4).  out: same shape as x, another buffer.  One launch, no
+ * allocation, no synchronisation, no scratch, graph-capture safe.
+ * Returns -1 for a null pointer, out == x or a dim < 1; -2 for V < 2 or a joint index outside [0, V) (csk_last_error set,
+ * nothing launched).
+ */
+int csk_prenorm_f32(const float *x, float *out, int N, int T, int V, int M, int zaxis0, int zaxis1, int xaxis0, int xaxis1,
+                    void *stream);
+
+/*
+ * The same for the r = 1..8 frames of a launch cycle of the continual path in one launch.  The centring is per frame and so
+ * causal; the two matrices are latched from a stream's FIRST frame: rot (N, 18) fp64 holds a stream's Rz then Rx (row-major),
+ * has_rot (N,) int32 says whether it does (both on the device).  frames[i] (N, 3, V, M) -> dst[i], same shape; frames / dst
+ * are HOST arrays of device pointers, as for csk_derive_modality_frames_f32; every dst[i] is a buffer of its own.  A stream
+ * with has_rot == 0 computes both matrices from frames[0] -- exactly as csk_prenorm_f32 does from frame 0 of a clip, so the
+ * two forms agree bit for bit -- and uses them for all r frames.  update != 0: the launch then stores them into rot and sets
+ * has_rot -- behind a workgroup barrier, by the workgroup that read them (a workgroup owns whole streams); update == 0
+ * leaves both bitwise untouched (forward_step(update_state=False)).
+ * Returns -1 for a null pointer (frames, dst, a frame, rot, has_rot), a dim < 1 or a dst that is a source frame; -2 for r
+ * outside 1..8, V < 2 or a joint index outside [0, V) (csk_last_error set, nothing launched).
+ */
+int csk_prenorm_frames_f32(const float *const *frames, float *const *dst, int r, double *rot, int32_t *has_rot, int update, int N,
+                           int V, int M, int zaxis0, int zaxis1, int xaxis0, int xaxis1, void *stream);
 
 /*
  * Multi-stream logit fusion + top-k support, scripts/multi_stream_eval.py:33-60: fused = left fold of add
