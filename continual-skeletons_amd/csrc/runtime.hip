@@ -45,7 +45,8 @@ extern "C" const char *csk_last_error(void) { return g_err; }
 // the same result, for A/B runs and as references in the tests:
 //   CSK_TCN16=1 / =2   the clip temporal conv never / wherever supported on the 16x16x4 family (tcn16.hip)
 //   CSK_GCN16=1 / =2   the graph conv never / wherever supported on the 16x16x4 family (step16.hip)
-//   CSK_TCN_WINO=1     the direct temporal conv instead of the Winograd kernel (tcn_wino.hip)
+//   CSK_TCN_WINO=1     the direct temporal conv instead of the Winograd kernel (tcn_wino.hip); =2 / =3 the Winograd kernel in
+//                      its wide / tall workgroup shape wherever the layer allows both
 //   CSK_GCN_GENERAL=1  the general (dense-capable) GCN kernel instead of the skeleton-sparse one (gcn.hip)
 static const bool g_diag = getenv("CSK_DIAG") != nullptr;
 bool csk_diag_flag(const char *name) { return g_diag && getenv(name) != nullptr; }

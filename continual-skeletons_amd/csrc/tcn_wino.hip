@@ -15,6 +15,12 @@
 // activation chunk in LDS serves the 12 (group, point) products; the transform is 4 VALU ops per 8 MFMAs.
 // Tiling: 256 threads = 4 waves, workgroup tile 64 output channels x 128 pair columns; a wave owns all 64 channels x 32 pair
 // columns per point (2 x 1 MFMA 32x32x2 accumulators per point, 8 in all = 128 registers), two workgroups per CU.
+// Second workgroup shape (MW = 2, "tall"): 128 output channels x 64 pair columns, waves 2 x 2 with the same wave tile and the
+// same MFMA order per accumulator element, so both shapes give the same bits.  Tiles do not cross sequences, so a sequence of
+// 950 pair columns (T = 75, V = 25) issues 1024 columns in wide tiles and 960 in tall ones; the host takes per layer the shape
+// that measures faster (wino_pick_mw: stride 2 the tall one, stride 1 the tall one where it saves 1/16 of the columns; the wide
+// one where c_out % 128 != 0).  Tall: 12 (13) weight rows x 8 x 128 staged per chunk, 48 (52) prefetch registers per thread,
+// 255 VGPRs, 60.5 KB (70 KB stride 2) LDS at V = 25.
 // K loop: 8-channel chunks as in tcn_stage_kernel (tcn.hip), the next chunk's loads trickled in three thirds in front of the
 // three group segments.  The weights stream from the host-transformed image, the staging types are those of mfma_core.h.
 // T odd: the last pair's second frame (t = T) is computed from zero padding and not stored.
@@ -33,18 +39,23 @@
 //           chunks over x after the main loop, a 1-tap group with d2 := d1: acc0 += wres (d0 - d1), acc1 += wres d1 (d0 = x[4 j],
 //           d1 = x[4 j + 2]), which the output transform turns into out(2 j) += wres d0, out(2 j + 1) += wres d1.
 //   weights (host, fold.pack_conv_weight_wino_s2): 13 rows E0 (4), E1 (3), O0 (3), O1 (3); the residual streams the direct w_res.
+#include <type_traits>
+
 #include "mfma_core.h"
 #include "tcn_params.h"
 
 namespace {
 
-constexpr int WMT = 64;        // output channels per workgroup tile
-constexpr int WNT = 128;       // pair columns per workgroup tile (32 per wave)
+constexpr int WMT = 64;        // output channels per wave, and per workgroup tile of the wide shape
+constexpr int WNT = 128;       // pair columns per workgroup tile of the wide shape (32 per wave)
 constexpr int WTAPS = 12;      // (group, point) products per channel
+// Workgroup shapes, MW = waves along the channels: MW = 1 wide, 64 channels x 128 pair columns (waves 1 x 4); MW = 2 tall, 128
+// channels x 64 pair columns (waves 2 x 2: wave w owns channel half w / 2, column half w % 2).  A wave's tile and code are the
+// same in both, so both give the same bits; the host picks by layer (wino_pick_mw).
 
 // LDS row of one staged channel: the raw frames 2 ja - 4 .. 2 jb + 5 of a tile whose pair columns span pairs ja .. jb
-template <int VT>
-constexpr int wino_ldb() { return ((2 * ((WNT + VT - 2) / VT) + 10) * VT + 3) / 4 * 4; }
+template <int VT, int MW = 1>
+constexpr int wino_ldb() { return ((2 * ((WNT / MW + VT - 2) / VT) + 10) * VT + 3) / 4 * 4; }
 
 // Weight staging of a 12-tap chunk of the 64-row tile: 12 * KC * 16 = 1536 f32x4 = 6 per thread; slot u of a thread is tap
 // 2 u + tid / 128, channel row (tid / 16) % 8, rows 4 (tid % 16) .. -- the offsets of the slots differ by wave-uniform constants
@@ -64,26 +75,66 @@ struct WStage12x64 {
 #pragma unroll
         for (int u = 0; u < 6; ++u) issue_slot(u, chunk_base);
     }
+    // the part of the next chunk's loads issued in front of group segment G
+    template <int G>
+    __device__ __forceinline__ void issue_part(const float *__restrict__ chunk_base) {
+        issue_slot(2 * G, chunk_base);
+        issue_slot(2 * G + 1, chunk_base);
+    }
     __device__ __forceinline__ void commit(float *__restrict__ Wl) const {
 #pragma unroll
         for (int u = 0; u < 6; ++u) *reinterpret_cast<f32x4 *>(Wl + u * (NTHREADS * 4) + loff0) = v[u];
     }
 };
 
+// Weight staging of an NT-row chunk of the 128-row tile: NT * KC * 32 f32x4 = NT per thread; slot u of a thread is image row u,
+// channel row tid / 32, rows 4 (tid % 32) .. (the layout of WStage9x128 in mfma_core.h).  issue_part<G>: the rows of group G
+// (four groups of 4, 3, 3, 3 rows for NT = 13, three of 4 for NT = 12).
+template <int NT>
+struct WStageNx128 {
+    unsigned goff0, loff0, gstride;
+    f32x4 v[NT];
+    __device__ __forceinline__ void setup(int Cpad, int Mpad, int tid) {
+        goff0 = 4u * (unsigned)((tid >> 5) * Mpad + (tid & 31) * 4);          // bytes
+        loff0 = (unsigned)(tid * 4);
+        gstride = (unsigned)(Cpad * Mpad);
+    }
+    // wave-uniform row base + one 32-bit per-lane byte offset (ld_lane in mfma_core.h): NT 64-bit per-lane addresses would
+    // not fit the register budget
+    __device__ __forceinline__ void issue_slot(int u, const float *__restrict__ chunk_base) {
+        v[u] = *reinterpret_cast<const f32x4 *>(reinterpret_cast<const char *>(chunk_base + (size_t)u * gstride) + goff0);
+    }
+    __device__ __forceinline__ void issue(const float *__restrict__ chunk_base) {
+#pragma unroll
+        for (int u = 0; u < NT; ++u) issue_slot(u, chunk_base);
+    }
+    template <int G>
+    __device__ __forceinline__ void issue_part(const float *__restrict__ chunk_base) {
+        constexpr int lo = NT == 13 ? (G == 0 ? 0 : 3 * G + 1) : 4 * G, hi = NT == 13 ? 3 * G + 4 : 4 * G + 4;
+#pragma unroll
+        for (int u = lo; u < hi; ++u) issue_slot(u, chunk_base);
+    }
+    __device__ __forceinline__ void commit(float *__restrict__ Wl) const {
+#pragma unroll
+        for (int u = 0; u < NT; ++u) *reinterpret_cast<f32x4 *>(Wl + u * (KC * 128) + loff0) = v[u];
+    }
+};
+
 // One group segment of a chunk for one wave: acc[i][mi] += U[4 g + i][kk][rows mi] x B_{g,i}[kk][this lane's column]
-template <int VT, int G>
+// (Wl: the staged weights at this wave's first row; MT = rows of the staged tile)
+template <int VT, int G, int MW>
 __device__ __forceinline__ void wino_group(const float *__restrict__ Wl, const float *__restrict__ Bl, int off, int l31, int kh,
                                            f32x16 (&acc)[4][2]) {
-    constexpr int LDB = wino_ldb<VT>();
+    constexpr int LDB = wino_ldb<VT, MW>(), MT = WMT * MW;
     const float *br = Bl + kh * LDB + off + 3 * G * VT;
-    const float *wr = Wl + 4 * G * (KC * WMT) + kh * WMT + l31;
+    const float *wr = Wl + 4 * G * (KC * MT) + kh * MT + l31;
 #pragma unroll
     for (int s = 0; s < KC / 2; ++s) {
         const float d0 = br[2 * s * LDB], d1 = br[2 * s * LDB + VT], d2 = br[2 * s * LDB + 2 * VT], d3 = br[2 * s * LDB + 3 * VT];
         const float b[4] = {d0 - d2, d1 + d2, d2 - d1, d1 - d3};
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const float a0 = wr[i * (KC * WMT) + 2 * s * WMT], a1 = wr[i * (KC * WMT) + 2 * s * WMT + 32];
+            const float a0 = wr[i * (KC * MT) + 2 * s * MT], a1 = wr[i * (KC * MT) + 2 * s * MT + 32];
             acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b[i], acc[i][0], 0, 0, 0);
             acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b[i], acc[i][1], 0, 0, 0);
         }
@@ -92,13 +143,13 @@ __device__ __forceinline__ void wino_group(const float *__restrict__ Wl, const f
 
 // ---- epilogue: output transform, + bias (+ identity residual, RES), ReLU.  C/D map: column = lane & 31 (this lane's pair column),
 // row = (g & 3) + 8 (g >> 2) + 4 (lane >> 5).  Row base pointers are wave-uniform (64-bit); a lane adds one 32-bit byte offset
-// (4 kh rows + its position; T V < 2^26 keeps it below 2^32).  Every tile has all 64 rows (c_out % 64 == 0, host gate).
-// p.Tout = output frames; (jc, vc) = this lane's pair column.
+// (4 kh rows + its position; T V < 2^26 keeps it below 2^32).  Every wave has all 64 rows (c_out a multiple of the tile's rows,
+// host gate).  p.Tout = output frames; m0 = the wave's first row, wn = its column quarter / half; (jc, vc) = this lane's pair column.
 template <int VT, bool RES>
 __device__ __forceinline__ void wino_epilogue(const TcnParams &p, const f32x16 (&acc)[4][2], int m0, int q0, int qend, int seg,
-                                              int wave, int l31, int kh, int jc, int vc) {
+                                              int wn, int l31, int kh, int jc, int vc) {
     const int T = p.Tout, TV = T * VT;
-    const bool qv = q0 + wave * 32 + l31 < qend;
+    const bool qv = q0 + wn * 32 + l31 < qend;
     const bool odd_ok = 2 * jc + 1 < T;                              // the pair's second frame exists (T odd: not the last pair)
     const unsigned p0 = (unsigned)(2 * jc * VT + vc);
     const unsigned b0 = 4u * (4u * (unsigned)kh * (unsigned)TV + p0);
@@ -140,26 +191,27 @@ __device__ __forceinline__ void wino_epilogue(const TcnParams &p, const f32x16 (
 }  // namespace
 
 // p.Tout = T (frames in and out), p.nt = pair columns per segment ((T + 1) / 2 * V), p.w = the transformed weight image
-template <int VT, bool RES = true>
+template <int VT, bool RES = true, int MW = 1>
 __global__ __launch_bounds__(NTHREADS, 2) void tcn_stage_wino_kernel(const TcnParams p) {
-    constexpr int LDB = wino_ldb<VT>();
+    constexpr int LDB = wino_ldb<VT, MW>(), MT = WMT * MW, NT = WNT / MW;
     constexpr int NJ = (LDB + 63) / 64;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *Wl = smem;
-    float *Bl = smem + WTAPS * KC * WMT;
+    float *Bl = smem + WTAPS * KC * MT;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, kh = lane >> 5;
+    const int wm = MW == 2 ? wave >> 1 : 0, wn = MW == 2 ? wave & 1 : wave;     // this wave's channel half / column part
     // work item -> (m-tile fastest: shares the activation tile; then column tile; then segment)
     const unsigned wid = xcd_contiguous_id(blockIdx.x, gridDim.x);
-    const int m0 = (int)(wid % p.mtiles) * WMT, q0 = (int)((wid / p.mtiles) % p.qtiles) * WNT;
+    const int m0 = (int)(wid % p.mtiles) * MT, q0 = (int)((wid / p.mtiles) % p.qtiles) * NT;
     const int seg = (int)(wid / (p.mtiles * p.qtiles));
     const int T = p.Tout, TV = T * VT, QP = p.nt;
-    const int qend = min(q0 + WNT, QP);
+    const int qend = min(q0 + NT, QP);
     const int ja = div_magic(q0, p.vmagic), jb = div_magic(qend - 1, p.vmagic);
 
     // this lane's pair column (clamped into the tile; lanes past its end compute a copy of the last column and store nothing)
-    const int qc = min(q0 + wave * 32 + l31, qend - 1);
+    const int qc = min(q0 + wn * 32 + l31, qend - 1);
     const int jc = div_magic(qc, p.vmagic), vc = qc - jc * VT;
     const int off = 2 * (jc - ja) * VT + vc;
 
@@ -177,7 +229,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void tcn_stage_wino_kernel(const TcnPa
         const int64_t cs = (int64_t)TV;
         const float *seg_base = p.y + (int64_t)seg * p.C * cs;       // 64-bit segment base; 32-bit offsets inside it
         const float *wbase = p.w + m0;
-        WStage12x64 ws;
+        const float *Ww = Wl + wm * WMT;                             // this wave's rows of the staged weights
+        std::conditional_t<MW == 2, WStageNx128<WTAPS>, WStage12x64> ws;
         ws.setup(p.Cpad, p.Mpad, tid);
         auto kloop = [&](auto &bx) {
             ws.issue(wbase);
@@ -189,32 +242,29 @@ __global__ __launch_bounds__(NTHREADS, 2) void tcn_stage_wino_kernel(const TcnPa
                 __syncthreads();
                 const float *wnext = wbase + (size_t)(c0 + KC) * p.Mpad;
                 const int cn = c0 + KC;
-                ws.issue_slot(0, wnext);
-                ws.issue_slot(1, wnext);
+                ws.template issue_part<0>(wnext);
                 bx.template issue_third<0>(seg_base, p.C, cs, cn, wave);
                 __builtin_amdgcn_s_setprio(1);
-                wino_group<VT, 0>(Wl, Bl, off, l31, kh, acc);
+                wino_group<VT, 0, MW>(Ww, Bl, off, l31, kh, acc);
                 __builtin_amdgcn_s_setprio(0);
-                ws.issue_slot(2, wnext);
-                ws.issue_slot(3, wnext);
+                ws.template issue_part<1>(wnext);
                 bx.template issue_third<1>(seg_base, p.C, cs, cn, wave);
                 __builtin_amdgcn_s_setprio(1);
-                wino_group<VT, 1>(Wl, Bl, off, l31, kh, acc);
+                wino_group<VT, 1, MW>(Ww, Bl, off, l31, kh, acc);
                 __builtin_amdgcn_s_setprio(0);
-                ws.issue_slot(4, wnext);
-                ws.issue_slot(5, wnext);
+                ws.template issue_part<2>(wnext);
                 bx.template issue_third<2>(seg_base, p.C, cs, cn, wave);
                 __builtin_amdgcn_s_setprio(1);
-                wino_group<VT, 2>(Wl, Bl, off, l31, kh, acc);
+                wino_group<VT, 2, MW>(Ww, Bl, off, l31, kh, acc);
                 __builtin_amdgcn_s_setprio(0);
             }
             __syncthreads();                         // peeled last chunk
             ws.commit(Wl);
             bx.commit(Bl, LDB, wave);
             __syncthreads();
-            wino_group<VT, 0>(Wl, Bl, off, l31, kh, acc);
-            wino_group<VT, 1>(Wl, Bl, off, l31, kh, acc);
-            wino_group<VT, 2>(Wl, Bl, off, l31, kh, acc);
+            wino_group<VT, 0, MW>(Ww, Bl, off, l31, kh, acc);
+            wino_group<VT, 1, MW>(Ww, Bl, off, l31, kh, acc);
+            wino_group<VT, 2, MW>(Ww, Bl, off, l31, kh, acc);
         };
         // tiles whose staged span lies inside the sequence: 16-byte staging; the others (zero padding at either end) element-wise
         const bool interior = fa >= 0 && fa * VT + 4 * ((span + 3) / 4) <= TV;     // uniform
@@ -229,7 +279,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void tcn_stage_wino_kernel(const TcnPa
         }
     }
 
-    wino_epilogue<VT, RES>(p, acc, m0, q0, qend, seg, wave, l31, kh, jc, vc);
+    wino_epilogue<VT, RES>(p, acc, m0 + wm * WMT, q0, qend, seg, wn, l31, kh, jc, vc);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -240,8 +290,8 @@ namespace {
 constexpr int W2TAPS = 13;     // (group, point) products per channel: E0 4, E1 3, O0 3, O1 3
 
 // LDS row of one staged channel: the raw frames 4 ja - 4 .. 4 jb + 6 of a tile whose pair columns span pairs ja .. jb
-template <int VT>
-constexpr int wino2_ldb() { return ((4 * ((WNT + VT - 2) / VT) + 11) * VT + 3) / 4 * 4; }
+template <int VT, int MW = 1>
+constexpr int wino2_ldb() { return ((4 * ((WNT / MW + VT - 2) / VT) + 11) * VT + 3) / 4 * 4; }
 
 // Weight staging of a 13-row chunk of the 64-row tile: 13 * KC * 16 = 1664 f32x4 = 6.5 per thread; slot u of a thread is image
 // row 2 u + tid / 128 (WStage12x64); the upper half of the threads has no slot 6 and repeats its slot 5 (same value to the
@@ -262,6 +312,15 @@ struct WStage13x64 {
     __device__ __forceinline__ void issue(const float *__restrict__ chunk_base) {
 #pragma unroll
         for (int u = 0; u < 7; ++u) issue_slot(u, chunk_base);
+    }
+    template <int G>
+    __device__ __forceinline__ void issue_part(const float *__restrict__ chunk_base) {
+        if (G < 3) {
+            issue_slot(2 * G, chunk_base);
+            issue_slot(2 * G + 1, chunk_base);
+        } else {
+            issue_slot(6, chunk_base);
+        }
     }
     __device__ __forceinline__ void commit(float *__restrict__ Wl) const {
 #pragma unroll
@@ -285,14 +344,84 @@ struct WStageRes64 {
     __device__ __forceinline__ void commit(float *__restrict__ Wl) const { *reinterpret_cast<f32x4 *>(Wl + loff0) = v; }
 };
 
+// The same for the 128-row tile: 256 f32x4, one per thread (channel row tid / 32, rows 4 (tid % 32) ..)
+struct WStageRes128 {
+    unsigned goff0, loff0;
+    f32x4 v;
+    __device__ __forceinline__ void setup(int Mpad, int tid) {
+        goff0 = (unsigned)((tid >> 5) * Mpad + (tid & 31) * 4);
+        loff0 = (unsigned)(tid * 4);
+    }
+    __device__ __forceinline__ void issue(const float *__restrict__ chunk_base) {
+        v = *reinterpret_cast<const f32x4 *>(chunk_base + goff0);
+    }
+    __device__ __forceinline__ void commit(float *__restrict__ Wl) const { *reinterpret_cast<f32x4 *>(Wl + loff0) = v; }
+};
+
+// BStage4 (mfma_core.h) for the tall shape, whose weight stage holds 13 registers-of-four per thread: a row of LDB floats as NV
+// whole 16-byte sweeps (256 floats each) and, where the rest is short, NS 4-byte sweeps (64 floats each) in place of one more
+// 16-byte sweep that three quarters of the lanes would only repeat.  One offset per sweep serves the global and the LDS side
+// (the tile's first position goes into the wave-uniform row base).
+template <int LDB>
+struct BStage4Tail {
+    static constexpr int RPW = KC / (NTHREADS / 64);   // rows per wave
+    static constexpr int REST = LDB % 256;
+    static constexpr int NV = LDB / 256 + (REST > 128 ? 1 : 0), NS = REST > 128 ? 0 : (REST + 63) / 64;
+    static_assert(NV >= 1 && NV <= 2 && NS <= 2, "issue_third: 16-byte sweeps with thirds 0 and 1, 4-byte sweeps with third 2");
+    unsigned off4[NV], off1[NS > 0 ? NS : 1];
+    int pbase_;
+    f32x4 v[RPW][NV];
+    float t[RPW][NS > 0 ? NS : 1];
+    __device__ __forceinline__ void setup(int pbase, int span, int lane) {
+        const int nvec = (span + 3) / 4;
+        pbase_ = pbase;
+#pragma unroll
+        for (int u = 0; u < NV; ++u) off4[u] = (unsigned)(4 * min(u * 64 + lane, nvec - 1));
+#pragma unroll
+        for (int u = 0; u < NS; ++u) off1[u] = (unsigned)min(NV * 256 + u * 64 + lane, span - 1);
+    }
+    __device__ __forceinline__ const float *row(const float *__restrict__ seg_base, int C, int64_t chan_stride, int c0, int wave,
+                                                int rr) const {
+        const int c = min(c0 + wave + rr * (NTHREADS / 64), C - 1);         // clamped: padding channels carry zero weights
+        return seg_base + (int64_t)c * chan_stride + pbase_;
+    }
+    template <int G>
+    __device__ __forceinline__ void issue_third(const float *__restrict__ seg_base, int C, int64_t chan_stride, int c0, int wave) {
+#pragma unroll
+        for (int rr = 0; rr < RPW; ++rr) {
+            const float *src = row(seg_base, C, chan_stride, c0, wave, rr);
+            if (G < NV) v[rr][G < NV ? G : 0] = *reinterpret_cast<const f32x4u *>(src + off4[G < NV ? G : 0]);
+            if (G == 2) {
+#pragma unroll
+                for (int u = 0; u < NS; ++u) t[rr][u] = src[off1[u]];
+            }
+        }
+    }
+    __device__ __forceinline__ void issue(const float *__restrict__ seg_base, int C, int64_t chan_stride, int c0, int wave) {
+        issue_third<0>(seg_base, C, chan_stride, c0, wave);
+        issue_third<1>(seg_base, C, chan_stride, c0, wave);
+        issue_third<2>(seg_base, C, chan_stride, c0, wave);
+    }
+    __device__ __forceinline__ void commit(float *__restrict__ Bl, int ldb, int wave) const {
+#pragma unroll
+        for (int rr = 0; rr < RPW; ++rr) {
+            float *dst = Bl + (wave + rr * (NTHREADS / 64)) * ldb;
+#pragma unroll
+            for (int u = 0; u < NV; ++u) *reinterpret_cast<f32x4 *>(dst + off4[u]) = v[rr][u];
+#pragma unroll
+            for (int u = 0; u < NS; ++u) dst[off1[u]] = t[rr][u];
+        }
+    }
+};
+
 // One group segment of a chunk for one wave: image rows ROW0 .. ROW0 + NP - 1, phase samples d_i at raw frame F + 2 i of the
 // lane's column; NP = 3: the group's third tap is zero -- no point-inf product, d3 not read
-template <int VT, int ROW0, int F, int NP>
+template <int VT, int ROW0, int F, int NP, int MW>
 __device__ __forceinline__ void wino2_group(const float *__restrict__ Wl, const float *__restrict__ Bl, int off, int l31, int kh,
                                             f32x16 (&acc)[4][2]) {
-    constexpr int LDB = wino2_ldb<VT>();
+    constexpr int LDB = wino2_ldb<VT, MW>(), MT = WMT * MW;
     const float *br = Bl + kh * LDB + off + F * VT;
-    const float *wr = Wl + ROW0 * (KC * WMT) + kh * WMT + l31;
+    const float *wr = Wl + ROW0 * (KC * MT) + kh * MT + l31;
 #pragma unroll
     for (int s = 0; s < KC / 2; ++s) {
         const float d0 = br[2 * s * LDB], d1 = br[2 * s * LDB + 2 * VT], d2 = br[2 * s * LDB + 4 * VT];
@@ -300,7 +429,7 @@ __device__ __forceinline__ void wino2_group(const float *__restrict__ Wl, const 
         const float b[4] = {d0 - d2, d1 + d2, d2 - d1, d1 - d3};
 #pragma unroll
         for (int i = 0; i < NP; ++i) {
-            const float a0 = wr[i * (KC * WMT) + 2 * s * WMT], a1 = wr[i * (KC * WMT) + 2 * s * WMT + 32];
+            const float a0 = wr[i * (KC * MT) + 2 * s * MT], a1 = wr[i * (KC * MT) + 2 * s * MT + 32];
             acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b[i], acc[i][0], 0, 0, 0);
             acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b[i], acc[i][1], 0, 0, 0);
         }
@@ -308,16 +437,16 @@ __device__ __forceinline__ void wino2_group(const float *__restrict__ Wl, const 
 }
 
 // One residual chunk: the staged row starts at raw frame 4 ja of x; d0 = x[4 j], d1 = x[4 j + 2]
-template <int VT>
+template <int VT, int MW>
 __device__ __forceinline__ void wino2_res_chunk(const float *__restrict__ Wl, const float *__restrict__ Bl, int off, int l31, int kh,
                                                 f32x16 (&acc)[4][2]) {
-    constexpr int LDB = wino2_ldb<VT>();
+    constexpr int LDB = wino2_ldb<VT, MW>(), MT = WMT * MW;
     const float *br = Bl + kh * LDB + off;
-    const float *wr = Wl + kh * WMT + l31;
+    const float *wr = Wl + kh * MT + l31;
 #pragma unroll
     for (int s = 0; s < KC / 2; ++s) {
         const float d0 = br[2 * s * LDB], d1 = br[2 * s * LDB + 2 * VT];
-        const float a0 = wr[2 * s * WMT], a1 = wr[2 * s * WMT + 32];
+        const float a0 = wr[2 * s * MT], a1 = wr[2 * s * MT + 32];
         const float b0 = d0 - d1;
         acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
         acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[0][1], 0, 0, 0);
@@ -330,26 +459,28 @@ __device__ __forceinline__ void wino2_res_chunk(const float *__restrict__ Wl, co
 
 // p.Tin = input frames, p.Tout = output frames ((Tin - 1) / 2 + 1), p.nt = pair columns per segment ((Tout + 1) / 2 * V),
 // p.w = the 13-row image, p.wres / p.xres = direct residual image and block input (RESCONV) with p.Tres == p.Tin
-template <int VT, bool RESCONV>
+template <int VT, bool RESCONV, int MW = 1>
 __global__ __launch_bounds__(NTHREADS, 2) void tcn_stage_wino_s2_kernel(const TcnParams p) {
-    constexpr int LDB = wino2_ldb<VT>();
+    constexpr int LDB = wino2_ldb<VT, MW>(), MT = WMT * MW, NT = WNT / MW;
     constexpr int NJ = (LDB + 63) / 64;
-    constexpr int NJR = ((4 * ((WNT + VT - 2) / VT) + 3) * VT + 63) / 64;     // residual rows: raw frames 4 ja .. 4 jb + 2
+    constexpr int NJR = ((4 * ((NT + VT - 2) / VT) + 3) * VT + 63) / 64;      // residual rows: raw frames 4 ja .. 4 jb + 2
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *Wl = smem;
-    float *Bl = smem + W2TAPS * KC * WMT;
+    float *Bl = smem + W2TAPS * KC * MT;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, kh = lane >> 5;
+    const int wm = MW == 2 ? wave >> 1 : 0, wn = MW == 2 ? wave & 1 : wave;     // this wave's channel half / column part
     const unsigned wid = xcd_contiguous_id(blockIdx.x, gridDim.x);
-    const int m0 = (int)(wid % p.mtiles) * WMT, q0 = (int)((wid / p.mtiles) % p.qtiles) * WNT;
+    const int m0 = (int)(wid % p.mtiles) * MT, q0 = (int)((wid / p.mtiles) % p.qtiles) * NT;
     const int seg = (int)(wid / (p.mtiles * p.qtiles));
     const int TVin = p.Tin * VT, QP = p.nt;
-    const int qend = min(q0 + WNT, QP);
+    const int qend = min(q0 + NT, QP);
     const int ja = div_magic(q0, p.vmagic), jb = div_magic(qend - 1, p.vmagic);
+    const float *Ww = Wl + wm * WMT;                                 // this wave's rows of the staged weights
 
     // this lane's pair column (clamped into the tile; lanes past its end compute a copy of the last column and store nothing)
-    const int qc = min(q0 + wave * 32 + l31, qend - 1);
+    const int qc = min(q0 + wn * 32 + l31, qend - 1);
     const int jc = div_magic(qc, p.vmagic), vc = qc - jc * VT;
     const int off = 4 * (jc - ja) * VT + vc;
 
@@ -367,7 +498,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void tcn_stage_wino_s2_kernel(const Tc
         const int64_t cs = (int64_t)TVin;
         const float *seg_base = p.y + (int64_t)seg * p.C * cs;       // 64-bit segment base; 32-bit offsets inside it
         const float *wbase = p.w + m0;
-        WStage13x64 ws;
+        std::conditional_t<MW == 2, WStageNx128<W2TAPS>, WStage13x64> ws;
         ws.setup(p.Cpad, p.Mpad, tid);
         auto kloop = [&](auto &bx) {
             ws.issue(wbase);
@@ -379,42 +510,39 @@ __global__ __launch_bounds__(NTHREADS, 2) void tcn_stage_wino_s2_kernel(const Tc
                 __syncthreads();
                 const float *wnext = wbase + (size_t)(c0 + KC) * p.Mpad;
                 const int cn = c0 + KC;
-                ws.issue_slot(0, wnext);
-                ws.issue_slot(1, wnext);
+                ws.template issue_part<0>(wnext);
                 bx.template issue_third<0>(seg_base, p.C, cs, cn, wave);
                 __builtin_amdgcn_s_setprio(1);
-                wino2_group<VT, 0, 0, 4>(Wl, Bl, off, l31, kh, acc);
+                wino2_group<VT, 0, 0, 4, MW>(Ww, Bl, off, l31, kh, acc);
                 __builtin_amdgcn_s_setprio(0);
-                ws.issue_slot(2, wnext);
-                ws.issue_slot(3, wnext);
+                ws.template issue_part<1>(wnext);
                 bx.template issue_third<1>(seg_base, p.C, cs, cn, wave);
                 __builtin_amdgcn_s_setprio(1);
-                wino2_group<VT, 4, 6, 3>(Wl, Bl, off, l31, kh, acc);
+                wino2_group<VT, 4, 6, 3, MW>(Ww, Bl, off, l31, kh, acc);
                 __builtin_amdgcn_s_setprio(0);
-                ws.issue_slot(4, wnext);
-                ws.issue_slot(5, wnext);
+                ws.template issue_part<2>(wnext);
                 bx.template issue_third<2>(seg_base, p.C, cs, cn, wave);
                 __builtin_amdgcn_s_setprio(1);
-                wino2_group<VT, 7, 1, 3>(Wl, Bl, off, l31, kh, acc);
+                wino2_group<VT, 7, 1, 3, MW>(Ww, Bl, off, l31, kh, acc);
                 __builtin_amdgcn_s_setprio(0);
-                ws.issue_slot(6, wnext);
+                ws.template issue_part<3>(wnext);
                 __builtin_amdgcn_s_setprio(1);
-                wino2_group<VT, 10, 5, 3>(Wl, Bl, off, l31, kh, acc);
+                wino2_group<VT, 10, 5, 3, MW>(Ww, Bl, off, l31, kh, acc);
                 __builtin_amdgcn_s_setprio(0);
             }
             __syncthreads();                         // peeled last chunk
             ws.commit(Wl);
             bx.commit(Bl, LDB, wave);
             __syncthreads();
-            wino2_group<VT, 0, 0, 4>(Wl, Bl, off, l31, kh, acc);
-            wino2_group<VT, 4, 6, 3>(Wl, Bl, off, l31, kh, acc);
-            wino2_group<VT, 7, 1, 3>(Wl, Bl, off, l31, kh, acc);
-            wino2_group<VT, 10, 5, 3>(Wl, Bl, off, l31, kh, acc);
+            wino2_group<VT, 0, 0, 4, MW>(Ww, Bl, off, l31, kh, acc);
+            wino2_group<VT, 4, 6, 3, MW>(Ww, Bl, off, l31, kh, acc);
+            wino2_group<VT, 7, 1, 3, MW>(Ww, Bl, off, l31, kh, acc);
+            wino2_group<VT, 10, 5, 3, MW>(Ww, Bl, off, l31, kh, acc);
         };
         // tiles whose staged span lies inside the sequence: 16-byte staging; the others (zero padding at either end) element-wise
         const bool interior = fa >= 0 && fa * VT + 4 * ((span + 3) / 4) <= TVin;   // uniform
         if (interior) {
-            BStage4<(NJ + 3) / 4> b4;
+            std::conditional_t<MW == 2, BStage4Tail<LDB>, BStage4<(NJ + 3) / 4>> b4;
             b4.setup(fa * VT, span, lane);
             kloop(b4);
         } else {
@@ -432,7 +560,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void tcn_stage_wino_s2_kernel(const Tc
         const float *seg_base = p.xres + (int64_t)seg * p.Cres * cs;
         const float *wbase = p.wres + m0;
         const int cend = (p.Cres + KC - 1) / KC * KC;                // <= CresPad: rows of the image
-        WStageRes64 wr;
+        std::conditional_t<MW == 2, WStageRes128, WStageRes64> wr;
         wr.setup(p.Mpad, tid);
         BStage<NJR> bs;
         bs.setup(4 * ja * VT, span, p.Tres * VT, lane);
@@ -445,16 +573,32 @@ __global__ __launch_bounds__(NTHREADS, 2) void tcn_stage_wino_s2_kernel(const Tc
             __syncthreads();
             wr.issue(wbase + (size_t)(c0 + KC) * p.Mpad);
             bs.issue(seg_base, p.Cres, cs, c0 + KC, wave);
-            wino2_res_chunk<VT>(Wl, Bl, off, l31, kh, acc);
+            wino2_res_chunk<VT, MW>(Ww, Bl, off, l31, kh, acc);
         }
         __syncthreads();
         wr.commit(Wl);
         bs.commit(Bl, LDB, wave);
         __syncthreads();
-        wino2_res_chunk<VT>(Wl, Bl, off, l31, kh, acc);
+        wino2_res_chunk<VT, MW>(Ww, Bl, off, l31, kh, acc);
     }
 
-    wino_epilogue<VT, false>(p, acc, m0, q0, qend, seg, wave, l31, kh, jc, vc);
+    wino_epilogue<VT, false>(p, acc, m0 + wm * WMT, q0, qend, seg, wn, l31, kh, jc, vc);
+}
+
+// Workgroup shape of a launch with qp pair columns per sequence -- a function of the layer alone, never of the batch.  Both
+// shapes need c_out a multiple of their rows, so the tall one never issues more columns x rows than the wide one.  Measured at
+// batch 256 (profiles/HISTORY.md round 16): at equal issued columns the tall stride-2 kernel is 2 % faster than the wide one (it
+// stages less per chunk), the tall stride-1 kernel 2 - 5 % slower (twice the weight traffic per column).  So stride 2 takes the
+// tall shape wherever c_out allows it, stride 1 where it issues at least 1/16 fewer columns (T = 75: 960 against 1024 at V = 25,
+// 704 against 768 at V = 18; not T = 300: 3776 against 3840, measured 2 % slower).
+// CSK_TCN_WINO=2 / =3 (diagnostic, under CSK_DIAG) takes the wide / the tall shape wherever c_out allows both.
+static int wino_pick_mw(int qp, int c_out, int stride) {
+    if (c_out % (2 * WMT) != 0) return 1;
+    const int force = csk_diag_int("CSK_TCN_WINO");
+    if (force == 2 || force == 3) return force - 1;
+    if (stride == 2) return 2;
+    const int64_t wide = round_up(qp, WNT), tall = round_up(qp, WNT / 2);
+    return 16 * tall <= 15 * wide ? 2 : 1;
 }
 
 // -2: the shape is not one the Winograd kernel is built for (the caller runs the direct kernels); 0 / error code otherwise.
@@ -468,9 +612,10 @@ static int tcn_stage_wino_launch(const float *y, const float *w_wino, const floa
         return -2;
     if ((V != 25 && V != 18) || c_out % WMT != 0 || c < 1 || n_seg < 1 || t_in < 1) return -2;
     if ((int64_t)t_in * V >= (1 << 26)) return -2;                    // 32-bit position / lane byte offsets inside a segment
-    if (csk_diag_flag("CSK_TCN_WINO")) return -2;                     // diagnostic A/B switch: the direct kernels
+    if (csk_diag_flag("CSK_TCN_WINO") && csk_diag_int("CSK_TCN_WINO") < 2) return -2;   // diagnostic A/B switch: the direct kernels
     const int qp = (t_in + 1) / 2 * V;
-    const int qtiles = (qp + WNT - 1) / WNT, mtiles = c_out / WMT;
+    const int mw = wino_pick_mw(qp, c_out, stride);
+    const int qtiles = (qp + WNT / mw - 1) / (WNT / mw), mtiles = c_out / (WMT * mw);
     if ((int64_t)qtiles * mtiles * n_seg >= (1ll << 31)) return -2;
     TcnParams p = {};
     p.y = y; p.w = w_wino; p.xres = res_none ? nullptr : x_res; p.wres = nullptr; p.bias = bias; p.out = out;
@@ -479,11 +624,19 @@ static int tcn_stage_wino_launch(const float *y, const float *w_wino, const floa
     p.res_mode = res_mode; p.Cres = res_none ? 0 : c_res; p.CresPad = round_up(p.Cres, CSK_CPAD); p.Tres = res_none ? 0 : t_res;
     p.res_off = 0; p.relu = relu;
     p.vmagic = vmagic_of(V); p.mtiles = (unsigned)mtiles; p.qtiles = (unsigned)qtiles; p.nt = qp;
-    void (*kern)(TcnParams) = res_none ? (V == 25 ? tcn_stage_wino_kernel<25, false> : tcn_stage_wino_kernel<18, false>)
-                                       : (V == 25 ? tcn_stage_wino_kernel<25> : tcn_stage_wino_kernel<18>);
-    const int ldb = V == 25 ? wino_ldb<25>() : wino_ldb<18>();
+    void (*kern)(TcnParams);
+    int ldb;
+    if (mw == 2) {
+        kern = res_none ? (V == 25 ? tcn_stage_wino_kernel<25, false, 2> : tcn_stage_wino_kernel<18, false, 2>)
+                        : (V == 25 ? tcn_stage_wino_kernel<25, true, 2> : tcn_stage_wino_kernel<18, true, 2>);
+        ldb = V == 25 ? wino_ldb<25, 2>() : wino_ldb<18, 2>();
+    } else {
+        kern = res_none ? (V == 25 ? tcn_stage_wino_kernel<25, false> : tcn_stage_wino_kernel<18, false>)
+                        : (V == 25 ? tcn_stage_wino_kernel<25> : tcn_stage_wino_kernel<18>);
+        ldb = V == 25 ? wino_ldb<25>() : wino_ldb<18>();
+    }
     p.ldb = ldb;
-    const size_t lds = (size_t)(WTAPS * KC * WMT + KC * ldb) * sizeof(float);
+    const size_t lds = (size_t)(WTAPS * KC * WMT * mw + KC * ldb) * sizeof(float);
     if (const int e = csk_ensure_lds((const void *)kern, lds)) return e;
     hipLaunchKernelGGL(kern, dim3((unsigned)(qtiles * mtiles * n_seg)), dim3(NTHREADS), lds, (hipStream_t)stream, p);
     return (int)hipGetLastError();
@@ -500,10 +653,11 @@ static int tcn_stage_wino_s2_launch(const float *y, const float *w_s2, const flo
     if (conv && (!x_res || !w_res || c_res < 1 || t_res != t_in)) return -2;
     if ((V != 25 && V != 18) || c_out % WMT != 0 || c < 1 || n_seg < 1 || t_in < 1) return -2;
     if ((int64_t)t_in * V >= (1 << 26)) return -2;                    // 32-bit position / lane byte offsets inside a segment
-    if (csk_diag_flag("CSK_TCN_WINO")) return -2;                     // diagnostic A/B switch: the direct kernels
+    if (csk_diag_flag("CSK_TCN_WINO") && csk_diag_int("CSK_TCN_WINO") < 2) return -2;   // diagnostic A/B switch: the direct kernels
     const int t_out = (t_in - 1) / 2 + 1;
     const int qp = (t_out + 1) / 2 * V;
-    const int qtiles = (qp + WNT - 1) / WNT, mtiles = c_out / WMT;
+    const int mw = wino_pick_mw(qp, c_out, stride);
+    const int qtiles = (qp + WNT / mw - 1) / (WNT / mw), mtiles = c_out / (WMT * mw);
     if ((int64_t)qtiles * mtiles * n_seg >= (1ll << 31)) return -2;
     TcnParams p = {};
     p.y = y; p.w = w_s2; p.xres = conv ? x_res : nullptr; p.wres = conv ? w_res : nullptr; p.bias = bias; p.out = out;
@@ -512,11 +666,19 @@ static int tcn_stage_wino_s2_launch(const float *y, const float *w_s2, const flo
     p.res_mode = res_mode; p.Cres = conv ? c_res : 0; p.CresPad = round_up(p.Cres, CSK_CPAD); p.Tres = conv ? t_res : 0;
     p.res_off = 0; p.relu = relu;
     p.vmagic = vmagic_of(V); p.mtiles = (unsigned)mtiles; p.qtiles = (unsigned)qtiles; p.nt = qp;
-    void (*kern)(TcnParams) = conv ? (V == 25 ? tcn_stage_wino_s2_kernel<25, true> : tcn_stage_wino_s2_kernel<18, true>)
-                                   : (V == 25 ? tcn_stage_wino_s2_kernel<25, false> : tcn_stage_wino_s2_kernel<18, false>);
-    const int ldb = V == 25 ? wino2_ldb<25>() : wino2_ldb<18>();
+    void (*kern)(TcnParams);
+    int ldb;
+    if (mw == 2) {
+        kern = conv ? (V == 25 ? tcn_stage_wino_s2_kernel<25, true, 2> : tcn_stage_wino_s2_kernel<18, true, 2>)
+                    : (V == 25 ? tcn_stage_wino_s2_kernel<25, false, 2> : tcn_stage_wino_s2_kernel<18, false, 2>);
+        ldb = V == 25 ? wino2_ldb<25, 2>() : wino2_ldb<18, 2>();
+    } else {
+        kern = conv ? (V == 25 ? tcn_stage_wino_s2_kernel<25, true> : tcn_stage_wino_s2_kernel<18, true>)
+                    : (V == 25 ? tcn_stage_wino_s2_kernel<25, false> : tcn_stage_wino_s2_kernel<18, false>);
+        ldb = V == 25 ? wino2_ldb<25>() : wino2_ldb<18>();
+    }
     p.ldb = ldb;
-    const size_t lds = (size_t)(W2TAPS * KC * WMT + KC * ldb) * sizeof(float);
+    const size_t lds = (size_t)(W2TAPS * KC * WMT * mw + KC * ldb) * sizeof(float);
     if (const int e = csk_ensure_lds((const void *)kern, lds)) return e;
     hipLaunchKernelGGL(kern, dim3((unsigned)(qtiles * mtiles * n_seg)), dim3(NTHREADS), lds, (hipStream_t)stream, p);
     return (int)hipGetLastError();
