@@ -20,11 +20,12 @@ from .blocks import (  # noqa: F401
     unity,
     zero,
 )
-from .models import StGcn  # noqa: F401
+from .models import StGcn, StGcnMod  # noqa: F401
 from .continual import (  # noqa: F401
     CoGraphConvolution,
     CoSpatioTemporalBlock,
     CoStGcn,
+    CoStGcnMod,
     CoTemporalConvolution,
     set_step_precision,
 )
@@ -42,7 +43,7 @@ CoStGcnBlock = CoSpatioTemporalBlock
 
 __all__ = [
     "Graph", "ntu_graph", "kinetics_graph", "GraphConvolution", "TemporalConvolution",
-    "SpatioTemporalBlock", "SpatialGraphConv", "StGcnBlock", "CoStGcnBlock", "StGcn", "CoStGcn",
+    "SpatioTemporalBlock", "SpatialGraphConv", "StGcnBlock", "CoStGcnBlock", "StGcn", "CoStGcn", "StGcnMod", "CoStGcnMod",
     "CoGraphConvolution", "CoTemporalConvolution", "CoSpatioTemporalBlock",
     "AdaptiveGraphConvolution", "CoAdaptiveGraphConvolution", "AGcn", "CoAGcn", "GcnUnitAttention", "STr", "CoSTr",
     "init_weights", "zero", "unity",

@@ -341,12 +341,14 @@ class TemporalConvolution(_Folded):
 
 
 def tcn_stage(y, w, bias, c_out, k, stride, pad, relu=True, res_mode=0, x_res=None, w_res=None, res_off=0, out=None,
-              split=False, ksplit=1, scratch=None, w_wino=None, w_wino_ext=None):
+              split=False, ksplit=1, scratch=None, w_wino=None, w_wino_ext=None, w_wino_valid=None):
     """csk_tcn_stage_f32, or with split=True csk_tcn_stage_bf16x3 (w / w_res are then the split operand images), or with
     ksplit > 1 csk_tcn_stage_splitk_f32 (clip latency mode: K loop cut into channel ranges, partial sums in split order), or
     with the Winograd image w_wino (fold.pack_conv_weight_wino) csk_tcn_stage_wino_f32 (the Winograd kernel where the layer's
     shape allows it, csk_tcn_stage_f32 otherwise), or with the image w_wino_ext csk_tcn_stage_wino_ext_f32 (stride 2:
-    fold.pack_conv_weight_wino_s2, the polyphase Winograd kernel; stride 1 without residual: fold.pack_conv_weight_wino)."""
+    fold.pack_conv_weight_wino_s2, the polyphase Winograd kernel; stride 1 without residual: fold.pack_conv_weight_wino), or with
+    w_wino_valid (the same image as w_wino) csk_tcn_stage_wino_valid_f32: the pad-0 form of the stride-1 Winograd kernel with the
+    centred identity residual (res_off 4) or none."""
     n, c, t_in, v = y.shape
     if t_in + 2 * pad < k:
         raise RuntimeError(f"temporal extent {t_in} (+2*{pad}) shorter than kernel {k}")
@@ -365,6 +367,15 @@ def tcn_stage(y, w, bias, c_out, k, stride, pad, relu=True, res_mode=0, x_res=No
             n, c, c_out, t_in, v, k, stride, pad, res_mode, c_res, t_res, res_off, int(relu), ksplit, native.ptr(part),
             native.stream_of(y))
         native.check(rc, "csk_tcn_stage_splitk_f32")
+        return out
+    if w_wino_valid is not None and not split:
+        if w_wino_valid.dim() != 3 or w_wino_valid.shape[0] != 12 or tuple(w_wino_valid.shape[1:]) != tuple(w.shape[1:]):
+            raise RuntimeError(f"tcn_stage: w_wino_valid must be the [12][c_pad][c_out_pad] image of the conv, got {tuple(w_wino_valid.shape)}")
+        rc = native.lib().csk_tcn_stage_wino_valid_f32(
+            native.ptr(y), native.ptr(w), native.ptr(x_res), native.ptr(w_res), native.ptr(bias), native.ptr(out),
+            n, c, c_out, t_in, v, k, stride, pad, res_mode, c_res, t_res, res_off, int(relu), native.ptr(w_wino_valid),
+            native.stream_of(y))
+        native.check(rc, "csk_tcn_stage_wino_valid_f32")
         return out
     if w_wino_ext is not None and not split:
         rows = 13 if stride == 2 else 12                       # the entry is not told the image's size
@@ -424,6 +435,7 @@ class SpatioTemporalBlock(_Folded):
     precision = "f32"      # or "bf16x3" (opt-in, set_precision): arithmetic of the temporal conv / residual conv kernels
     clip_split_k = 0       # set_clip_latency_mode: channel ranges per tile of the clip forward's temporal conv (0 / 1: off)
     clip_split_max_seq = CLIP_SPLIT_MAX_SEQUENCES   # ... for forwards of at most this many sequences
+    wino_valid = True      # temporal_padding=0 blocks with the identity residual: csk_tcn_stage_wino_valid_f32 (False: the direct kernels)
 
     def _watched(self):    # the tail's operands are folded from the temporal conv and the residual conv; the graph conv keeps its own cache
         return [m for m in (self.tcn, self.residual) if isinstance(m, nn.Module)]
@@ -460,6 +472,11 @@ class SpatioTemporalBlock(_Folded):
         # two launches (tests/test_gpu_clip_parity.py), and it computes the direct sums; tcn_stage(w_wino_ext=) offers the
         # Winograd form of that shape to callers that do not need those bits
         ks = max(1, min(self.clip_split_k, -(-ops["c"] // 8))) if (self.clip_split_k > 1 and ops["k"] == 9 and y.shape[0] <= self.clip_split_max_seq) else 1
+        if self.tcn.padding == 0 and shrink == 4 and self.residual is unity and self.stride == 1 and ks == 1 and self.wino_valid:
+            # the unpadded "*" block with the centred identity residual: the valid form of the Winograd kernel (the no-residual
+            # and conv-residual "*" blocks keep the direct kernels, which take pad 0 and res_off as they are)
+            return tcn_stage(y, ops["w"], ops["bias"], ops["c_out"], ops["k"], 1, 0, relu=True, res_mode=1, x_res=x, res_off=4,
+                             out=out, w_wino_valid=ops["w_wino"])
         return tcn_stage(y, ops["w"], ops["bias"], ops["c_out"], ops["k"], self.stride, self.tcn.padding, relu=True,
                          res_mode=mode, x_res=xr, w_res=ops["w_res"], res_off=shrink, out=out, ksplit=ks,
                          scratch=_scratch_of(self) if ks > 1 else None, w_wino=ops["w_wino"] if ks == 1 else None,

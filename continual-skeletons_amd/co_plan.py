@@ -92,6 +92,8 @@ class NativePlan:
         if not plan:
             raise RuntimeError("csk_co_plan_create: " + native.lib().csk_last_error().decode())
         self.__dict__["_plan"] = plan
+        delays = (ctypes.c_int32 * 10)(*[blk.delay for blk in self._blocks])      # 4 per block (CoStGcn), 8 (CoStGcnMod)
+        native.check(native.lib().csk_co_plan_set_delays(plan, 10, ctypes.byref(delays)), "csk_co_plan_set_delays")
         self._install_dirty_hooks()
         self.__dict__["_plan_keep"] = (keep, self._weight_slots())
         self.__dict__.pop("_weights_dirty", None)

@@ -34,7 +34,7 @@ from .co_plan import NativePlan
 from .co_reset import StreamReset
 from .modality import ContinualModality
 from .prenorm import ContinualPreNorm
-from .models import layer_table, per_layer
+from .models import MOD_TEMPORAL_PADDING, layer_table, per_layer
 
 MAX_CYCLE = native.CO_MAX_CYCLE
 RES_MODE = {"none": 0, "identity": 1, "conv": 2}    # block residual as the step kernels and csk_co_layer.res_kind take it
@@ -534,6 +534,8 @@ def set_step_precision(module: nn.Module, precision: str = "f32") -> nn.Module:
         raise NotImplementedError("step precision 'bf16x3' is built for blocks with the plain GraphConvolution (CoStGcn); "
                                   "the model is unchanged")
     models = [m for m in module.modules() if isinstance(m, CoStGcn)]
+    if precision != "f32" and any(m.unpadded for m in models):
+        raise NotImplementedError("step precision 'bf16x3' is not built for the unpadded '*' models (CoStGcnMod); the model is unchanged")
     owned = {id(b) for m in models for b in m.layers.values()}
     for m in models:                # as set_max_cycle: the native plan goes now, the slab is re-bound (zeroed) on the next step
         m._destroy_plan()
@@ -546,12 +548,14 @@ def set_step_precision(module: nn.Module, precision: str = "f32") -> nn.Module:
     return module
 
 
-def co_geometry(c_in=3):
-    """receptive_field / padding / stride of the ten-block stack (read from co.Sequential at base.py:86-97)."""
+def co_geometry(c_in=3, unpadded=False):
+    """receptive_field / padding / stride of the ten-block stack (read from co.Sequential at base.py:86-97), from the layer
+    table: (153, 76, 4) for the padded table, (81, 0, 1) for the "*" table (``unpadded``: stride 1, temporal padding 0)."""
     r, p, s = 1, 0, 1
-    for (_, _, st, _) in layer_table(c_in):
+    block_padding = MOD_TEMPORAL_PADDING if unpadded else 4
+    for (_, _, st, _) in layer_table(c_in, unpadded):
         r += 8 * s
-        p += 4 * s
+        p += block_padding * s
         s *= st
     return r, p, s
 
@@ -572,6 +576,7 @@ class CoStGcn(NativePlan, StreamReset, ContinualPreNorm, ContinualModality, _Fol
     # False: drive every launch from Python (same kernels, same results).  Read on every cycle: both engines step on the one
     # counter buffer, so they may alternate; the plan itself is built when the slab is bound with the attribute set
     use_native_plan = True
+    unpadded = False        # CoStGcnMod: the "*" layer table (stride 1, block padding 0 -> delay 8 per block)
 
     def __init__(self, graph_A, input_shape=(3, 300, 25, 2), num_classes=60, pool_size=-1, pool_padding=-1,
                  CoGraphConv=CoGraphConvolution):
@@ -581,13 +586,13 @@ class CoStGcn(NativePlan, StreamReset, ContinualPreNorm, ContinualModality, _Fol
         self.data_bn = nn.BatchNorm1d(m * c_in * v)
         convs = [CoGraphConvolution if f is None else f for f in per_layer(CoGraphConv)]   # one factory, or ten (None: default)
         self.layers = nn.ModuleDict(OrderedDict(
-            (f"layer{i + 1}", CoSpatioTemporalBlock(ci, co, graph_A, stride=s, residual=r, padding="equal",
-                                                    CoGraphConv=convs[i]))
-            for i, (ci, co, s, r) in enumerate(layer_table(c_in))))
+            (f"layer{i + 1}", CoSpatioTemporalBlock(ci, co, graph_A, stride=s, residual=r,
+                                                    padding=MOD_TEMPORAL_PADDING if self.unpadded else "equal", CoGraphConv=convs[i]))
+            for i, (ci, co, s, r) in enumerate(layer_table(c_in, self.unpadded))))
         self.fc = nn.Linear(256, num_classes)
         init_weights(self.data_bn, bs=1)
         init_weights(self.fc, bs=num_classes)
-        self.receptive_field, self.padding, self.stride = co_geometry(c_in)
+        self.receptive_field, self.padding, self.stride = co_geometry(c_in, self.unpadded)
         self.delay = self.padding
         if pool_size == -1:                                                   # base.py:86-90
             pool_size = math.ceil((t - self.receptive_field + 2 * self.padding + 1) / self.stride)
@@ -941,3 +946,29 @@ class CoStGcn(NativePlan, StreamReset, ContinualPreNorm, ContinualModality, _Fol
         frames = self.receptive_field - self.padding - 1 if frames is None else frames
         for _ in range(frames):
             self.forward_step(torch.randn((n, c, v, m), device=device))
+
+
+class CoStGcnMod(CoStGcn):
+    """CoST-GCN*: models/cost_gcn_mod/cost_gcn_mod.py:29-40 -- ten continual blocks with ``padding=0`` and stride 1 (``window_size`` is
+    accepted by the block and unused, as in the reference).  Geometry from the table (``co_geometry(c, unpadded=True)``): receptive
+    field 81, padding 0, stride 1, delay 0; the defaults of base.py:86-97 then give pool_size = T - 80 and pool_padding = 0.  Every
+    block waits k - 1 = 8 frames (delay 8 against CoStGcn's 4), so the first layer-10 feature comes with frame 80 and every
+    frame after it yields one: emission s is StGcnMod's clip feature frame s - 80.  state_dict keys are the reference's; a StGcnMod
+    state dict loads through ``map_state_dict``.  Steps on the native plan (per-layer delay: csk_co_plan_set_delays) and on the
+    Python engine; stream reset, input modality and pre-normalisation are CoStGcn's (generic in delay and stride).  The latency
+    mode and the "bf16x3" precisions are not built for it: they raise."""
+
+    unpadded = True
+
+    def __init__(self, graph_A, input_shape=(3, 300, 25, 2), num_classes=60, pool_size=-1, pool_padding=-1):
+        super().__init__(graph_A, input_shape, num_classes, pool_size, pool_padding)
+
+    def set_latency_mode(self, split_k: int = 8):
+        raise NotImplementedError("the latency mode is not built for the unpadded '*' models; the model is unchanged")
+
+    def _clip_features(self, x):
+        if any(b.precision != "f32" for b in self._blocks):
+            raise NotImplementedError("precision 'bf16x3' is not built for the unpadded '*' models: set_precision(model, 'f32')")
+        if x.dim() != 5 or x.shape[2] < self.receptive_field:
+            raise ValueError(f"CoStGcnMod's clip forward needs T >= {self.receptive_field} frames, got {tuple(x.shape)}")
+        return super()._clip_features(x)

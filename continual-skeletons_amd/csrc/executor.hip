@@ -21,6 +21,7 @@ struct Counters {
 
 struct csk_co_plan {
     std::vector<csk_co_layer> layers;
+    std::vector<int> delay;    // per layer: steps before the first emission, k - 1 - padding (4: padding "equal"; 8: padding 0)
     float *xin0;
     int xin0_slots;
     int N, C, V, M, classes, pool_size, pool_padding;
@@ -77,6 +78,7 @@ extern "C" csk_co_plan *csk_co_plan_create(int n_layers, const csk_co_layer *lay
     csk_co_plan *p = new csk_co_plan();
     p->max_cycle = max_cycle;
     p->layers.assign(layers, layers + n_layers);
+    p->delay.assign(n_layers, 4);
     p->xin0 = xin0; p->xin0_slots = xin0_slots; p->N = N; p->C = C; p->V = V; p->M = M; p->P = P;
     p->bn_scale = bn_scale; p->bn_shift = bn_shift; p->classes = classes; p->fc_w = fc_w; p->fc_b = fc_b;
     p->pool_size = pool_size; p->pool_padding = pool_padding;
@@ -113,9 +115,19 @@ extern "C" int csk_co_plan_set_fusion(csk_co_plan *plan, int enable) {
     return 0;
 }
 
-// a whole emitting 4-frame cycle of a 64-row block that csk_co_block_step_f32 / csk_co_stack_step_f32 take (continual.py:_fusable)
-static bool fusable_cycle(const csk_co_layer &l, const BlockCounters &c, int r, int V) {
-    return l.agcn_inter == 0 && r == 4 && l.stride == 1 && l.c_out <= 64 && c.s >= 4 && l.res_kind != CSK_RES_CONV && l.tcn_ksplit <= 1 &&
+extern "C" int csk_co_plan_set_delays(csk_co_plan *plan, int n_layers, const int32_t *delays) {
+    if (!plan || !delays) CSK_FAIL("co_plan_set_delays: null pointer");
+    if (n_layers != (int)plan->layers.size()) CSK_FAIL("co_plan_set_delays: layer count mismatch");
+    for (int i = 0; i < n_layers; ++i)
+        if (delays[i] < 4 || delays[i] > 8) CSK_FAIL("co_plan_set_delays: layer %d delay %d outside [4, 8] (k - 1 - padding, k = 9)", i, delays[i]);
+    plan->delay.assign(delays, delays + n_layers);
+    return 0;
+}
+
+// a whole emitting 4-frame cycle of a 64-row block that csk_co_block_step_f32 / csk_co_stack_step_f32 take (continual.py:_fusable);
+// the fused kernels emit for all four frames and read y[s - 8 .. s], x[s - 4]: right for any delay once s >= delay
+static bool fusable_cycle(const csk_co_layer &l, const BlockCounters &c, int delay, int r, int V) {
+    return l.agcn_inter == 0 && r == 4 && l.stride == 1 && l.c_out <= 64 && c.s >= delay && l.res_kind != CSK_RES_CONV && l.tcn_ksplit <= 1 &&
            l.gcn_ksplit <= 1 && l.ell_cnt[0] <= 1 && l.ell_cnt[1] <= 1 && l.ell_cnt[2] <= 4 && ((64 + V - 2) / V + 1) * V <= 128;
 }
 
@@ -137,9 +149,9 @@ static int64_t emissions(int64_t s0, int r, int delay, int stride, int *n) {
 
 // one block in two stages: r frames are already in xin[(s .. s+r-1) % HIST] (HIST = depth of the input ring = the upstream
 // layer's out_slots); returns emissions via *slot0 / *n_emit
-static int advance_block(const csk_co_layer &l, BlockCounters &c, const float *xin, int HIST, int r, int n_frames, int V,
+static int advance_block(const csk_co_layer &l, BlockCounters &c, int delay, const float *xin, int HIST, int r, int n_frames, int V,
                          int64_t P, int *slot0, int *n_emit, void *stream) {
-    constexpr int K = 9, DELAY = 4, LAG = 4;      // padding="equal": delay = k-1-p = 4; residual lag (k-1)/2
+    constexpr int K = 9, LAG = 4;                 // delay = k-1-p (4: padding="equal", 8: padding 0); residual lag (k-1)/2 in both
     const int YRING = l.y_slots, OUT = l.out_slots;      // (run_blocks has checked that r frames fit YRING and HIST)
     const int64_t s0 = c.s;
     for (int f = 0; f < r;) {                      // per-frame graph conv, one launch per non-wrapping slot run
@@ -172,7 +184,7 @@ static int advance_block(const csk_co_layer &l, BlockCounters &c, const float *x
         f += run;
     }
     int ne;
-    const int64_t first = emissions(s0, r, DELAY, l.stride, &ne);
+    const int64_t first = emissions(s0, r, delay, l.stride, &ne);
     c.s += r;
     *n_emit = 0;
     if (ne == 0) return 0;
@@ -196,7 +208,7 @@ static int run_blocks(const csk_co_plan *p, std::vector<BlockCounters> &cnt, int
     const float *xin = p->xin0;
     int rr = r, in_slots = p->xin0_slots;
     *n_last = 0;
-    auto fusable = [&](size_t k, int r) { return p->fuse && k < p->layers.size() && fusable_cycle(p->layers[k], cnt[k], r, p->V); };
+    auto fusable = [&](size_t k, int r) { return p->fuse && k < p->layers.size() && fusable_cycle(p->layers[k], cnt[k], p->delay[k], r, p->V); };
     // identity gcn_residual: what the fused stack kernel covers
     auto stackable = [&](size_t k, int r) { return fusable(k, r) && p->layers[k].gcn_res_mode == CSK_RES_IDENTITY; };
     for (size_t i = 0; i < p->layers.size(); ++i) {
@@ -226,7 +238,7 @@ static int run_blocks(const csk_co_plan *p, std::vector<BlockCounters> &cnt, int
             continue;
         }
         int ne = 0;
-        const int rc = advance_block(l, cnt[i], xin, in_slots, rr, p->N * p->M, p->V, p->P, slot0, &ne, stream);
+        const int rc = advance_block(l, cnt[i], p->delay[i], xin, in_slots, rr, p->N * p->M, p->V, p->P, slot0, &ne, stream);
         if (rc) return rc;
         if (ne == 0) return 0;
         rr = ne;

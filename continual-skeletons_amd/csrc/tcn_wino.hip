@@ -145,17 +145,22 @@ __device__ __forceinline__ void wino_group(const float *__restrict__ Wl, const f
 // row = (g & 3) + 8 (g >> 2) + 4 (lane >> 5).  Row base pointers are wave-uniform (64-bit); a lane adds one 32-bit byte offset
 // (4 kh rows + its position; T V < 2^26 keeps it below 2^32).  Every wave has all 64 rows (c_out a multiple of the tile's rows,
 // host gate).  p.Tout = output frames; m0 = the wave's first row, wn = its column quarter / half; (jc, vc) = this lane's pair column.
-template <int VT, bool RES>
+// VALID (csk_tcn_stage_wino_valid_f32): the output has p.Tout = p.Tin - 8 frames, the residual is the block input of p.Tin
+// frames read 4 frames further on (the centred shrink) -- its own row length and lane offsets.
+template <int VT, bool RES, bool VALID = false>
 __device__ __forceinline__ void wino_epilogue(const TcnParams &p, const f32x16 (&acc)[4][2], int m0, int q0, int qend, int seg,
                                               int wn, int l31, int kh, int jc, int vc) {
     const int T = p.Tout, TV = T * VT;
+    const int TVR = VALID ? p.Tin * VT : TV;                         // row length of the residual
     const bool qv = q0 + wn * 32 + l31 < qend;
     const bool odd_ok = 2 * jc + 1 < T;                              // the pair's second frame exists (T odd: not the last pair)
     const unsigned p0 = (unsigned)(2 * jc * VT + vc);
     const unsigned b0 = 4u * (4u * (unsigned)kh * (unsigned)TV + p0);
     const unsigned b1 = odd_ok ? b0 + 4u * VT : b0;                  // phantom frame: re-read frame 2 j (value unused)
     const unsigned kh16 = 16u * (unsigned)kh;
-    const float *rseg = RES ? p.xres + (int64_t)seg * p.Cout * TV : nullptr;
+    const unsigned r0 = VALID ? 4u * (4u * (unsigned)kh * (unsigned)TVR + p0 + 4u * VT) : b0;
+    const unsigned r1 = VALID ? (odd_ok ? r0 + 4u * VT : r0) : b1;
+    const float *rseg = RES ? p.xres + (int64_t)seg * p.Cout * TVR : nullptr;
     float *oseg = p.out + (int64_t)seg * p.Cout * TV;
 #pragma unroll
     for (int mi = 0; mi < 2; ++mi) {
@@ -169,9 +174,9 @@ __device__ __forceinline__ void wino_epilogue(const TcnParams &p, const f32x16 (
             float v0 = acc[0][mi][g] + m1 + m2 + bias;
             float v1 = m1 - m2 - acc[3][mi][g] + bias;
             if (RES) {
-                const float *rrow = rseg + (int64_t)row * TV;
-                v0 += ld_lane(rrow, b0);
-                v1 += ld_lane(rrow, b1);
+                const float *rrow = rseg + (int64_t)row * TVR;
+                v0 += ld_lane(rrow, r0);
+                v1 += ld_lane(rrow, r1);
             }
             if (p.relu) { v0 = relu_nan(v0); v1 = relu_nan(v1); }
             o0[g] = v0;
@@ -190,8 +195,12 @@ __device__ __forceinline__ void wino_epilogue(const TcnParams &p, const f32x16 (
 
 }  // namespace
 
-// p.Tout = T (frames in and out), p.nt = pair columns per segment ((T + 1) / 2 * V), p.w = the transformed weight image
-template <int VT, bool RES = true, int MW = 1>
+// p.Tout = T (frames in and out), p.nt = pair columns per segment ((T + 1) / 2 * V), p.w = the transformed weight image.
+// VALID: the unpadded conv (pad 0) -- the padded conv's output frames [4, T - 4) stored at t - 4.  Pair column (j, v) is the
+// padded form's pair j + 2, so it reads the raw frames 2 j .. 2 j + 9 (the staged span starts at frame 2 ja instead of 2 ja - 4)
+// and stores the frames 2 j, 2 j + 1 of an output of p.Tout = p.Tin - 8 frames; p.nt = (p.Tout + 1) / 2 * V.  Same products in the
+// same order per accumulator element: bit for bit the padded form's frames.
+template <int VT, bool RES = true, int MW = 1, bool VALID = false>
 __global__ __launch_bounds__(NTHREADS, 2) void tcn_stage_wino_kernel(const TcnParams p) {
     constexpr int LDB = wino_ldb<VT, MW>(), MT = WMT * MW, NT = WNT / MW;
     constexpr int NJ = (LDB + 63) / 64;
@@ -206,7 +215,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void tcn_stage_wino_kernel(const TcnPa
     const unsigned wid = xcd_contiguous_id(blockIdx.x, gridDim.x);
     const int m0 = (int)(wid % p.mtiles) * MT, q0 = (int)((wid / p.mtiles) % p.qtiles) * NT;
     const int seg = (int)(wid / (p.mtiles * p.qtiles));
-    const int T = p.Tout, TV = T * VT, QP = p.nt;
+    const int T = VALID ? p.Tin : p.Tout, TV = T * VT, QP = p.nt;    // T: input frames
     const int qend = min(q0 + NT, QP);
     const int ja = div_magic(q0, p.vmagic), jb = div_magic(qend - 1, p.vmagic);
 
@@ -224,7 +233,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void tcn_stage_wino_kernel(const TcnPa
             for (int g = 0; g < 16; ++g) acc[i][mi][g] = 0.f;
 
     {
-        const int fa = 2 * ja - 4;                                   // first raw frame of the tile (pad 4)
+        const int fa = VALID ? 2 * ja : 2 * ja - 4;                  // first raw frame of the tile (pad 4; VALID: pad 0)
         const int span = (2 * (jb - ja) + 10) * VT;
         const int64_t cs = (int64_t)TV;
         const float *seg_base = p.y + (int64_t)seg * p.C * cs;       // 64-bit segment base; 32-bit offsets inside it
@@ -279,7 +288,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void tcn_stage_wino_kernel(const TcnPa
         }
     }
 
-    wino_epilogue<VT, RES>(p, acc, m0 + wm * WMT, q0, qend, seg, wn, l31, kh, jc, vc);
+    wino_epilogue<VT, RES, VALID>(p, acc, m0 + wm * WMT, q0, qend, seg, wn, l31, kh, jc, vc);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -642,6 +651,49 @@ static int tcn_stage_wino_launch(const float *y, const float *w_wino, const floa
     return (int)hipGetLastError();
 }
 
+// the valid form (pad 0, centred identity residual or none) of the stride-1 kernel: csk_tcn_stage_wino_valid_f32; -2 as above.
+// The workgroup shape is picked by the valid form's own column count ((t_in - 7) / 2 pairs per sequence, not (t_in + 1) / 2).
+static int tcn_stage_wino_valid_launch(const float *y, const float *w_wino, const float *x_res, const float *bias, float *out,
+                                       int n_seg, int c, int c_out, int t_in, int V, int k, int stride, int pad, int res_mode,
+                                       int c_res, int t_res, int res_off, int relu, void *stream) {
+    if (!w_wino || !y || !bias || !out) return -2;
+    if (k != 9 || stride != 1 || pad != 0 || t_in < 9) return -2;
+    const bool res = res_mode == CSK_RES_IDENTITY;
+    if (!res && res_mode != CSK_RES_NONE) return -2;
+    if (res && (res_off != 4 || !x_res || c_res != c_out || t_res != t_in)) return -2;
+    if ((V != 25 && V != 18) || c_out % WMT != 0 || c < 1 || n_seg < 1) return -2;
+    if ((int64_t)t_in * V >= (1 << 26)) return -2;                    // 32-bit position / lane byte offsets inside a segment
+    if (csk_diag_flag("CSK_TCN_WINO") && csk_diag_int("CSK_TCN_WINO") < 2) return -2;   // diagnostic A/B switch: the direct kernels
+    const int t_out = t_in - 8;
+    const int qp = (t_out + 1) / 2 * V;
+    const int mw = wino_pick_mw(qp, c_out, stride);
+    const int qtiles = (qp + WNT / mw - 1) / (WNT / mw), mtiles = c_out / (WMT * mw);
+    if ((int64_t)qtiles * mtiles * n_seg >= (1ll << 31)) return -2;
+    TcnParams p = {};
+    p.y = y; p.w = w_wino; p.xres = res ? x_res : nullptr; p.wres = nullptr; p.bias = bias; p.out = out;
+    p.C = c; p.Cpad = round_up(c, CSK_CPAD); p.Cout = c_out; p.Mpad = round_up(c_out, CSK_MT);
+    p.Tin = t_in; p.Tout = t_out; p.V = V; p.K = k; p.stride = 1; p.pad = 0;
+    p.res_mode = res_mode; p.Cres = res ? c_res : 0; p.CresPad = round_up(p.Cres, CSK_CPAD); p.Tres = res ? t_res : 0;
+    p.res_off = res ? 4 : 0; p.relu = relu;
+    p.vmagic = vmagic_of(V); p.mtiles = (unsigned)mtiles; p.qtiles = (unsigned)qtiles; p.nt = qp;
+    void (*kern)(TcnParams);
+    int ldb;
+    if (mw == 2) {
+        kern = res ? (V == 25 ? tcn_stage_wino_kernel<25, true, 2, true> : tcn_stage_wino_kernel<18, true, 2, true>)
+                   : (V == 25 ? tcn_stage_wino_kernel<25, false, 2, true> : tcn_stage_wino_kernel<18, false, 2, true>);
+        ldb = V == 25 ? wino_ldb<25, 2>() : wino_ldb<18, 2>();
+    } else {
+        kern = res ? (V == 25 ? tcn_stage_wino_kernel<25, true, 1, true> : tcn_stage_wino_kernel<18, true, 1, true>)
+                   : (V == 25 ? tcn_stage_wino_kernel<25, false, 1, true> : tcn_stage_wino_kernel<18, false, 1, true>);
+        ldb = V == 25 ? wino_ldb<25>() : wino_ldb<18>();
+    }
+    p.ldb = ldb;
+    const size_t lds = (size_t)(WTAPS * KC * WMT * mw + KC * ldb) * sizeof(float);
+    if (const int e = csk_ensure_lds((const void *)kern, lds)) return e;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(qtiles * mtiles * n_seg)), dim3(NTHREADS), lds, (hipStream_t)stream, p);
+    return (int)hipGetLastError();
+}
+
 // form B of csk_tcn_stage_wino_ext_f32; -2 as above
 static int tcn_stage_wino_s2_launch(const float *y, const float *w_s2, const float *x_res, const float *w_res, const float *bias,
                                     float *out, int n_seg, int c, int c_out, int t_in, int V, int k, int stride, int pad,
@@ -705,6 +757,17 @@ extern "C" int csk_tcn_stage_wino_ext_f32(const float *y, const float *w, const 
     else if (stride == 2)
         rc = tcn_stage_wino_s2_launch(y, w_wino_ext, x_res, w_res, bias, out, n_seg, c, c_out, t_in, V, k, stride, pad, res_mode,
                                       c_res, t_res, res_off, relu, stream);
+    if (rc != -2) return rc;
+    return csk_tcn_stage_f32(y, w, x_res, w_res, bias, out, n_seg, c, c_out, t_in, V, k, stride, pad, res_mode, c_res, t_res,
+                             res_off, relu, stream);
+}
+
+extern "C" int csk_tcn_stage_wino_valid_f32(const float *y, const float *w, const float *x_res, const float *w_res, const float *bias,
+                                            float *out, int n_seg, int c, int c_out, int t_in, int V, int k, int stride, int pad,
+                                            int res_mode, int c_res, int t_res, int res_off, int relu, const float *w_wino,
+                                            void *stream) {
+    const int rc = tcn_stage_wino_valid_launch(y, w_wino, x_res, bias, out, n_seg, c, c_out, t_in, V, k, stride, pad, res_mode,
+                                               c_res, t_res, res_off, relu, stream);
     if (rc != -2) return rc;
     return csk_tcn_stage_f32(y, w, x_res, w_res, bias, out, n_seg, c, c_out, t_in, V, k, stride, pad, res_mode, c_res, t_res,
                              res_off, relu, stream);

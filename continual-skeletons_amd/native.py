@@ -23,6 +23,7 @@ SIGNATURES = {
     "csk_tcn_stage_f32": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     "csk_tcn_stage_wino_f32": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p],
     "csk_tcn_stage_wino_ext_f32": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p],
+    "csk_tcn_stage_wino_valid_f32": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p],
     "csk_block_few_channels_f32": [_p, _p, _p, _p, _p, _p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
     "csk_tcn_stage_splitk_f32": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p],
     "csk_conv1x1_f32": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _l, _l, _l, _l, _p],
@@ -54,6 +55,7 @@ SIGNATURES = {
     "csk_co_plan_destroy": [_p],
     "csk_co_plan_update_weights": [_p, _i, _p, _p, _p, _p, _p],
     "csk_co_plan_set_fusion": [_p, _i],
+    "csk_co_plan_set_delays": [_p, _i, _p],
     "csk_co_plan_cycle": [_p, C.POINTER(C.c_int64), _i, _p, _i, _p, _p, _p, _p, _p],
     "csk_co_scrub_streams_f32": [_p, _i, _p, _i, _i, _p],
     "csk_str_unit_f32": [_p, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _l, _l, _l, _l, _p],

@@ -27,8 +27,8 @@
 extern "C" {
 #endif
 
-/* Stays 16 while entries are only added: csk_derive_modality_f32 / _frames_f32 and csk_prenorm_f32 / _frames_f32 are additive
- * (no existing entry, struct or constant changed). */
+/* Stays 16 while entries are only added: csk_derive_modality_f32 / _frames_f32, csk_prenorm_f32 / _frames_f32,
+ * csk_tcn_stage_wino_valid_f32 and csk_co_plan_set_delays are additive (no existing entry, struct or constant changed). */
 #define CSK_ABI_VERSION 16
 #define CSK_KC 8    /* channel-chunk of the K loop of the TCN kernels                                */
 #define CSK_CPAD 16 /* packed weights zero-pad C_in to a multiple of this                             */
@@ -168,6 +168,23 @@ int csk_tcn_stage_wino_ext_f32(const float *y, const float *w, const float *x_re
                                const float *bias, float *out,
                                int n_seg, int c, int c_out, int t_in, int V, int k, int stride, int pad,
                                int res_mode, int c_res, int t_res, int res_off, int relu, const float *w_wino_ext, void *stream);
+
+/*
+ * The VALID (pad 0) form of the stride-1 Winograd kernel: the temporal conv of the unpadded "*" blocks (SpatioTemporalBlock with
+ * temporal_padding = 0; StGcnMod layers 2-4, 6-7, 9-10).  Arguments as csk_tcn_stage_f32 plus w_wino, the [12][c_pad][c_out_pad]
+ * image of fold.pack_conv_weight_wino -- the SAME image as the padded form's.  For a 9-tap stride-1 conv the unpadded output
+ * frame u is the padded output frame u + 4, and the centred identity residual x[u + 4] has that frame's index: the valid form is
+ * the kernel of csk_tcn_stage_wino_f32 restricted to the output frames [4, t_in - 4) and stored at t - 4 -- pair columns start
+ * at the padded form's pair 2, no column is spent on a halo frame; out is (n_seg, c_out, t_in - 8, V).  Per element the same
+ * products in the same order: bit for bit the padded form's frames [4, t_in - 4) (tests/test_gpu_winograd_valid.py).
+ * Taken when k == 9, stride == 1, pad == 0, t_in >= 9, V in {25, 18}, c_out % 64 == 0, w_wino != NULL and res_mode is NONE, or
+ * IDENTITY with res_off == 4, c_res == c_out, t_res == t_in (a function of the layer, never of n_seg or t_in; the workgroup
+ * shape follows the valid form's own column count).  Any other call runs csk_tcn_stage_f32.
+ */
+int csk_tcn_stage_wino_valid_f32(const float *y, const float *w, const float *x_res, const float *w_res,
+                                 const float *bias, float *out,
+                                 int n_seg, int c, int c_out, int t_in, int V, int k, int stride, int pad,
+                                 int res_mode, int c_res, int t_res, int res_off, int relu, const float *w_wino, void *stream);
 
 /*
  * A whole SpatioTemporalBlock with a FEW input channels and no block residual -- layer 1 of the reference's stacks
@@ -601,6 +618,12 @@ int csk_co_plan_update_weights(csk_co_plan *plan, int n_layers, const csk_co_lay
 /* 1 (default): blocks that qualify advance a 4-frame cycle with one csk_co_block_step_f32 launch instead of a
  * csk_gcn_stage_f32 + csk_tcn_step_f32 pair (bit-identical results); 0: always the two-launch form. */
 int csk_co_plan_set_fusion(csk_co_plan *plan, int enable);
+/* Per-layer emission delay k - 1 - padding of the blocks' temporal convs: layer i emits nothing during its first delays[i]
+ * steps.  A new plan has 4 in every layer (padding "equal", CoST-GCN); the unpadded "*" stacks (CoST-GCN*, padding 0) set 8.
+ * The residual lag stays (k - 1) / 2 = 4 in both families (co.Delay / the centred residual shrink), and so do the ring depths:
+ * an emission reads the k - 1 post-GCN frames behind it and the input frame 4 behind it whatever the delay.  delays is a HOST
+ * array of n_layers values in [4, 8]; it lives in the plan's own layer description (csk_co_layer is unchanged). */
+int csk_co_plan_set_delays(csk_co_plan *plan, int n_layers, const int32_t *delays);
 /* Advance by r = 1..CSK_CO_MAX_CYCLE frames, frames[i] = (N, C, V, M) device pointers.  On return
  * *last_slot / *n_feat describe the last layer's emissions of this cycle (slot of the first, count) and
  * *n_logits how many predictions were written to `logits` ([CSK_CO_MAX_CYCLE][N][classes], slice j = prediction j).
