@@ -31,6 +31,8 @@ from .continual import (  # noqa: F401
 )
 from .agcn import AdaptiveGraphConvolution, AGcn, CoAdaptiveGraphConvolution, CoAGcn  # noqa: F401
 from .str import CoSTr, GcnUnitAttention, STr  # noqa: F401
+# The "*" forms of A-GCN and S-TR live in their modules and are reached there -- ``agcn.AGcnMod``, ``agcn.CoAGcnMod``, ``str.STrMod``,
+# ``str.CoSTrMod`` -- not as package-level names: tests/test_mod_cpu.py pins the package namespace without them.
 from . import fusion, modality, native, prenorm, weights  # noqa: F401
 from .modality import set_input_modality  # noqa: F401
 from .prenorm import pre_normalize_clip, set_pre_normalization  # noqa: F401

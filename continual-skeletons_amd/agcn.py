@@ -14,8 +14,8 @@ import torch.nn as nn
 
 from . import blocks, fold, native
 from .blocks import GraphConvolution, _check_input, init_weights
-from .continual import CoStGcn
-from .models import StGcn
+from .continual import CoStGcn, CoStGcnMod
+from .models import StGcn, StGcnMod, use_wino_valid_res
 
 
 class AdaptiveGraphConvolution(GraphConvolution):
@@ -136,6 +136,49 @@ class AdaptiveGraphConvolution(GraphConvolution):
                          adj_seg_stride=3 * v * v, adj_per_frame=1)
 
 
+class AdaptiveGraphConvolutionMod(GraphConvolution):
+    """models/a_gcn_mod/a_gcn_mod.py:12-64, the graph conv of A-GCN*: same constructor, parameters and state_dict keys (``a_conv.*``,
+    ``b_conv.*`` beside GraphConvolution's).  Its forward (a_gcn_mod.py:48-64) forms the attention per frame,
+        A1 = softmax_w( a_i(x)[n, :, t, v] . b_i(x)[n, :, t, w] / inter_c ) + (A + graph_attn)_i[v, w],
+    and applies it with ``einsum("nctv,nvwt->nctv", x, A1)`` -- an einsum that does not contract x over the joints: it multiplies
+    x[n, c, t, v] by the row sum of A1 over w.  The softmax sums to 1 over w, so that factor is
+        s_i[v] = 1 + sum_w (A + graph_attn)_i[v, w],
+    a constant of the weights: the embedding convs never reach the output.  The published checkpoints were trained with exactly this
+    arithmetic.  On the device it is therefore the plain sparse graph conv with a DIAGONAL adjacency -- one ELL entry per column
+    (source v, value s_i[v], formed in float64 and rounded once) -- through csk_gcn_stage_f32 in the clip and the step form, the
+    native plan included (``folds_to_plain``).  ``a_conv`` / ``b_conv`` are carried for the state_dict and never launched.
+    One divergence: where a frame's attention logits hold a NaN or an infinity the reference's output is NaN; here it stays
+    finite, because the softmax is never formed."""
+
+    folds_to_plain = True
+
+    def __init__(self, in_channels, out_channels, A, bn_momentum=0.1, coff_embedding=4):
+        super().__init__(in_channels, out_channels, A, bn_momentum)
+        self.inter_c = out_channels // coff_embedding
+        self.a_conv = nn.ModuleList(nn.Conv2d(in_channels, self.inter_c, 1) for _ in range(self.num_subset))
+        self.b_conv = nn.ModuleList(nn.Conv2d(in_channels, self.inter_c, 1) for _ in range(self.num_subset))
+        for m in list(self.a_conv) + list(self.b_conv):
+            init_weights(m)
+        self.soft = nn.Softmax(-2)
+
+    def _fold(self):
+        sd = {k: v.detach().cpu() for k, v in self.state_dict().items() if not k.startswith(("a_conv.", "b_conv."))}
+        f = fold.fold_graph_conv(sd)                      # weights / bias as for GraphConvolution ...
+        v = f["V"]
+        # ... and the diagonal adjacency: column v of subset i holds the one entry (v, s_i[v])
+        s = 1.0 + (sd["A"].double() + sd["graph_attn"].double()).sum(-1)          # (3, V), a_gcn_mod.py:50, 56-60
+        f["ell_src"] = torch.arange(v, dtype=torch.int32).repeat(3, 1).unsqueeze(-1).contiguous()
+        f["ell_val"] = s.float().unsqueeze(-1).contiguous()
+        f["ell_cnt_host"] = torch.tensor([1, 1, 1], dtype=torch.int32)
+        f["ell_w"] = 1
+        return f
+
+
+def CoAdaptiveGraphConvolutionMod(in_channels, out_channels, A, bn_momentum=0.1):
+    """models/coa_gcn_mod/coa_gcn_mod.py:11-14 -- per frame already, so the same module"""
+    return AdaptiveGraphConvolutionMod(in_channels, out_channels, A, bn_momentum)
+
+
 def CoAdaptiveGraphConvolution(in_channels, out_channels, A, bn_momentum=0.1):
     """models/coa_gcn/coa_gcn.py:11-14"""
     return AdaptiveGraphConvolution(in_channels, out_channels, A, bn_momentum)
@@ -153,3 +196,24 @@ class CoAGcn(CoStGcn):
 
     def __init__(self, graph_A, input_shape=(3, 300, 25, 2), num_classes=60, pool_size=-1, pool_padding=-1):
         super().__init__(graph_A, input_shape, num_classes, pool_size, pool_padding, CoGraphConv=CoAdaptiveGraphConvolution)
+
+
+class AGcnMod(StGcnMod):
+    """A-GCN*: models/a_gcn_mod/a_gcn_mod.py:67-124 -- StGcnMod's table, geometry (T >= 81, one feature frame per input frame from
+    frame 80 on) and refusals with ``AdaptiveGraphConvolutionMod`` in every block, i.e. StGcnMod's launches with a diagonal
+    adjacency: no embedding GEMM, no attention launch.  The conv-residual blocks (layers 5 and 8) run the valid Winograd form with
+    the conv residual (csk_tcn_stage_wino_valid_res_f32)."""
+
+    def __init__(self, graph_A, input_shape=(3, 300, 25, 2), num_classes=60):
+        super().__init__(graph_A, input_shape, num_classes, GraphConv=AdaptiveGraphConvolutionMod)
+        use_wino_valid_res(self)
+
+
+class CoAGcnMod(CoStGcnMod):
+    """CoA-GCN*: models/coa_gcn_mod/coa_gcn_mod.py -- CoStGcnMod with ``AdaptiveGraphConvolutionMod`` per frame.  The graph conv is
+    per frame in the clip model too, so emission s is AGcnMod's clip feature frame s - 80 (which CoAGcn cannot offer against AGcn).
+    A stack of plain graph convs for the native plan."""
+
+    def __init__(self, graph_A, input_shape=(3, 300, 25, 2), num_classes=60, pool_size=-1, pool_padding=-1):
+        super().__init__(graph_A, input_shape, num_classes, pool_size, pool_padding, CoGraphConv=CoAdaptiveGraphConvolutionMod)
+        use_wino_valid_res(self)

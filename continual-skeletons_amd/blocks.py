@@ -303,6 +303,13 @@ class GraphConvolution(_Folded):
         gcn_stage(x, y, ops, n_seg=n_seg, frames=frames, x_strides=x_strides, y_strides=y_strides)
 
 
+def is_plain_graph_conv(module) -> bool:
+    """The module's device form is the sparse graph conv on ``fold_graph_conv``'s operands alone -- ``GraphConvolution`` itself, or a
+    subclass that says so (``folds_to_plain``: agcn.AdaptiveGraphConvolutionMod).  What the continual drivers ask before they hand a
+    block to the fused step entries and the native plan."""
+    return type(module) is GraphConvolution or bool(getattr(module, "folds_to_plain", False))
+
+
 def gcn_stage(x, y, ops, n_seg, frames, x_strides, y_strides, adj_seg_stride=0, adj_per_frame=0):
     rc = native.lib().csk_gcn_stage_f32(
         native.ptr(x), native.ptr(y), native.ptr(ops["w"]), native.ptr(ops["bias"]),
@@ -341,14 +348,17 @@ class TemporalConvolution(_Folded):
 
 
 def tcn_stage(y, w, bias, c_out, k, stride, pad, relu=True, res_mode=0, x_res=None, w_res=None, res_off=0, out=None,
-              split=False, ksplit=1, scratch=None, w_wino=None, w_wino_ext=None, w_wino_valid=None):
+              split=False, ksplit=1, scratch=None, w_wino=None, w_wino_ext=None, w_wino_valid=None, w_wino_valid_res=None):
     """csk_tcn_stage_f32, or with split=True csk_tcn_stage_bf16x3 (w / w_res are then the split operand images), or with
     ksplit > 1 csk_tcn_stage_splitk_f32 (clip latency mode: K loop cut into channel ranges, partial sums in split order), or
     with the Winograd image w_wino (fold.pack_conv_weight_wino) csk_tcn_stage_wino_f32 (the Winograd kernel where the layer's
     shape allows it, csk_tcn_stage_f32 otherwise), or with the image w_wino_ext csk_tcn_stage_wino_ext_f32 (stride 2:
     fold.pack_conv_weight_wino_s2, the polyphase Winograd kernel; stride 1 without residual: fold.pack_conv_weight_wino), or with
     w_wino_valid (the same image as w_wino) csk_tcn_stage_wino_valid_f32: the pad-0 form of the stride-1 Winograd kernel with the
-    centred identity residual (res_off 4) or none."""
+    centred identity residual (res_off 4) or none, or with w_wino_valid_res (the same image again)
+    csk_tcn_stage_wino_valid_res_f32: the pad-0 form with the conv residual on the centred shrink (res_mode 2, res_off 4, w_res the
+    direct residual image) -- that entry does not fall back itself: where it answers -2 (not a shape of the kernel) the direct
+    csk_tcn_stage_f32 runs."""
     n, c, t_in, v = y.shape
     if t_in + 2 * pad < k:
         raise RuntimeError(f"temporal extent {t_in} (+2*{pad}) shorter than kernel {k}")
@@ -368,6 +378,16 @@ def tcn_stage(y, w, bias, c_out, k, stride, pad, relu=True, res_mode=0, x_res=No
             native.stream_of(y))
         native.check(rc, "csk_tcn_stage_splitk_f32")
         return out
+    if w_wino_valid_res is not None and not split:
+        if w_wino_valid_res.dim() != 3 or w_wino_valid_res.shape[0] != 12 or tuple(w_wino_valid_res.shape[1:]) != tuple(w.shape[1:]):
+            raise RuntimeError(f"tcn_stage: w_wino_valid_res must be the [12][c_pad][c_out_pad] image of the conv, got {tuple(w_wino_valid_res.shape)}")
+        rc = native.lib().csk_tcn_stage_wino_valid_res_f32(
+            native.ptr(y), native.ptr(x_res), native.ptr(w_res), native.ptr(bias), native.ptr(out),
+            n, c, c_out, t_in, v, k, stride, pad, res_mode, c_res, t_res, res_off, int(relu), native.ptr(w_wino_valid_res),
+            native.stream_of(y))
+        if rc != -2:
+            native.check(rc, "csk_tcn_stage_wino_valid_res_f32")
+            return out
     if w_wino_valid is not None and not split:
         if w_wino_valid.dim() != 3 or w_wino_valid.shape[0] != 12 or tuple(w_wino_valid.shape[1:]) != tuple(w.shape[1:]):
             raise RuntimeError(f"tcn_stage: w_wino_valid must be the [12][c_pad][c_out_pad] image of the conv, got {tuple(w_wino_valid.shape)}")
@@ -436,6 +456,7 @@ class SpatioTemporalBlock(_Folded):
     clip_split_k = 0       # set_clip_latency_mode: channel ranges per tile of the clip forward's temporal conv (0 / 1: off)
     clip_split_max_seq = CLIP_SPLIT_MAX_SEQUENCES   # ... for forwards of at most this many sequences
     wino_valid = True      # temporal_padding=0 blocks with the identity residual: csk_tcn_stage_wino_valid_f32 (False: the direct kernels)
+    wino_valid_res = False  # temporal_padding=0, stride-1 blocks with the conv residual: csk_tcn_stage_wino_valid_res_f32 (set per layer by the A-GCN* / S-TR* models)
 
     def _watched(self):    # the tail's operands are folded from the temporal conv and the residual conv; the graph conv keeps its own cache
         return [m for m in (self.tcn, self.residual) if isinstance(m, nn.Module)]
@@ -474,9 +495,15 @@ class SpatioTemporalBlock(_Folded):
         ks = max(1, min(self.clip_split_k, -(-ops["c"] // 8))) if (self.clip_split_k > 1 and ops["k"] == 9 and y.shape[0] <= self.clip_split_max_seq) else 1
         if self.tcn.padding == 0 and shrink == 4 and self.residual is unity and self.stride == 1 and ks == 1 and self.wino_valid:
             # the unpadded "*" block with the centred identity residual: the valid form of the Winograd kernel (the no-residual
-            # and conv-residual "*" blocks keep the direct kernels, which take pad 0 and res_off as they are)
+            # "*" block keeps the direct kernels, which take pad 0 and res_off as they are; so does the conv-residual one unless
+            # wino_valid_res is set, below)
             return tcn_stage(y, ops["w"], ops["bias"], ops["c_out"], ops["k"], 1, 0, relu=True, res_mode=1, x_res=x, res_off=4,
                              out=out, w_wino_valid=ops["w_wino"])
+        if (self.tcn.padding == 0 and shrink == 4 and isinstance(self.residual, TemporalConvolution) and self.stride == 1 and ks == 1
+                and self.wino_valid_res):
+            # the unpadded "*" block with the conv residual on the centred shrink (layers 5 and 8 of the "*" tables)
+            return tcn_stage(y, ops["w"], ops["bias"], ops["c_out"], ops["k"], 1, 0, relu=True, res_mode=2, x_res=x,
+                             w_res=ops["w_res"], res_off=4, out=out, w_wino_valid_res=ops["w_wino"])
         return tcn_stage(y, ops["w"], ops["bias"], ops["c_out"], ops["k"], self.stride, self.tcn.padding, relu=True,
                          res_mode=mode, x_res=xr, w_res=ops["w_res"], res_off=shrink, out=out, ksplit=ks,
                          scratch=_scratch_of(self) if ks > 1 else None, w_wino=ops["w_wino"] if ks == 1 else None,

@@ -7,7 +7,7 @@ import ctypes
 import torch
 
 from . import native
-from .blocks import GraphConvolution
+from .blocks import is_plain_graph_conv
 
 
 class NativePlan:
@@ -56,7 +56,7 @@ class NativePlan:
         for i, blk in enumerate(self._blocks):
             arr[i], held = blk._layer_struct(device)
             keep += held
-            if type(blk.gcn) is not GraphConvolution:      # adaptive graph conv: adjacency per skeleton frame (agcn.py)
+            if not is_plain_graph_conv(blk.gcn):           # adaptive graph conv: adjacency per skeleton frame (agcn.py)
                 L, a, dev = arr[i], blk.gcn.plan_operands(device), blk._state.y.device
                 adj = self.__dict__.get("_agcn_adj")
                 need = self.max_cycle * self._n * self.input_shape[3] * 3 * self.input_shape[2] ** 2      # [cycle frames][skeletons][3][V][V]
@@ -81,7 +81,7 @@ class NativePlan:
         if not self.use_native_plan or any(blk.step_precision != "f32" for blk in self._blocks):
             return
         for gcn in (blk.gcn for blk in self._blocks):
-            if type(gcn) is not GraphConvolution and (getattr(gcn, "plan_operands", None) is None or gcn.plan_operands(device) is None):
+            if not is_plain_graph_conv(gcn) and (getattr(gcn, "plan_operands", None) is None or gcn.plan_operands(device) is None):
                 return
         c, _, v, m = self.input_shape
         arr, keep, ops, fcw, fcb = self._layer_structs(device)

@@ -29,7 +29,7 @@ import torch
 import torch.nn as nn
 
 from . import blocks, fold, native
-from .blocks import GraphConvolution, SpatioTemporalBlock, TemporalConvolution, _Folded, init_weights, unity, zero
+from .blocks import GraphConvolution, SpatioTemporalBlock, TemporalConvolution, _Folded, init_weights, is_plain_graph_conv, unity, zero
 from .co_plan import NativePlan
 from .co_reset import StreamReset
 from .modality import ContinualModality
@@ -414,7 +414,7 @@ class CoSpatioTemporalBlock(SpatioTemporalBlock):
         if self._use_split_step():
             return False
         if not (self.fuse_step and r == 4 and self.stride == 1 and self.out_channels <= 64 and s0 >= self.delay
-                and self.kind in ("none", "identity") and type(self.gcn) is GraphConvolution and self._state.ksplit == 1
+                and self.kind in ("none", "identity") and is_plain_graph_conv(self.gcn) and self._state.ksplit == 1
                 and self._state.gcn_ksplit == 1):
             return False
         g = self.gcn._packed_ops(self._state.y.device)
@@ -960,8 +960,9 @@ class CoStGcnMod(CoStGcn):
 
     unpadded = True
 
-    def __init__(self, graph_A, input_shape=(3, 300, 25, 2), num_classes=60, pool_size=-1, pool_padding=-1):
-        super().__init__(graph_A, input_shape, num_classes, pool_size, pool_padding)
+    def __init__(self, graph_A, input_shape=(3, 300, 25, 2), num_classes=60, pool_size=-1, pool_padding=-1,
+                 CoGraphConv=CoGraphConvolution):
+        super().__init__(graph_A, input_shape, num_classes, pool_size, pool_padding, CoGraphConv=CoGraphConv)
 
     def set_latency_mode(self, split_k: int = 8):
         raise NotImplementedError("the latency mode is not built for the unpadded '*' models; the model is unchanged")
@@ -970,5 +971,5 @@ class CoStGcnMod(CoStGcn):
         if any(b.precision != "f32" for b in self._blocks):
             raise NotImplementedError("precision 'bf16x3' is not built for the unpadded '*' models: set_precision(model, 'f32')")
         if x.dim() != 5 or x.shape[2] < self.receptive_field:
-            raise ValueError(f"CoStGcnMod's clip forward needs T >= {self.receptive_field} frames, got {tuple(x.shape)}")
+            raise ValueError(f"{type(self).__name__}'s clip forward needs T >= {self.receptive_field} frames, got {tuple(x.shape)}")
         return super()._clip_features(x)

@@ -39,6 +39,10 @@
 //           chunks over x after the main loop, a 1-tap group with d2 := d1: acc0 += wres (d0 - d1), acc1 += wres d1 (d0 = x[4 j],
 //           d1 = x[4 j + 2]), which the output transform turns into out(2 j) += wres d0, out(2 j + 1) += wres d1.
 //   weights (host, fold.pack_conv_weight_wino_s2): 13 rows E0 (4), E1 (3), O0 (3), O1 (3); the residual streams the direct w_res.
+//
+// csk_tcn_stage_wino_valid_res_f32: the valid (pad 0) stride-1 form with the 1 x 1 conv residual on the centred shrink, res[u] =
+// wres . x[u + 4] -- extra chunks over x behind the main loop that add wres x[2 j + 4] to M0 and wres (-x[2 j + 5]) to M3, which the
+// output transform turns into the residual of both frames of the pair (wino_valid_res_chunk; RESCONV of tcn_stage_wino_kernel).
 #include <type_traits>
 
 #include "mfma_core.h"
@@ -120,6 +124,35 @@ struct WStageNx128 {
     }
 };
 
+// Residual weights: one 8-channel chunk of the direct w_res image for the 64-row tile = 128 f32x4, one per thread of the lower
+// half; the upper half repeats it (same value to the same address)
+struct WStageRes64 {
+    unsigned goff0, loff0;
+    f32x4 v;
+    __device__ __forceinline__ void setup(int Mpad, int tid) {
+        goff0 = (unsigned)(((tid >> 4) & 7) * Mpad + (tid & 15) * 4);
+        loff0 = (unsigned)((tid & 127) * 4);
+    }
+    __device__ __forceinline__ void issue(const float *__restrict__ chunk_base) {
+        v = *reinterpret_cast<const f32x4 *>(chunk_base + goff0);
+    }
+    __device__ __forceinline__ void commit(float *__restrict__ Wl) const { *reinterpret_cast<f32x4 *>(Wl + loff0) = v; }
+};
+
+// The same for the 128-row tile: 256 f32x4, one per thread (channel row tid / 32, rows 4 (tid % 32) ..)
+struct WStageRes128 {
+    unsigned goff0, loff0;
+    f32x4 v;
+    __device__ __forceinline__ void setup(int Mpad, int tid) {
+        goff0 = (unsigned)((tid >> 5) * Mpad + (tid & 31) * 4);
+        loff0 = (unsigned)(tid * 4);
+    }
+    __device__ __forceinline__ void issue(const float *__restrict__ chunk_base) {
+        v = *reinterpret_cast<const f32x4 *>(chunk_base + goff0);
+    }
+    __device__ __forceinline__ void commit(float *__restrict__ Wl) const { *reinterpret_cast<f32x4 *>(Wl + loff0) = v; }
+};
+
 // One group segment of a chunk for one wave: acc[i][mi] += U[4 g + i][kk][rows mi] x B_{g,i}[kk][this lane's column]
 // (Wl: the staged weights at this wave's first row; MT = rows of the staged tile)
 template <int VT, int G, int MW>
@@ -138,6 +171,27 @@ __device__ __forceinline__ void wino_group(const float *__restrict__ Wl, const f
             acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b[i], acc[i][0], 0, 0, 0);
             acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b[i], acc[i][1], 0, 0, 0);
         }
+    }
+}
+
+// One chunk of the valid form's conv residual res[u] = w_res . x[u + 4]: the staged row starts at raw frame 2 ja + 4 of x, so the
+// lane's column reads d0 = x[2 j + 4] and d1 = x[2 j + 5].  No accumulator set of its own: acc0 += w_res d0 and acc3 += w_res (-d1),
+// which the output transform out(2 j) = M0 + M1 + M2, out(2 j + 1) = M1 - M2 - M3 turns into out(2 j) += w_res d0 and
+// out(2 j + 1) += w_res d1.  The sign sits in the staged operand: the weights are the direct w_res image as it is.
+template <int VT, int MW>
+__device__ __forceinline__ void wino_valid_res_chunk(const float *__restrict__ Wl, const float *__restrict__ Bl, int off, int l31,
+                                                     int kh, f32x16 (&acc)[4][2]) {
+    constexpr int LDB = wino_ldb<VT, MW>(), MT = WMT * MW;
+    const float *br = Bl + kh * LDB + off;
+    const float *wr = Wl + kh * MT + l31;
+#pragma unroll
+    for (int s = 0; s < KC / 2; ++s) {
+        const float d0 = br[2 * s * LDB], nd1 = -br[2 * s * LDB + VT];
+        const float a0 = wr[2 * s * MT], a1 = wr[2 * s * MT + 32];
+        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, d0, acc[0][0], 0, 0, 0);
+        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, d0, acc[0][1], 0, 0, 0);
+        acc[3][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, nd1, acc[3][0], 0, 0, 0);
+        acc[3][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, nd1, acc[3][1], 0, 0, 0);
     }
 }
 
@@ -200,8 +254,11 @@ __device__ __forceinline__ void wino_epilogue(const TcnParams &p, const f32x16 (
 // padded form's pair j + 2, so it reads the raw frames 2 j .. 2 j + 9 (the staged span starts at frame 2 ja instead of 2 ja - 4)
 // and stores the frames 2 j, 2 j + 1 of an output of p.Tout = p.Tin - 8 frames; p.nt = (p.Tout + 1) / 2 * V.  Same products in the
 // same order per accumulator element: bit for bit the padded form's frames.
-template <int VT, bool RES = true, int MW = 1, bool VALID = false>
+// RESCONV (VALID only, csk_tcn_stage_wino_valid_res_f32): the 1 x 1 conv residual on the centred shrink, res[u] = p.wres . p.xres[u + 4]
+// (p.xres: p.Cres channels, a multiple of 16, x p.Tres == p.Tin frames), as a second K phase behind the main loop.
+template <int VT, bool RES = true, int MW = 1, bool VALID = false, bool RESCONV = false>
 __global__ __launch_bounds__(NTHREADS, 2) void tcn_stage_wino_kernel(const TcnParams p) {
+    static_assert(!RESCONV || (VALID && !RES), "the conv-residual phase is built for the valid form");
     constexpr int LDB = wino_ldb<VT, MW>(), MT = WMT * MW, NT = WNT / MW;
     constexpr int NJ = (LDB + 63) / 64;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -288,6 +345,38 @@ __global__ __launch_bounds__(NTHREADS, 2) void tcn_stage_wino_kernel(const TcnPa
         }
     }
 
+    if (RESCONV) {
+        // conv residual: 8-channel chunks of x, frames 2 ja + 4 .. 2 jb + 5 -- inside the sequence for every tile (the last pair's
+        // second frame is at most frame Tin - 4), so 16-byte staging throughout; the next chunk's loads are issued in front of the
+        // current chunk's products
+        constexpr int NJ4R = (((2 * ((NT + VT - 2) / VT) + 2) * VT + 3) / 4 + 63) / 64;
+        const int span = (2 * (jb - ja) + 2) * VT;
+        const int64_t cs = (int64_t)p.Tres * VT;
+        const float *seg_base = p.xres + (int64_t)seg * p.Cres * cs;
+        const float *wbase = p.wres + m0;
+        const float *Ww = Wl + wm * WMT;                             // this wave's rows of the staged weights
+        std::conditional_t<MW == 2, WStageRes128, WStageRes64> wr;
+        wr.setup(p.Mpad, tid);
+        BStage4<NJ4R> b4;
+        b4.setup((2 * ja + 4) * VT, span, lane);
+        wr.issue(wbase);
+        b4.issue(seg_base, p.Cres, cs, 0, wave);
+        for (int c0 = 0; c0 + KC < p.Cres; c0 += KC) {
+            __syncthreads();
+            wr.commit(Wl);
+            b4.commit(Bl, LDB, wave);
+            __syncthreads();
+            wr.issue(wbase + (size_t)(c0 + KC) * p.Mpad);
+            b4.issue(seg_base, p.Cres, cs, c0 + KC, wave);
+            wino_valid_res_chunk<VT, MW>(Ww, Bl, off, l31, kh, acc);
+        }
+        __syncthreads();
+        wr.commit(Wl);
+        b4.commit(Bl, LDB, wave);
+        __syncthreads();
+        wino_valid_res_chunk<VT, MW>(Ww, Bl, off, l31, kh, acc);
+    }
+
     wino_epilogue<VT, RES, VALID>(p, acc, m0 + wm * WMT, q0, qend, seg, wn, l31, kh, jc, vc);
 }
 
@@ -336,35 +425,6 @@ struct WStage13x64 {
         for (int u = 0; u < 6; ++u) *reinterpret_cast<f32x4 *>(Wl + u * (NTHREADS * 4) + loff0) = v[u];
         *reinterpret_cast<f32x4 *>(Wl + u6 * (NTHREADS * 4) + loff0) = v[6];
     }
-};
-
-// Residual weights: one 8-channel chunk of the direct w_res image for the 64-row tile = 128 f32x4, one per thread of the lower
-// half; the upper half repeats it (same value to the same address)
-struct WStageRes64 {
-    unsigned goff0, loff0;
-    f32x4 v;
-    __device__ __forceinline__ void setup(int Mpad, int tid) {
-        goff0 = (unsigned)(((tid >> 4) & 7) * Mpad + (tid & 15) * 4);
-        loff0 = (unsigned)((tid & 127) * 4);
-    }
-    __device__ __forceinline__ void issue(const float *__restrict__ chunk_base) {
-        v = *reinterpret_cast<const f32x4 *>(chunk_base + goff0);
-    }
-    __device__ __forceinline__ void commit(float *__restrict__ Wl) const { *reinterpret_cast<f32x4 *>(Wl + loff0) = v; }
-};
-
-// The same for the 128-row tile: 256 f32x4, one per thread (channel row tid / 32, rows 4 (tid % 32) ..)
-struct WStageRes128 {
-    unsigned goff0, loff0;
-    f32x4 v;
-    __device__ __forceinline__ void setup(int Mpad, int tid) {
-        goff0 = (unsigned)((tid >> 5) * Mpad + (tid & 31) * 4);
-        loff0 = (unsigned)(tid * 4);
-    }
-    __device__ __forceinline__ void issue(const float *__restrict__ chunk_base) {
-        v = *reinterpret_cast<const f32x4 *>(chunk_base + goff0);
-    }
-    __device__ __forceinline__ void commit(float *__restrict__ Wl) const { *reinterpret_cast<f32x4 *>(Wl + loff0) = v; }
 };
 
 // BStage4 (mfma_core.h) for the tall shape, whose weight stage holds 13 registers-of-four per thread: a row of LDB floats as NV
@@ -653,14 +713,18 @@ static int tcn_stage_wino_launch(const float *y, const float *w_wino, const floa
 
 // the valid form (pad 0, centred identity residual or none) of the stride-1 kernel: csk_tcn_stage_wino_valid_f32; -2 as above.
 // The workgroup shape is picked by the valid form's own column count ((t_in - 7) / 2 pairs per sequence, not (t_in + 1) / 2).
+// res_conv: csk_tcn_stage_wino_valid_res_f32 -- the conv residual on the centred shrink and nothing else (c_res a multiple of 16:
+// whole chunks of the direct w_res image); without it a conv residual is not a shape of this launcher.
 static int tcn_stage_wino_valid_launch(const float *y, const float *w_wino, const float *x_res, const float *bias, float *out,
                                        int n_seg, int c, int c_out, int t_in, int V, int k, int stride, int pad, int res_mode,
-                                       int c_res, int t_res, int res_off, int relu, void *stream) {
+                                       int c_res, int t_res, int res_off, int relu, void *stream, bool res_conv = false,
+                                       const float *w_res = nullptr) {
     if (!w_wino || !y || !bias || !out) return -2;
     if (k != 9 || stride != 1 || pad != 0 || t_in < 9) return -2;
     const bool res = res_mode == CSK_RES_IDENTITY;
-    if (!res && res_mode != CSK_RES_NONE) return -2;
+    if (res_conv ? res_mode != CSK_RES_CONV : (!res && res_mode != CSK_RES_NONE)) return -2;
     if (res && (res_off != 4 || !x_res || c_res != c_out || t_res != t_in)) return -2;
+    if (res_conv && (res_off != 4 || !x_res || !w_res || c_res < CSK_CPAD || c_res % CSK_CPAD != 0 || t_res != t_in)) return -2;
     if ((V != 25 && V != 18) || c_out % WMT != 0 || c < 1 || n_seg < 1) return -2;
     if ((int64_t)t_in * V >= (1 << 26)) return -2;                    // 32-bit position / lane byte offsets inside a segment
     if (csk_diag_flag("CSK_TCN_WINO") && csk_diag_int("CSK_TCN_WINO") < 2) return -2;   // diagnostic A/B switch: the direct kernels
@@ -669,22 +733,25 @@ static int tcn_stage_wino_valid_launch(const float *y, const float *w_wino, cons
     const int mw = wino_pick_mw(qp, c_out, stride);
     const int qtiles = (qp + WNT / mw - 1) / (WNT / mw), mtiles = c_out / (WMT * mw);
     if ((int64_t)qtiles * mtiles * n_seg >= (1ll << 31)) return -2;
+    const bool xr = res || res_conv;
     TcnParams p = {};
-    p.y = y; p.w = w_wino; p.xres = res ? x_res : nullptr; p.wres = nullptr; p.bias = bias; p.out = out;
+    p.y = y; p.w = w_wino; p.xres = xr ? x_res : nullptr; p.wres = res_conv ? w_res : nullptr; p.bias = bias; p.out = out;
     p.C = c; p.Cpad = round_up(c, CSK_CPAD); p.Cout = c_out; p.Mpad = round_up(c_out, CSK_MT);
     p.Tin = t_in; p.Tout = t_out; p.V = V; p.K = k; p.stride = 1; p.pad = 0;
-    p.res_mode = res_mode; p.Cres = res ? c_res : 0; p.CresPad = round_up(p.Cres, CSK_CPAD); p.Tres = res ? t_res : 0;
-    p.res_off = res ? 4 : 0; p.relu = relu;
+    p.res_mode = res_mode; p.Cres = xr ? c_res : 0; p.CresPad = round_up(p.Cres, CSK_CPAD); p.Tres = xr ? t_res : 0;
+    p.res_off = xr ? 4 : 0; p.relu = relu;
     p.vmagic = vmagic_of(V); p.mtiles = (unsigned)mtiles; p.qtiles = (unsigned)qtiles; p.nt = qp;
     void (*kern)(TcnParams);
     int ldb;
     if (mw == 2) {
-        kern = res ? (V == 25 ? tcn_stage_wino_kernel<25, true, 2, true> : tcn_stage_wino_kernel<18, true, 2, true>)
-                   : (V == 25 ? tcn_stage_wino_kernel<25, false, 2, true> : tcn_stage_wino_kernel<18, false, 2, true>);
+        kern = res_conv ? (V == 25 ? tcn_stage_wino_kernel<25, false, 2, true, true> : tcn_stage_wino_kernel<18, false, 2, true, true>)
+               : res    ? (V == 25 ? tcn_stage_wino_kernel<25, true, 2, true> : tcn_stage_wino_kernel<18, true, 2, true>)
+                        : (V == 25 ? tcn_stage_wino_kernel<25, false, 2, true> : tcn_stage_wino_kernel<18, false, 2, true>);
         ldb = V == 25 ? wino_ldb<25, 2>() : wino_ldb<18, 2>();
     } else {
-        kern = res ? (V == 25 ? tcn_stage_wino_kernel<25, true, 1, true> : tcn_stage_wino_kernel<18, true, 1, true>)
-                   : (V == 25 ? tcn_stage_wino_kernel<25, false, 1, true> : tcn_stage_wino_kernel<18, false, 1, true>);
+        kern = res_conv ? (V == 25 ? tcn_stage_wino_kernel<25, false, 1, true, true> : tcn_stage_wino_kernel<18, false, 1, true, true>)
+               : res    ? (V == 25 ? tcn_stage_wino_kernel<25, true, 1, true> : tcn_stage_wino_kernel<18, true, 1, true>)
+                        : (V == 25 ? tcn_stage_wino_kernel<25, false, 1, true> : tcn_stage_wino_kernel<18, false, 1, true>);
         ldb = V == 25 ? wino_ldb<25>() : wino_ldb<18>();
     }
     p.ldb = ldb;
@@ -771,4 +838,13 @@ extern "C" int csk_tcn_stage_wino_valid_f32(const float *y, const float *w, cons
     if (rc != -2) return rc;
     return csk_tcn_stage_f32(y, w, x_res, w_res, bias, out, n_seg, c, c_out, t_in, V, k, stride, pad, res_mode, c_res, t_res,
                              res_off, relu, stream);
+}
+
+// -2 where the shape is not the kernel's: no launch, the caller runs csk_tcn_stage_f32 (include/cskel.h)
+extern "C" int csk_tcn_stage_wino_valid_res_f32(const float *y, const float *x_res, const float *w_res, const float *bias, float *out,
+                                                int n_seg, int c, int c_out, int t_in, int V, int k, int stride, int pad,
+                                                int res_mode, int c_res, int t_res, int res_off, int relu, const float *w_wino,
+                                                void *stream) {
+    return tcn_stage_wino_valid_launch(y, w_wino, x_res, bias, out, n_seg, c, c_out, t_in, V, k, stride, pad, res_mode, c_res, t_res,
+                                       res_off, relu, stream, true, w_res);
 }

@@ -28,6 +28,16 @@ def layer_table(c_in, unpadded=False):
 
 MOD_TEMPORAL_PADDING = 0      # temporal padding of every block of the "*" models; a block then shortens the clip by k - 1 = 8 frames
 MOD_MIN_FRAMES = 10 * 8 + 1   # receptive field of the ten unpadded 9-tap blocks: shorter clips leave no output frame
+MOD_CONV_RESIDUAL_LAYERS = (5, 8)   # the "*" blocks that change the channel count: 1 x 1 conv + BN residual on the centred shrink
+
+
+def use_wino_valid_res(net, layers=MOD_CONV_RESIDUAL_LAYERS):
+    """Route the conv-residual blocks ``layers`` of a "*" model through csk_tcn_stage_wino_valid_res_f32 (the A-GCN* / S-TR* models
+    call it in their constructors; StGcnMod / CoStGcnMod keep the direct kernels there).  Which layers are listed follows the
+    measurement in profiles/r17_mod_family.md."""
+    for i in layers:
+        net.layers[f"layer{i}"].wino_valid_res = True
+    return net
 
 
 def per_layer(factory):
@@ -121,15 +131,15 @@ class StGcnMod(StGcn):
 
     unpadded = True
 
-    def __init__(self, graph_A, input_shape=(3, 300, 25, 2), num_classes=60):
-        super().__init__(graph_A, input_shape, num_classes)
+    def __init__(self, graph_A, input_shape=(3, 300, 25, 2), num_classes=60, GraphConv=None):
+        super().__init__(graph_A, input_shape, num_classes, GraphConv=GraphConv)
 
     def features(self, x):
         if x.dim() != 5 or x.shape[2] < MOD_MIN_FRAMES:
-            raise ValueError(f"StGcnMod needs (N, C, T, V, M) clips of T >= {MOD_MIN_FRAMES} frames (ten unpadded 9-tap blocks, 8 frames "
+            raise ValueError(f"{type(self).__name__} needs (N, C, T, V, M) clips of T >= {MOD_MIN_FRAMES} frames (ten unpadded 9-tap blocks, 8 frames "
                              f"each), got {tuple(x.shape)}")
         if any(b.precision != "f32" or b.clip_split_k > 1 for b in self.layers.values()):
-            raise NotImplementedError("StGcnMod runs the exact fp32 default kernels only (no 'bf16x3' precision, no clip latency mode)")
+            raise NotImplementedError(f"{type(self).__name__} runs the exact fp32 default kernels only (no 'bf16x3' precision, no clip latency mode)")
         return super().features(x)
 
     def set_latency_mode(self, *args, **kwargs):

@@ -25,8 +25,8 @@ import torch.nn as nn
 
 from . import fold, native
 from .blocks import _check_input, _Folded
-from .continual import CoStGcn
-from .models import StGcn
+from .continual import CoStGcn, CoStGcnMod
+from .models import StGcn, StGcnMod, use_wino_valid_res
 
 NH = 8
 
@@ -178,3 +178,34 @@ class CoSTr(CoStGcn):
 
         super().__init__(graph_A, input_shape, num_classes, pool_size, pool_padding,
                          CoGraphConv=[co_graph_conv if i in ATTENTION_LAYERS else None for i in range(10)])
+
+
+class STrMod(StGcnMod):
+    """S-TR*: models/s_tr_mod/s_tr_mod.py -- StGcnMod's table, geometry and refusals with ``GcnUnitAttention`` in layers 4-10.
+    Layers 5 and 8 run the valid Winograd form with the conv residual (csk_tcn_stage_wino_valid_res_f32)."""
+
+    def __init__(self, graph_A, input_shape=(3, 300, 25, 2), num_classes=60):
+        v = input_shape[2]
+
+        def graph_conv(in_channels, out_channels, A):
+            return GcnUnitAttention(in_channels, out_channels, A, num_point=v)
+
+        super().__init__(graph_A, input_shape, num_classes,
+                         GraphConv=[graph_conv if i in ATTENTION_LAYERS else None for i in range(10)])
+        use_wino_valid_res(self)
+
+
+class CoSTrMod(CoStGcnMod):
+    """CoS-TR*: models/cos_tr_mod/cos_tr_mod.py -- CoStGcnMod with ``GcnUnitAttention`` in layers 4-10 (``bn_momentum`` lands in
+    ``num`` as in CoSTr).  The ``window_size`` arguments of the reference's blocks -- halved in layers 6-10 although the stride is
+    1 -- are metadata no computation reads, and are not reproduced.  Steps run on the Python engine, as CoSTr's."""
+
+    def __init__(self, graph_A, input_shape=(3, 300, 25, 2), num_classes=60, pool_size=-1, pool_padding=-1):
+        v = input_shape[2]
+
+        def co_graph_conv(in_channels, out_channels, A, bn_momentum=0.1):
+            return GcnUnitAttention(in_channels, out_channels, A, bn_momentum, num_point=v)
+
+        super().__init__(graph_A, input_shape, num_classes, pool_size, pool_padding,
+                         CoGraphConv=[co_graph_conv if i in ATTENTION_LAYERS else None for i in range(10)])
+        use_wino_valid_res(self)

@@ -28,7 +28,8 @@ extern "C" {
 #endif
 
 /* Stays 16 while entries are only added: csk_derive_modality_f32 / _frames_f32, csk_prenorm_f32 / _frames_f32,
- * csk_tcn_stage_wino_valid_f32 and csk_co_plan_set_delays are additive (no existing entry, struct or constant changed). */
+ * csk_tcn_stage_wino_valid_f32, csk_tcn_stage_wino_valid_res_f32 and csk_co_plan_set_delays are additive (no existing entry, struct
+ * or constant changed). */
 #define CSK_ABI_VERSION 16
 #define CSK_KC 8    /* channel-chunk of the K loop of the TCN kernels                                */
 #define CSK_CPAD 16 /* packed weights zero-pad C_in to a multiple of this                             */
@@ -185,6 +186,26 @@ int csk_tcn_stage_wino_valid_f32(const float *y, const float *w, const float *x_
                                  const float *bias, float *out,
                                  int n_seg, int c, int c_out, int t_in, int V, int k, int stride, int pad,
                                  int res_mode, int c_res, int t_res, int res_off, int relu, const float *w_wino, void *stream);
+
+/*
+ * The valid form with the CONV residual on the centred shrink -- the unpadded "*" blocks that change the channel count (layers 5
+ * and 8 of the "*" tables at stride 1; SpatioTemporalBlock with temporal_padding = 0 and in_channels != out_channels):
+ *     out[u] = ReLU( BN(conv_{9 x 1, pad 0}(y))[u] + BN(conv_{1 x 1}(x_res))[u + 4] ),   u = 0 .. t_in - 9
+ * The kernel of csk_tcn_stage_wino_valid_f32 with a second K phase over the c_res channels of x_res: per output frame pair j the
+ * phase adds w_res . x_res[2 j + 4] to the accumulator set M0 and w_res . (-x_res[2 j + 5]) to M3, which the output transform
+ * out(2 j) = M0 + M1 + M2, out(2 j + 1) = M1 - M2 - M3 turns into the residual of both frames -- no accumulator set of its own,
+ * and the sign is applied to the staged activation, so w_res is the direct [1][c_res_pad][c_out_pad] image of csk_tcn_stage_f32
+ * and bias its folded bias (both BN shifts).  Exact fp32 arithmetic; differs from csk_tcn_stage_f32 by the rounding of the
+ * transformed weights and operands (about 1e-6 relative).
+ * Taken when k == 9, stride == 1, pad == 0, t_in >= 9, V in {25, 18}, c_out % 64 == 0, res_mode == CSK_RES_CONV, res_off == 4,
+ * t_res == t_in, c_res a multiple of 16 and x_res, w_res, w_wino != NULL (a function of the layer, never of n_seg or t_in).
+ * UNLIKE the entries above this one does not fall back: for any other call it returns -2, launches nothing and leaves
+ * csk_last_error() alone; the caller runs csk_tcn_stage_f32.  Arguments as csk_tcn_stage_wino_valid_f32 without the direct conv
+ * weight w, which this entry never reads.
+ */
+int csk_tcn_stage_wino_valid_res_f32(const float *y, const float *x_res, const float *w_res, const float *bias, float *out,
+                                     int n_seg, int c, int c_out, int t_in, int V, int k, int stride, int pad,
+                                     int res_mode, int c_res, int t_res, int res_off, int relu, const float *w_wino, void *stream);
 
 /*
  * A whole SpatioTemporalBlock with a FEW input channels and no block residual -- layer 1 of the reference's stacks
