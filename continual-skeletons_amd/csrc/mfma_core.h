@@ -186,7 +186,9 @@ struct WStage9x64 {
 
 // activations: KC channel rows x span positions of one segment -> Bl [KC][ldb]; positions outside [0, TV)
 // and channels >= C read as zero (conv zero padding / channel padding): the address is clamped into the
-// tensor and the value replaced by 0 with a select, so the load itself is unconditional.
+// tensor, so the load itself is unconditional, and the value is replaced by 0 with a select at COMMIT time.
+// issue_slot keeps the raw loaded value: a select there needs its operand, so the compiler would wait for the
+// load (s_waitcnt vmcnt) right behind its issue, in front of the MFMAs it is meant to run under.
 template <int NJ, int RPW_ = KC / (NTHREADS / 64)>
 struct BStage {
     static constexpr int RPW = RPW_;                   // rows per wave (2 for an 8-channel chunk; 2 G for G channel groups)
@@ -195,9 +197,11 @@ struct BStage {
     // of 2 NJ registers held across the K loop -- the 9-tap kernels run at the 256-register limit
     int lane_, spanm1, pbase_, tvm1;
     unsigned valid;      // bit u: position is inside [0, TV)
+    unsigned live;       // bit rr: row rr of the chunk in flight is a real channel (c < C); wave-uniform, recorded at issue
     float v[RPW][NJ];
     __device__ __forceinline__ void setup(int pbase, int span, int TV, int lane) {
         valid = 0;
+        live = 0;
         lane_ = lane;
         spanm1 = span - 1;
         pbase_ = pbase;
@@ -219,13 +223,15 @@ struct BStage {
                                                int c0, int wave) {
         if (u >= NJ) return;
         const unsigned g = goff(u);
+        unsigned lv = 0;
 #pragma unroll
         for (int rr = 0; rr < RPW; ++rr) {
             const int c = c0 + wave + rr * (NTHREADS / 64);
             const float *src = seg_base + (int64_t)min(c, C - 1) * chan_stride;
-            const float x = src[g];
-            v[rr][u] = ((c < C ? valid : 0u) >> u) & 1u ? x : 0.f;
+            v[rr][u] = src[g];
+            lv |= c < C ? 1u << rr : 0u;
         }
+        live = lv;       // every slot of a chunk records the same bits (scalar unit)
     }
     // wave is wave-uniform (readfirstlane); rows c0 + wave + 4*rr
     __device__ __forceinline__ void issue(const float *__restrict__ seg_base, int C, int64_t chan_stride, int c0,
@@ -243,15 +249,17 @@ struct BStage {
             if (NJ > 9) issue_slot(3 * G + j + 9, seg_base, C, chan_stride, c0, wave);
         }
     }
+    // the zero fill happens here, not at issue: the loads stay in flight under the MFMAs until the LDS write needs them
     __device__ __forceinline__ void commit(float *__restrict__ Bl, int ldb, int wave) const {
 #pragma unroll
         for (int rr = 0; rr < RPW; ++rr) {
             float *dst = Bl + (wave + rr * (NTHREADS / 64)) * ldb;
+            const unsigned m = (live >> rr) & 1u ? valid : 0u;
 #pragma unroll
             for (int u = 0; u < NJ; ++u) {
                 int l = lane_;
                 asm volatile("" : "+v"(l));
-                dst[min(u * 64 + l, spanm1)] = v[rr][u];
+                dst[min(u * 64 + l, spanm1)] = (m >> u) & 1u ? v[rr][u] : 0.f;
             }
         }
     }
