@@ -682,3 +682,59 @@ def test_co_stack_step_argument_errors_and_host_side_policies():
     assert len(shared) == 1                      # one scratch for the whole tree
     pkg.set_clip_latency_mode(m, 0)
     assert all(mod.__dict__.get("_split_scratch") is None for mod in m.modules() if "_split_scratch" in mod.__dict__)
+
+
+def test_head_and_input_entry_points_validate_their_arguments_without_a_gpu():
+    """csk_input_norm_f32, csk_pool_fc_f32, csk_pool_scaled_f32, csk_fc_f32, csk_co_spatial_pool_f32, csk_co_window_mean_f32:
+    null pointers, non-positive dims, streams that do not fit a frame row, a ring position outside the window and the FC's
+    alignment rule are reported before anything is launched (every call here fails its guard)."""
+    import ctypes as C
+    lib = pkg.native.lib()
+    fake, skew = C.c_void_p(0x1000), C.c_void_p(0x1004)
+
+    def refused(rc, why):
+        assert rc == -1 and why in lib.csk_last_error(), (rc, why, lib.csk_last_error())
+
+    def norm(x=fake, scale=fake, shift=fake, h=fake, N=2, Cc=3, T=5, V=25, M=2):
+        return lib.csk_input_norm_f32(x, scale, shift, h, N, Cc, T, V, M, Cc * T * V, T * V, None)
+    for kw in (dict(x=None), dict(scale=None), dict(shift=None), dict(h=None)):
+        refused(norm(**kw), b"input_norm: null pointer")
+    for kw in (dict(N=0), dict(Cc=0), dict(T=0), dict(V=-1), dict(M=0)):
+        refused(norm(**kw), b"input_norm: bad dims")
+
+    def pool_fc(h=fake, feat=fake, N=2, M=2, Cc=8, TV=50):
+        return lib.csk_pool_fc_f32(h, fake, fake, feat, fake, N, M, Cc, TV, 5, None)
+    for kw in (dict(h=None), dict(feat=None)):
+        refused(pool_fc(**kw), b"pool_fc: null pointer")
+    for kw in (dict(N=0), dict(M=0), dict(Cc=-4), dict(TV=0)):
+        refused(pool_fc(**kw), b"pool_fc: bad dims")
+
+    def pool_scaled(h=fake, feat=fake, N=2, M=2, Cc=8, TV=50):
+        return lib.csk_pool_scaled_f32(h, feat, N, M, Cc, TV, 0.75, None)
+    for kw in (dict(h=None), dict(feat=None)):
+        refused(pool_scaled(**kw), b"pool_scaled: null pointer")
+    for kw in (dict(N=-1), dict(M=0), dict(Cc=0), dict(TV=0)):
+        refused(pool_scaled(**kw), b"pool_scaled: bad dims")
+
+    def fc(feat=fake, w=fake, b=fake, logits=fake, N=2, Cc=8, classes=5):
+        return lib.csk_fc_f32(feat, w, b, logits, N, Cc, classes, None)
+    for kw in (dict(feat=None), dict(w=None), dict(b=None), dict(logits=None)):
+        refused(fc(**kw), b"fc: null pointer")
+    for kw in (dict(N=0), dict(Cc=0), dict(classes=0)):
+        refused(fc(**kw), b"fc: bad dims")
+    for kw in (dict(feat=skew), dict(w=skew), dict(feat=skew, Cc=256), dict(feat=C.c_void_p(0x1008))):
+        refused(fc(**kw), b"16-byte aligned when C is a multiple of 4")
+
+    def spatial(h=fake, feat=fake, N=2, Cc=256, MV=50, P=100):
+        return lib.csk_co_spatial_pool_f32(h, feat, N, Cc, MV, P, None)
+    for kw in (dict(h=None), dict(feat=None)):
+        refused(spatial(**kw), b"co_spatial_pool: null pointer")
+    for kw in (dict(N=0), dict(Cc=0), dict(MV=0), dict(P=99), dict(N=3)):          # N MV > P: the streams do not fit a row
+        refused(spatial(**kw), b"co_spatial_pool: bad dims")
+
+    def mean(ring=fake, pooled=fake, n_elem=512, window=4, head=0, count=1):
+        return lib.csk_co_window_mean_f32(ring, pooled, n_elem, window, head, count, None)
+    for kw in (dict(ring=None), dict(pooled=None)):
+        refused(mean(**kw), b"co_window_mean: null pointer")
+    for kw in (dict(n_elem=0), dict(window=0), dict(head=-1), dict(head=4), dict(count=-1), dict(count=5)):
+        refused(mean(**kw), b"co_window_mean: bad dims")
