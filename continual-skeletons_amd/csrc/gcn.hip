@@ -818,6 +818,37 @@ static int gcn_stage_setup(const float *x, float *y, const float *w, const float
 // the launch of the slot-balanced 16x16x4 tiles (step16.hip; same sums) is tried for these
 static bool gcn16_candidate(const GcnParams &p, bool sparse) { return sparse && p.ksplit == 1; }
 
+// The kernel a set-up launch runs, family * 1000000 + template arguments (include/cskel.h, csk_gcn_stage_f32_route), or -1 with
+// the message set where no kernel takes the shape.  The ONE copy of the rule: gcn_stage_impl switches on it, the route query
+// reports it.  Host arithmetic: of the operands only the alignment is read (csk_gcn16_tile, csk_gcn_dense2_route).
+enum { ROUTE_UNIT = 1000000, ROUTE_SPARSE2 = 1, ROUTE_TILE16 = 2, ROUTE_DENSE2 = 3, ROUTE_DENSE128 = 4, ROUTE_GENERAL = 5 };
+static int gcn_stage_route(const GcnParams &p, bool sparse, int n_seg) {
+    const bool big = (p.Mpad % 128) == 0;
+    const int MT = big ? 128 : 64, NT = 16384 / MT, V = p.V;
+    if (gcn16_candidate(p, sparse)) {     // slot-balanced 16x16x4 tiles where they pack the chip better (step16.hip; same sums)
+        if (const int tile = csk_gcn16_tile(p, n_seg)) return ROUTE_TILE16 * ROUTE_UNIT + tile;
+    }
+    if (sparse) return ROUTE_SPARSE2 * ROUTE_UNIT + MT * 10 + (p.R == 4 ? 1 : 0);
+    // dense per-sample / per-frame adjacency at V = 18 / 25: on-the-fly aggregation from register-resident adjacency
+    // columns (gcn_dense.hip); every other dense shape continues below
+    if (p.dense) {
+        if (const int d2 = csk_gcn_dense2_route(p, n_seg)) return ROUTE_DENSE2 * ROUTE_UNIT + d2;
+    }
+    // dense per-segment adjacency (A-GCN clip form): aggregation on the matrix pipe, frame-aligned tiles
+    // (128-row tiles only: on the 64-row tiles of the C_out = 64 layers the VALU aggregation of the general kernel measured
+    // 0.31 ms per launch against 0.34 ms for this form -- profiles/r03a_agcn_clip_layers.md vs r03b)
+    if (big && p.dense && !p.adj_per_frame && V >= 4 && V <= 32 && NT / V >= 1 && p.frames * (int64_t)V >= 4) {
+        const int ft = NT / V;
+        if ((int64_t)((p.frames + ft - 1) / ft) * p.mtiles * n_seg >= (1ll << 31)) CSK_FAIL("gcn_stage: grid too large");
+        return ROUTE_DENSE128 * ROUTE_UNIT + (p.R == 4 ? 1 : 0);
+    }
+    // activation staging sweeps per row: whole frames of the tile only (no temporal halo), i.e. < NT + 2 V positions:
+    // <= 256 for 128-wide and <= 384 for 256-wide tiles at V <= 64 -- 3-4 / 5-6 sweeps of 64 lanes (all spill-free)
+    const int nj = (p.ldb + 63) / 64;
+    if (nj > (big ? 4 : 6)) CSK_FAIL("gcn_stage: activation tile of %d positions per channel exceeds the staged maximum", p.ldb);
+    return ROUTE_GENERAL * ROUTE_UNIT + MT * 10 + (big ? (nj <= 3 ? 3 : 4) : (nj <= 5 ? 5 : 6));
+}
+
 static int gcn_stage_impl(const float *x, float *y, const float *w, const float *bias, const int32_t *ell_src,
                           const float *ell_val, const int32_t *ell_cnt, int ell_w, int64_t adj_seg_stride,
                           int adj_per_frame,
@@ -835,11 +866,11 @@ static int gcn_stage_impl(const float *x, float *y, const float *w, const float 
     const int MT = big ? 128 : 64, NT = 16384 / MT;
     const int Q = frames * V;
     dim3 grid(p.qtiles * p.mtiles * n_seg);
-    if (gcn16_candidate(p, sparse)) {     // slot-balanced 16x16x4 tiles where they pack the chip better (step16.hip; same sums)
-        const int rc = csk_launch_gcn16(p, n_seg, stream);
-        if (rc != -2) return rc;
-    }
-    if (sparse) {
+    const int route = gcn_stage_route(p, sparse, n_seg);
+    if (route < 0) return route;
+    const int family = route / ROUTE_UNIT;
+    if (family == ROUTE_TILE16) return csk_launch_gcn16(p, n_seg, stream);
+    if (family == ROUTE_SPARSE2) {
         const int R = p.R;
         size_t lds2;
         void (*k)(GcnParams);
@@ -864,35 +895,23 @@ static int gcn_stage_impl(const float *x, float *y, const float *w, const float 
         }
         return (int)hipGetLastError();
     }
-    // dense per-sample / per-frame adjacency with an even V <= 18: on-the-fly aggregation from register-resident adjacency
-    // columns (gcn_dense.hip); every other dense shape continues below
-    if (p.dense) {
-        const int rc = csk_launch_gcn_dense2(p, n_seg, stream);
-        if (rc != -2) return rc;
-    }
-    // activation staging sweeps per row: whole frames of the tile only (no temporal halo), i.e. < NT + 2 V positions:
-    // <= 256 for 128-wide and <= 384 for 256-wide tiles at V <= 64 -- 3-4 / 5-6 sweeps of 64 lanes (all spill-free)
-    // dense per-segment adjacency (A-GCN clip form): aggregation on the matrix pipe, frame-aligned tiles
-    // (128-row tiles only: on the 64-row tiles of the C_out = 64 layers the VALU aggregation of the general kernel measured
-    // 0.31 ms per launch against 0.34 ms for this form -- profiles/r03a_agcn_clip_layers.md vs r03b)
-    if (big && p.dense && !p.adj_per_frame && V >= 4 && V <= 32 && NT / V >= 1 && frames * (int64_t)V >= 4) {
+    if (family == ROUTE_DENSE2) return csk_launch_gcn_dense2(p, n_seg, stream);
+    if (family == ROUTE_DENSE128) {
         const int KC2 = 8;
         p.lds_frames = NT / V;                                  // FT: whole frames per tile
         int ldbx = round_up(p.lds_frames * V, 4);
         if ((ldbx / 4) % 2 == 0) ldbx += 4;                     // row stride = 4 (mod 8) words: the row-block reads are at most 2-way conflicted
         p.ldb = ldbx;
         p.qtiles = (frames + p.lds_frames - 1) / p.lds_frames;
-        if ((int64_t)p.qtiles * p.mtiles * n_seg >= (1ll << 31)) CSK_FAIL("gcn_stage: grid too large");
         const size_t ldsd = (size_t)(p.R * KC2 * MT + 3 * KC2 * NT + KC2 * ldbx + 3 * V * V) * sizeof(float);
         void (*kd)(GcnParams) = p.R == 4 ? gcn_stage_dense_kernel<128, true, 8, 3> : gcn_stage_dense_kernel<128, false, 8, 3>;
         if (const int e = csk_ensure_lds((const void *)kd, ldsd)) return e;
         hipLaunchKernelGGL(kd, dim3(p.qtiles * p.mtiles * n_seg), dim3(NTHREADS), ldsd, (hipStream_t)stream, p);
         return (int)hipGetLastError();
     }
-    const int nj = (p.ldb + 63) / 64;
-    if (nj > (big ? 4 : 6)) CSK_FAIL("gcn_stage: activation tile of %d positions per channel exceeds the staged maximum", p.ldb);
-    void (*kern)(GcnParams) = big ? (nj <= 3 ? gcn_stage_kernel<128, 3> : gcn_stage_kernel<128, 4>)
-                                  : (nj <= 5 ? gcn_stage_kernel<64, 5> : gcn_stage_kernel<64, 6>);
+    const int nj = route % 10;
+    void (*kern)(GcnParams) = big ? (nj == 3 ? gcn_stage_kernel<128, 3> : gcn_stage_kernel<128, 4>)
+                                  : (nj == 5 ? gcn_stage_kernel<64, 5> : gcn_stage_kernel<64, 6>);
     if (const int e = csk_ensure_lds((const void *)kern, lds)) return e;
     hipLaunchKernelGGL(kern, grid, dim3(NTHREADS), lds, (hipStream_t)stream, p);
     return (int)hipGetLastError();
@@ -920,6 +939,21 @@ extern "C" int csk_gcn_stage_f32_tile(const float *x, const float *y, const int3
                                        nullptr, &p, &lds, &sparse))
         return rc;
     return gcn16_candidate(p, sparse) ? csk_gcn16_tile(p, n_seg) : 0;
+}
+
+extern "C" int csk_gcn_stage_f32_route(const float *x, const float *y, const float *ell_val, const int32_t *ell_cnt, int ell_w,
+                                       int64_t adj_seg_stride, int adj_per_frame, int n_seg, int c_in, int c_out, int frames, int V,
+                                       int64_t x_seg_stride, int64_t x_chan_stride, int64_t y_seg_stride, int64_t y_chan_stride,
+                                       int res_mode) {
+    if (!ell_cnt) CSK_FAIL("gcn_stage: null pointer");
+    GcnParams p;
+    size_t lds;
+    bool sparse;
+    if (const int rc = gcn_stage_setup(x, const_cast<float *>(y), nullptr, nullptr, nullptr, ell_val, ell_cnt, ell_w, adj_seg_stride, adj_per_frame,
+                                       n_seg, c_in, c_out, frames, V, x_seg_stride, x_chan_stride, y_seg_stride, y_chan_stride, res_mode, 1,
+                                       nullptr, &p, &lds, &sparse))
+        return rc;
+    return gcn_stage_route(p, sparse, n_seg);
 }
 
 extern "C" int csk_gcn_stage_splitk_f32(const float *x, float *y, const float *w, const float *bias, const int32_t *ell_src,

@@ -302,29 +302,36 @@ static int launch_dense2(const GcnParams &p, int n_seg, hipStream_t stream) {
     return (int)hipGetLastError();
 }
 
-template <int V>
-static int dispatch_dense2(GcnParams p, int n_seg, hipStream_t s) {
-    constexpr int FT = 128 / V;
+// The instantiation gcn_stage_dense2_kernel<MT, CONVRES, V, 8> a launch runs, as MT * 1000 + V * 10 + CONVRES; 0: not a shape
+// this file is built for.  The ONE copy of the rule: the launcher below switches on it, csk_gcn_stage_f32_route reports it.  Host
+// arithmetic: of p.x / p.ell_val only the alignment is read.
+int csk_gcn_dense2_route(const GcnParams &p, int n_seg) {
+    // built for the two skeleton layouts of the reference's datasets: V = 18 (Kinetics / OpenPose) and V = 25 (NTU RGB+D)
+    if (!p.dense || (p.V != 18 && p.V != 25) || p.frames < 1) return 0;
+    if (p.V % 2 == 0) {   // joint pairs are staged with 8-byte loads
+        if ((reinterpret_cast<uintptr_t>(p.x) & 7) || (p.x_seg_stride & 1) || (p.x_chan_stride & 1)) return 0;
+        if ((reinterpret_cast<uintptr_t>(p.ell_val) & 7) || (p.adj_seg_stride & 1)) return 0;
+    }
     // (64-row tiles -- three workgroups per CU -- for the under-filled step launches of the 128- / 256-row layers: 1 014-1 016 k
     // against 1 028 k frames/s, one shard 896-898 k against 891 k: noise, not adopted)
-    const bool big = (p.Mpad % 128) == 0;
-    const int MT = big ? 128 : 64;
-    p.lds_frames = FT;
-    p.qtiles = (p.frames + FT - 1) / FT;
-    p.mtiles = p.Mpad / MT;
-    if ((int64_t)p.qtiles * p.mtiles * n_seg >= (1ll << 31)) return -2;
-    // (16-channel chunks -- one barrier per 96 / 48 MFMAs -- measured equal on clips and 3 % slower online: 8 it is)
-    if (big) return p.R == 4 ? launch_dense2<128, true, V, 8>(p, n_seg, s) : launch_dense2<128, false, V, 8>(p, n_seg, s);
-    return p.R == 4 ? launch_dense2<64, true, V, 8>(p, n_seg, s) : launch_dense2<64, false, V, 8>(p, n_seg, s);
+    const int MT = (p.Mpad % 128) == 0 ? 128 : 64, FT = 128 / p.V;
+    const unsigned qtiles = (p.frames + FT - 1) / FT, mtiles = p.Mpad / MT;
+    if ((int64_t)qtiles * mtiles * n_seg >= (1ll << 31)) return 0;
+    return MT * 1000 + p.V * 10 + (p.R == 4 ? 1 : 0);
 }
 
 int csk_launch_gcn_dense2(GcnParams p, int n_seg, void *stream) {
-    // built for the two skeleton layouts of the reference's datasets: V = 18 (Kinetics / OpenPose) and V = 25 (NTU RGB+D)
-    if (!p.dense || (p.V != 18 && p.V != 25) || p.frames < 1) return -2;
-    if (p.V % 2 == 0) {   // joint pairs are staged with 8-byte loads
-        if ((reinterpret_cast<uintptr_t>(p.x) & 7) || (p.x_seg_stride & 1) || (p.x_chan_stride & 1)) return -2;
-        if ((reinterpret_cast<uintptr_t>(p.ell_val) & 7) || (p.adj_seg_stride & 1)) return -2;
-    }
+    const int route = csk_gcn_dense2_route(p, n_seg);
+    if (!route) return -2;
+    const int MT = route / 1000, V = route / 10 % 100, FT = 128 / V;
+    const bool convres = route % 10 != 0;
+    p.lds_frames = FT;
+    p.qtiles = (p.frames + FT - 1) / FT;
+    p.mtiles = p.Mpad / MT;
     hipStream_t s = (hipStream_t)stream;
-    return p.V == 18 ? dispatch_dense2<18>(p, n_seg, s) : dispatch_dense2<25>(p, n_seg, s);
+    // (16-channel chunks -- one barrier per 96 / 48 MFMAs -- measured equal on clips and 3 % slower online: 8 it is)
+#define CSK_D2(V_) (MT == 128 ? (convres ? launch_dense2<128, true, V_, 8>(p, n_seg, s) : launch_dense2<128, false, V_, 8>(p, n_seg, s)) \
+                              : (convres ? launch_dense2<64, true, V_, 8>(p, n_seg, s) : launch_dense2<64, false, V_, 8>(p, n_seg, s)))
+    return V == 18 ? CSK_D2(18) : CSK_D2(25);
+#undef CSK_D2
 }

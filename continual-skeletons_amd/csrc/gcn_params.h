@@ -49,6 +49,9 @@ inline GcnParams gcn_params(const float *x, float *y, const float *w, const floa
 // gcn_dense.hip: dense (per-segment or per-frame) adjacency with an even joint count V <= 18; returns -2 when the shape is
 // not one it is built for (the caller then uses the kernels of gcn.hip), otherwise the launch status
 int csk_launch_gcn_dense2(GcnParams p, int n_seg, void *stream);
+// the instantiation that launch runs, MT * 1000 + V * 10 + CONVRES of gcn_stage_dense2_kernel; 0 where it returns -2.  Host
+// arithmetic: of p.x / p.ell_val only the alignment is read (csk_gcn_stage_f32_route)
+int csk_gcn_dense2_route(const GcnParams &p, int n_seg);
 
 // step16.hip: the slot-balanced 16x16x4 tiles for skeleton-sparse adjacencies on 16-byte-aligned layouts; -2 when the shape is
 // not supported or the 32x32x2 kernels pack the chip as well (bitwise the same results either way)

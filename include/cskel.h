@@ -28,7 +28,7 @@ extern "C" {
 #endif
 
 /* Stays 16 while entries are only added: csk_derive_modality_f32 / _frames_f32, csk_prenorm_f32 / _frames_f32,
- * csk_tcn_stage_wino_valid_f32, csk_tcn_stage_wino_valid_res_f32 and csk_co_plan_set_delays are additive (no existing entry, struct
+ * csk_tcn_stage_wino_valid_f32, csk_tcn_stage_wino_valid_res_f32, csk_co_plan_set_delays and csk_gcn_stage_f32_route are additive (no existing entry, struct
  * or constant changed). */
 #define CSK_ABI_VERSION 16
 #define CSK_KC 8    /* channel-chunk of the K loop of the TCN kernels                                */
@@ -96,6 +96,27 @@ int csk_gcn_stage_f32_tile(const float *x, const float *y, const int32_t *ell_cn
                            int adj_per_frame, int n_seg, int c_in, int c_out, int frames, int V,
                            int64_t x_seg_stride, int64_t x_chan_stride, int64_t y_seg_stride, int64_t y_chan_stride,
                            int res_mode);
+
+/*
+ * The kernel csk_gcn_stage_f32 launches for a call, as family * 1000000 + the template arguments of the instantiation:
+ *   1000000 + MT * 10 + CONVRES            gcn_stage_sparse2_kernel<MT, CONVRES, 8>    (csrc/gcn.hip; skeleton-sparse shared adjacency)
+ *   2000000 + csk_gcn_stage_f32_tile's     gcn16_kernel<NB, F, CONVRES, 8>             (csrc/step16.hip; the value above, never 0 here)
+ *   3000000 + MT * 1000 + V * 10 + CONVRES gcn_stage_dense2_kernel<MT, CONVRES, V, 8>  (csrc/gcn_dense.hip; dense per-segment / per-frame
+ *                                                                                       adjacency at V = 18 / 25)
+ *   4000000 + CONVRES                      gcn_stage_dense_kernel<128, CONVRES, 8, 3>  (csrc/gcn.hip; dense per-segment adjacency,
+ *                                                                                       C_out_pad a multiple of 128, 4 <= V <= 32)
+ *   5000000 + MT * 10 + NJ                 gcn_stage_kernel<MT, NJ>                    (csrc/gcn.hip; everything else)
+ * MT = rows of a workgroup tile (128 when C_out_pad is a multiple of 128, else 64), CONVRES 1 for the conv gcn_residual, NJ the
+ * 64-lane sweeps that stage one activation row (3 / 4 at MT = 128, 5 / 6 at MT = 64).  Arguments as the stage's own without w,
+ * bias, ell_src and stream (csk_gcn_stage_f32_tile's plus ell_val): of x, y and ell_val only the alignment is read -- the V = 18
+ * form of gcn_dense.hip wants x and ell_val 8-byte aligned and even strides -- they are never dereferenced.  Host arithmetic only
+ * (no GPU); -1 (csk_last_error set) where csk_gcn_stage_f32 fails on the dimensions.  The launcher switches on the function this
+ * entry reports.  For tests and tools: families 1 and 2 give bitwise the same sums, the others differ in summation order.
+ */
+int csk_gcn_stage_f32_route(const float *x, const float *y, const float *ell_val, const int32_t *ell_cnt, int ell_w,
+                            int64_t adj_seg_stride, int adj_per_frame, int n_seg, int c_in, int c_out, int frames, int V,
+                            int64_t x_seg_stride, int64_t x_chan_stride, int64_t y_seg_stride, int64_t y_chan_stride,
+                            int res_mode);
 
 /*
  * The same stage with its K loop split over workgroups (latency mode: a handful of streams, where one workgroup per tile

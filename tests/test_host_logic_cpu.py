@@ -355,6 +355,40 @@ def test_new_entry_points_validate_their_arguments_without_a_gpu():
     assert split(w=C.c_void_p(0x1008)) == -1 and b"16-byte aligned" in lib.csk_last_error()
 
 
+def test_gcn_route_query_and_dense_guards_without_a_gpu():
+    """csk_gcn_stage_f32_route on bad dimensions, the per-frame V = 64 launch that does not fit 160 KiB of LDS (the stage itself fails
+    with the same message before it launches anything), and csk_agcn_attention_f32 at V = 33"""
+    import ctypes as C
+    lib = pkg.native.lib()
+    fake = C.c_void_p(0x10000)
+
+    def route(cnt=(18, 18, 18), ell_w=18, adj=3 * 18 * 18, per_frame=0, n_seg=2, c_in=64, c_out=64, frames=8, V=18, res=1, cnt_ptr=True):
+        c = (C.c_int32 * 3)(*cnt)
+        return lib.csk_gcn_stage_f32_route(fake, fake, fake, C.cast(c, C.c_void_p) if cnt_ptr else None, ell_w, adj, per_frame, n_seg, c_in, c_out,
+                                           frames, V, c_in * frames * V, frames * V, c_out * frames * V, frames * V, res)
+    assert route() == 3064180
+    assert route(cnt_ptr=False) == -1 and b"null pointer" in lib.csk_last_error()
+    for bad in (dict(n_seg=0), dict(c_in=0, c_out=0), dict(frames=0), dict(V=1, ell_w=1, cnt=(1, 1, 1)), dict(V=65, ell_w=65, cnt=(65, 65, 65))):
+        assert route(**bad) == -1 and b"bad dims" in lib.csk_last_error(), bad
+    assert route(ell_w=19) == -1 and b"ell_w" in lib.csk_last_error()
+    assert route(cnt=(18, 19, 18)) == -1 and b"ell_cnt[1]" in lib.csk_last_error()
+    assert route(res=0) == -1 and b"res_mode" in lib.csk_last_error()
+    assert route(c_in=32) == -1 and b"identity residual" in lib.csk_last_error()
+    assert route(per_frame=1, cnt=(1, 1, 4), ell_w=4, adj=0) == -1 and b"per-frame adjacency must be dense" in lib.csk_last_error()
+    # per-frame, V = 64: 3 V^2 floats of adjacency for each of the 6 frames a 256-position tile can touch
+    v64 = dict(V=64, ell_w=64, cnt=(64, 64, 64), adj=3 * 64 * 64, per_frame=1)
+    assert route(**v64) == -1 and b"exceeds 160 KiB" in lib.csk_last_error()
+    cnt = (C.c_int32 * 3)(64, 64, 64)
+    assert lib.csk_gcn_stage_f32(fake, fake, fake, fake, fake, fake, C.cast(cnt, C.c_void_p), 64, 3 * 64 * 64, 1, 2, 64, 64, 8, 64, 64 * 512, 512,
+                                 64 * 512, 512, 1, None) == -1 and b"gcn_stage: LDS tile" in lib.csk_last_error()
+    assert route(V=64, ell_w=64, cnt=(64, 64, 64), adj=3 * 64 * 64) == 5000645            # per segment it fits: general <64, 5>
+    # the tile query keeps its answers: 0 for everything that is not the 16x16x4 family
+    c18 = (C.c_int32 * 3)(18, 18, 18)
+    assert lib.csk_gcn_stage_f32_tile(fake, fake, C.cast(c18, C.c_void_p), 18, 3 * 18 * 18, 0, 2, 64, 64, 8, 18, 64 * 144, 144, 64 * 144, 144, 1) == 0
+    assert lib.csk_agcn_attention_f32(fake, fake, fake, fake, 2, 4, 6, 33, 6 * 24 * 198, 198, 2, 0, None) == -1
+    assert b"V <= 32" in lib.csk_last_error()
+
+
 def test_set_precision_marks_blocks_and_refolds():
     m = pkg.StGcn(pkg.ntu_graph().A)
     assert all(b.precision == "f32" for b in m.layers.values())
