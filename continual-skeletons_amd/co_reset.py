@@ -100,6 +100,17 @@ class StreamReset:
         depth, n, c = self._pool_ring.shape
         return native.ScrubJob(self._pool_ring.data_ptr(), c, depth, n, first % depth, min(count, depth), c, native.SCRUB_POOL_RING)
 
+    def _leave_cohorts(self, idx):
+        """The streams ``idx`` stop warming with whatever cohort they were in (reset again, or replaced by an imported stream)."""
+        gone = set(idx)
+        for at, (members, _) in list(self._cohorts.items()):
+            left = [i for i in members if i not in gone]
+            if len(left) != len(members):
+                if left:
+                    self._cohorts[at] = (left, self._device_indices(left))
+                else:
+                    del self._cohorts[at]
+
     def reset_streams(self, indices):
         """Start the streams ``indices`` (sequence of distinct ints in [0, N)) over while the others run on: from the next
         frame their features and predictions are bit for bit those of a fresh model fed their frames alone, available
@@ -117,14 +128,7 @@ class StreamReset:
         jobs += self._modality_reset_jobs()        # a motion modality: the streams' next frame is a first frame (modality.py)
         jobs += self._prenorm_reset_jobs()         # pre-normalisation: the next frame latches the rotations anew (prenorm.py)
         self._scrub(jobs, dev, len(idx))
-        again = set(idx)
-        for at, (members, _) in list(self._cohorts.items()):       # a stream reset again leaves its earlier cohort
-            left = [i for i in members if i not in again]
-            if len(left) != len(members):
-                if left:
-                    self._cohorts[at] = (left, self._device_indices(left))
-                else:
-                    del self._cohorts[at]
+        self._leave_cohorts(idx)                                   # a stream reset again leaves its earlier cohort
         at = self._frames
         if at in self._cohorts:                                    # a second call at the same frame: one cohort
             idx = self._cohorts[at][0] + idx

@@ -13,7 +13,7 @@ import warnings
 import torch
 import torch.distributed as dist
 
-from . import native
+from . import co_migrate, native
 
 
 def shard_bounds(n_total: int, rank: int, world: int):
@@ -131,6 +131,60 @@ class StreamShards:
             st.wait_stream(cur)
             with torch.cuda.stream(st):
                 model.reset_streams(part)
+
+    def _split_pairs(self, what, indices):
+        """GLOBAL indices -> per shard a list as long as ``indices`` holding the shard's local index where the stream is
+        the shard's and -1 elsewhere (csk_co_move_streams_f32 moves nothing for an index outside the slab), so that every shard
+        works on the one packed tensor, record j pairing with ``indices[j]``."""
+        idx = co_migrate._check_indices(what, indices, self.bounds[-1][1])
+        return idx, [[i - lo if lo <= i < hi else -1 for i in idx] for lo, hi in self.bounds]
+
+    def _move_on_shards(self, packed, pairs, to_ring):
+        cur = torch.cuda.current_stream(self.device) if len(self.models) > 1 else None
+        for part, model, st in zip(pairs, self.models, self.streams):
+            if all(i < 0 for i in part):
+                continue
+            if st is None:
+                model._move(packed, model._device_indices(part), len(part), to_ring)
+                continue
+            st.wait_stream(cur)
+            with torch.cuda.stream(st):
+                model._move(packed, model._device_indices(part), len(part), to_ring)
+        for st in self.streams:                        # the packed tensor belongs to the caller's stream again
+            if st is not None:
+                cur.wait_stream(st)
+
+    def export_streams(self, indices):
+        """``CoStGcn.export_streams`` for GLOBAL stream indices: one ``StreamState`` whose records are in the order of
+        ``indices``; every shard checks its part before any shard launches, each gathers on its own HIP stream."""
+        idx, pairs = self._split_pairs("export_streams", indices)
+        for part, model in zip(pairs, self.models):
+            model._check_export([i for i in part if i >= 0])
+        first = self.models[0]
+        packed = torch.empty((len(idx), first.record_floats()), device=self.device, dtype=torch.float32)
+        if idx:
+            self._move_on_shards(packed, pairs, to_ring=False)
+        ages = self.stream_ages()[idx] if idx else torch.zeros((0,), dtype=torch.int64)
+        return co_migrate.StreamState(packed, ages, first.move_signature())
+
+    def import_streams(self, state, indices):
+        """``CoStGcn.import_streams`` for GLOBAL stream indices (record j goes to stream ``indices[j]``): every shard checks
+        its part before any shard launches, each scatters on its own HIP stream."""
+        idx, pairs = self._split_pairs("import_streams", indices)
+        if isinstance(state, co_migrate.StreamState) and len(idx) != len(state):
+            raise ValueError(f"import_streams: {len(idx)} indices for {len(state)} records")
+        parts = []
+        for part, model in zip(pairs, self.models):
+            rows = [j for j, i in enumerate(part) if i >= 0]
+            mine = co_migrate.StreamState(state.packed[:len(rows)], state.ages[rows], state.signature) \
+                if isinstance(state, co_migrate.StreamState) else state      # the checks read the ages, the signature, the length
+            model._check_import(mine, [part[j] for j in rows])
+            parts.append(rows)
+        if not idx:
+            return
+        self._move_on_shards(state.packed, pairs, to_ring=True)
+        for part, rows, model in zip(pairs, parts, self.models):
+            model._adopt([part[j] for j in rows], state.ages[rows].tolist())
 
     def streams_ready(self):
         """(N,) bool CPU tensor over the global stream axis (``CoStGcn.streams_ready`` of every shard, concatenated)."""

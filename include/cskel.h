@@ -702,6 +702,34 @@ typedef struct csk_scrub_job {
 int csk_co_scrub_streams_f32(const csk_scrub_job *jobs, int n_jobs, const int32_t *streams, int n_streams, int n_total,
                              void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Moving live streams between slabs: the copying counterpart of csk_co_scrub_streams_f32.  One launch gathers (to_ring = 0,
+ * export) the state of SOME streams of a slab into a packed, position-independent buffer, or scatters it back (to_ring = 1,
+ * import) into the same or another slab.  A job names a ring as a scrub job does (kind, depth, rows, row_floats, seg), and
+ *   newest   the slot of the ring's newest live frame / emission: its frame number modulo the depth
+ *   window   how many newest slots move (0 <= window <= depth; 0 moves nothing)
+ *   offset   where the job's floats start inside one stream's record
+ * packed is a DEVICE buffer of n_streams records of record_floats floats each; record j pairs with stream streams[j] (a
+ * DEVICE array; an index outside [0, n_total) moves nothing and leaves record j alone).  Inside a record a job's floats are
+ * [window slot, OLDEST first][row][seg]: neither the ring depth nor the slot position, N or the P padding of a slab appears in
+ * it, so a record exported from one slab imports into a slab with other depths, positions and stream counts.  An import writes
+ * the named streams' segments in the window's slots and nothing else.  Words are moved as 32-bit patterns: per-stream int32
+ * flags (seg = 1) and fp64 values (seg = 2 per value) travel as block rings of one slot and one row.  jobs is a HOST array;
+ * every job's [offset, offset + window * rows * seg) must lie inside the record and the caller keeps them disjoint.  One launch
+ * covers up to CSK_CO_MOVE_MAX_JOBS jobs: a whole model is 21 rings plus up to four small per-stream states, more than
+ * CSK_CO_SCRUB_MAX_JOBS, so this entry has a limit of its own.  Buffers need 4-byte alignment only; the access width follows
+ * the addresses.  n_streams == 0 launches nothing.
+ * ------------------------------------------------------------------------------------------------ */
+#define CSK_CO_MOVE_MAX_JOBS 32
+typedef struct csk_move_job {
+    void *ring;
+    int64_t row_floats;
+    int64_t offset;
+    int32_t depth, rows, newest, window, seg, kind;   /* kind: CSK_SCRUB_BLOCK_RING / CSK_SCRUB_POOL_RING */
+} csk_move_job;
+int csk_co_move_streams_f32(const csk_move_job *jobs, int n_jobs, void *packed, int64_t record_floats, const int32_t *streams,
+                            int n_streams, int n_total, int to_ring, void *stream);
+
 /*
  * S-TR spatial-attention graph unit (GcnUnitAttention, models/s_tr/s_tr.py:303-477, in the configuration STr / CoSTr build:
  * only_attention, no relative / adjacency / more_channels, data_bn, skip, BN; Nh = 8, dk = C_out / 4, dv = C_out).  Per
