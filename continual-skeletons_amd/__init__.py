@@ -33,7 +33,7 @@ from .agcn import AdaptiveGraphConvolution, AGcn, CoAdaptiveGraphConvolution, Co
 from .str import CoSTr, GcnUnitAttention, STr  # noqa: F401
 # The "*" forms of A-GCN and S-TR live in their modules and are reached there -- ``agcn.AGcnMod``, ``agcn.CoAGcnMod``, ``str.STrMod``,
 # ``str.CoSTrMod`` -- not as package-level names: tests/test_mod_cpu.py pins the package namespace without them.
-from . import co_migrate, fusion, modality, native, prenorm, weights  # noqa: F401
+from . import co_migrate, co_prime, fusion, modality, native, prenorm, weights  # noqa: F401
 from .co_migrate import StreamState  # noqa: F401
 from .modality import set_input_modality  # noqa: F401
 from .prenorm import pre_normalize_clip, set_pre_normalization  # noqa: F401
@@ -51,5 +51,5 @@ __all__ = [
     "AdaptiveGraphConvolution", "CoAdaptiveGraphConvolution", "AGcn", "CoAGcn", "GcnUnitAttention", "STr", "CoSTr",
     "init_weights", "zero", "unity",
     "native", "fusion", "set_precision", "set_clip_latency_mode", "modality", "set_input_modality",
-    "prenorm", "pre_normalize_clip", "set_pre_normalization", "co_migrate", "StreamState",
+    "prenorm", "pre_normalize_clip", "set_pre_normalization", "co_migrate", "co_prime", "StreamState",
 ]

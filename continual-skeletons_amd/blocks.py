@@ -473,6 +473,19 @@ class SpatioTemporalBlock(_Folded):
         if self._few_channels_fusable(x):
             return self._forward_few_channels(x, out)
         y = self.gcn(x)                                   # GCN stage kernel (or any user GraphConv module)
+        return self._tail(x, y, out)
+
+    def forward_parts(self, x):
+        """``(y, out)``: the post-GCN tensor and the block's output, through the two launches of ``forward`` (never the fused
+        few-channel kernel, which is bit for bit those two launches and keeps no ``y``).  For callers that need the
+        intermediate: priming a continual stream from a clip pass (co_prime.py)."""
+        self._require_eval()
+        native.require_device_f32(x, "SpatioTemporalBlock input")
+        y = self.gcn(x)
+        return y, self._tail(x, y, None)
+
+    def _tail(self, x, y, out):
+        """Temporal conv + residual + ReLU on the post-GCN tensor ``y`` of input ``x``."""
         if not self._native_tail:
             # foreign TempConv / residual modules: compose exactly as models/base.py:376-387
             z = self.tcn(y)

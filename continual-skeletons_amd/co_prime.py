@@ -1,0 +1,202 @@
+"""Priming streams of a ``CoStGcn`` slab from buffered history: ``prime_state`` computes the packed
+record of 3d (``StreamState``, co_migrate.py) for streams that have received the T frames of a history tensor -- with ONE clip
+pass over the history instead of T steps -- and ``prime_streams`` imports it through ``import_streams``.  The clip kernels
+compute, for the same frames, the activations the steps compute (the project's clip-versus-steps parity); the record says
+which of them are state; csk_co_prime_pack_f32 (csrc/stream_prime.hip) reads them off the clip tensors in one launch.
+
+Which clip frames: with D(L) the cumulative delays of 3a and S(L) the cumulative stride through block L (S(0) = 1), a fresh
+stream of age T has pushed e(L) = max(0, ceil((T - D(L)) / S(L))) frames out of block L (e(0) = T: the input), so the ring fed
+by block L -- the post-GCN ring of block L + 1 and the output ring of block L behind it -- has received e(L) frames and the
+pooling window e(10) entries.  Frame j of a ring is frame j of the clip tensor of the same name, a window of w takes frames
+e - w .. e - 1, and an index below 0 is the zero state of a fresh model (``prime_table``).  No frame the clip's right padding
+has touched is taken: DESIGN.md 3e has the induction."""
+import ctypes
+
+import torch
+
+from . import native
+from .blocks import SpatioTemporalBlock
+from .co_migrate import StreamState
+from .modality import MOTION
+
+
+class StreamPrime:
+    """Base class of ``CoStGcn``; it has no state of its own."""
+
+    # Bytes of clip intermediates one launch group may hold: the streams of a call are primed in chunks that stay below it
+    # (at least one stream per chunk).  ``prime_stream_bytes`` is what one stream needs.
+    prime_budget_bytes = 1 << 30
+
+    # ---- which clip frames are state (host only) ---------------------------------------------------
+    def _cum_strides(self):
+        """[S(0) .. S(10)]: S(L) = the product of the strides of blocks 1 .. L."""
+        out = [1]
+        for blk in self._blocks:
+            out.append(out[-1] * blk.stride)
+        return out
+
+    def prime_counts(self, t):
+        """[e(0) .. e(10)]: frames a fresh stream of age ``t`` has pushed out of block L (e(0) = t, the input frames)."""
+        d, s = self._cum_delays(), self._cum_strides()
+        return [max(0, -(-(t - d[i]) // s[i])) for i in range(len(d))]
+
+    def prime_clip_frames(self, t):
+        """[T_0 .. T_10]: frames of the clip tensors for a history of ``t`` frames (T_0 = t; block L maps T to
+        (T + 2 * padding - k) // stride + 1)."""
+        out = [t]
+        for blk in self._blocks:
+            out.append((out[-1] + 2 * blk.padding - blk.kernel_size) // blk.stride + 1)
+        return out
+
+    def prime_table(self, t):
+        """[(name, source, count, first, window)] in record order (``_move_windows``) for the rings and the pooling window of
+        a fresh stream of age ``t``: the ring ``name`` has received ``count`` frames, frame j of it is frame j of the clip
+        tensor ``source`` -- "xin0": the input-norm output, "y<i>" / "out<i>": post-GCN tensor / output of block i (0-based)
+        -- and its window is the frames ``first`` .. ``first + window - 1`` (``first`` = count - window < 0: that many
+        leading zero frames).  Host only; from ``delay``, ``stride`` and ``kernel_size`` of the blocks."""
+        e, last = self.prime_counts(t), len(self._blocks) - 1
+        out = []
+        for name, _, _, window in self._move_windows():
+            if name == "xin0":
+                source, count = "xin0", e[0]
+            elif name == "pool":
+                source, count = f"out{last}", e[last + 1]
+            elif name[0] == "y" and name[1:].isdigit():
+                source, count = name, e[int(name[1:])]
+            elif name[:3] == "out" and name[3:].isdigit():
+                source, count = name, e[int(name[3:]) + 1]
+            else:
+                continue                                # the small per-stream states: not frames
+            out.append((name, source, count, count - window, window))
+        return out
+
+    def prime_stream_bytes(self, t):
+        """Bytes of clip intermediates ONE stream of ``t`` history frames holds while it is primed: the derived input, the
+        input-norm output and the post-GCN tensor and the output of every block (all of them are read by the one pack
+        launch).  84.8 MB for the NTU model at t = 300."""
+        c, _, v, m = self.input_shape
+        frames = self.prime_clip_frames(t)
+        words = 2 * c * t * v * m
+        for i, blk in enumerate(self._blocks):
+            words += blk.out_channels * (frames[i] + frames[i + 1]) * v * m
+        return 4 * words
+
+    # ---- checks (host only, before anything launches) ------------------------------------------------
+    def _check_prime(self, x_hist):
+        """Everything ``prime_state`` refuses; returns T."""
+        self._require_eval()
+        if self.unpadded:
+            raise NotImplementedError(f"prime_state is not built for the unpadded '*' models ({type(self).__name__}): their valid clip "
+                                      "form shifts every frame index; that table is a follow-up -- reset_streams and step the history")
+        if any(any(k.__name__ == "AdaptiveGraphConvolution" for k in type(b.gcn).__mro__) for b in self._blocks):
+            raise NotImplementedError(f"prime_state cannot serve {type(self).__name__}: the clip form of the adaptive graph conv forms one "
+                                      "adjacency over all T frames, the steps one per frame (clip != step by design); reset_streams "
+                                      "and step the history")
+        if any(b.precision != "f32" or getattr(b.gcn, "precision", "f32") != "f32" for b in self._blocks):
+            raise NotImplementedError("prime_state takes the exact-fp32 clip kernels: the clip precision of this model is 'bf16x3' "
+                                      "(set_precision(model, 'f32'))")
+        if not isinstance(x_hist, torch.Tensor) or x_hist.dim() != 5:
+            raise RuntimeError(f"prime_state takes an (n, C, T, V, M) history tensor, got "
+                               f"{tuple(x_hist.shape) if isinstance(x_hist, torch.Tensor) else type(x_hist).__name__}")
+        n, c, t, v, m = x_hist.shape
+        if (c, v, m) != (self.input_shape[0], self.input_shape[2], self.input_shape[3]):
+            raise RuntimeError(f"history shape {tuple(x_hist.shape)} does not match input_shape {self.input_shape}")
+        if t % self.stride:
+            raise ValueError(f"prime_state: a history of {t} frames is not a multiple of the total stride {self.stride}: the stride "
+                             "phase of the strided blocks must match the slab's (drop the oldest frames)")
+        d10 = self._cum_delays()[-1]
+        if t < d10:
+            raise ValueError(f"prime_state: a history of {t} frames is younger than the {d10} frames after which every block of a "
+                             "fresh model is live; such a stream needs its warm-up: reset_streams and step the history")
+        native.require_device_f32(x_hist, "history tensor")
+        return t
+
+    def _check_prime_streams(self, x_hist, indices):
+        """The host checks of both halves of ``prime_streams``: ``prime_state``'s, then ``import_streams``' on a record-less
+        stand-in with the lengths, ages and signature the real state will have."""
+        t = self._check_prime(x_hist)
+        ages = torch.full((x_hist.shape[0],), t, dtype=torch.int64)
+        return self._check_import(StreamState(torch.empty((x_hist.shape[0], 0)), ages, self.move_signature()), indices)
+
+    # ---- the clip pass -----------------------------------------------------------------------------------
+    def _history_as_stepped(self, x):
+        """The frames the steps would have derived from the history: pre-normalised (``_prenorm_clip``; off: ``x``), then the
+        modality.  A motion modality steps on the BACKWARD difference (3b): frame 0 is zero and frame s is the forward
+        difference of the clip form at s - 1 -- the same subtraction, shifted by one frame.  Returns (normalised joints,
+        derived frames)."""
+        xn = self._prenorm_clip(x)
+        d = self._derive_clip(xn)
+        if self.input_modality in MOTION:
+            shifted = torch.empty_like(d)
+            shifted[:, :, 0] = 0.0
+            shifted[:, :, 1:] = d[:, :, :-1]
+            d = shifted
+        return xn, d
+
+    def _prime_chunk(self, x, packed):
+        """Records of the streams ``x`` (n, C, T, V, M) into ``packed`` (n, record_floats): the clip pass with every block's
+        post-GCN tensor and output kept, then one pack launch."""
+        n, c, t, v, m = x.shape
+        ops = self._packed_ops(x.device)
+        xn, d = self._history_as_stepped(x)
+        h = torch.empty((n * m, c, t, v), device=x.device, dtype=torch.float32)
+        rc = native.lib().csk_input_norm_f32(native.ptr(d), native.ptr(ops["scale"]), native.ptr(ops["shift"]), native.ptr(h),
+                                             n, c, t, v, m, c * t * v, t * v, native.stream_of(x))
+        native.check(rc, "csk_input_norm_f32")
+        clip = {"xin0": h}
+        for i, blk in enumerate(self._blocks):
+            clip[f"y{i}"], h = SpatioTemporalBlock.forward_parts(blk, h)
+            clip[f"out{i}"] = h
+        small = {}
+        if self.input_modality in MOTION:               # the last normalised raw frame; every stream has a previous frame
+            small["mod_prev"] = xn[:, :, t - 1].contiguous()
+            small["mod_flags"] = torch.ones((n,), device=x.device, dtype=torch.int32)
+        if self.pre_normalization:
+            # the rotations a stream latches from its first frame, by the step entry itself (the bits of the steps)
+            first, rot = x[:, :, 0].contiguous(), torch.zeros((n, 18), device=x.device, dtype=torch.float64)
+            flags, sink = torch.zeros((n,), device=x.device, dtype=torch.int32), torch.empty((n, c, v, m), device=x.device)
+            rc = native.lib().csk_prenorm_frames_f32((ctypes.c_void_p * 1)(first.data_ptr()), (ctypes.c_void_p * 1)(sink.data_ptr()), 1,
+                                                     native.ptr(rot), native.ptr(flags), 1, n, v, m, *self._pn_joints,
+                                                     native.stream_of(x))
+            native.check(rc, "csk_prenorm_frames_f32")
+            small["pn_rot"], small["pn_flags"] = rot, flags
+        table = {name: (source, first) for name, source, _, first, _ in self.prime_table(t)}
+        jobs, offset = [], 0
+        for name, rows, seg, window in self._move_windows():
+            if name in table:
+                src, first = clip[table[name][0]], table[name][1]
+                kind, rows_ = (native.PRIME_POOL, seg) if name == "pool" else (native.PRIME_RING, rows)
+                jobs.append(native.PrimeJob(src.data_ptr(), offset, kind, rows_, src.shape[2], first, window, 0))
+            else:
+                src = small[name]
+                jobs.append(native.PrimeJob(src.data_ptr(), offset, native.PRIME_WORDS, seg, 1, 0, window, 0))
+            offset += rows * seg * window
+        if len(jobs) > native.MOVE_MAX_JOBS:
+            raise RuntimeError(f"{len(jobs)} jobs in one pack launch (limit {native.MOVE_MAX_JOBS})")
+        arr = (native.PrimeJob * len(jobs))(*jobs)
+        rc = native.lib().csk_co_prime_pack_f32(ctypes.byref(arr), len(jobs), native.ptr(packed), offset, n, m, v, native.stream_of(x))
+        native.check(rc, "csk_co_prime_pack_f32")
+
+    # ---- public ------------------------------------------------------------------------------------------
+    def prime_state(self, x_hist):
+        """``StreamState`` of ``n`` streams that have received the frames of ``x_hist`` (n, C, T, V, M), device fp32: one
+        record per stream, ages T, this model's ``move_signature()`` -- what ``export_streams`` would return for fresh streams
+        stepped through the history, within the clip-versus-steps tolerance of the activations (the small states bit for
+        bit), computed by one clip pass and one pack launch per chunk of streams.  T must be a multiple of the total stride
+        and at least D(10), the age from which every block of a fresh model is live (76 for the ten-block table).  Needs no
+        bound slab and neither reads nor writes the continual state.  Memory: ``prime_stream_bytes(T)`` of intermediates per
+        stream (84.8 MB for NTU at T = 300: 12 streams per chunk); the streams are primed in chunks that stay below ``prime_budget_bytes``
+        (1 GiB; at least one stream per chunk).  Not built for ``CoAGcn``, the '*' models and the 'bf16x3' clip precision."""
+        t = self._check_prime(x_hist)
+        n = x_hist.shape[0]
+        packed = torch.empty((n, self.record_floats()), device=x_hist.device, dtype=torch.float32)
+        chunk = max(1, int(self.prime_budget_bytes // self.prime_stream_bytes(t)))
+        for lo in range(0, n, chunk):
+            self._prime_chunk(x_hist[lo:lo + chunk], packed[lo:lo + chunk])
+        return StreamState(packed, torch.full((n,), t, dtype=torch.int64), self.move_signature())
+
+    def prime_streams(self, x_hist, indices):
+        """``import_streams(prime_state(x_hist), indices)``: stream ``indices[j]`` of this slab continues as a fresh stream that
+        has received the frames of ``x_hist[j]``.  Every host check of both halves runs before the first launch."""
+        self._check_prime_streams(x_hist, indices)
+        self.import_streams(self.prime_state(x_hist), indices)

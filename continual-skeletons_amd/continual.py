@@ -32,6 +32,7 @@ from . import blocks, fold, native
 from .blocks import GraphConvolution, SpatioTemporalBlock, TemporalConvolution, _Folded, init_weights, is_plain_graph_conv, unity, zero
 from .co_plan import NativePlan
 from .co_migrate import StreamMove
+from .co_prime import StreamPrime
 from .co_reset import StreamReset
 from .modality import ContinualModality
 from .prenorm import ContinualPreNorm
@@ -561,7 +562,7 @@ def co_geometry(c_in=3, unpadded=False):
     return r, p, s
 
 
-class CoStGcn(NativePlan, StreamReset, StreamMove, ContinualPreNorm, ContinualModality, _Folded):
+class CoStGcn(NativePlan, StreamReset, StreamMove, StreamPrime, ContinualPreNorm, ContinualModality, _Folded):
     """CoST-GCN: models/cost_gcn/cost_gcn.py:21-41 + CoModelBase (models/base.py:68-227) without the Ride shell.
 
     ``forward_step(x_t: (N, C, V, M))`` -> logits (N, classes) on the steps where the whole stack (10 blocks,
@@ -570,7 +571,7 @@ class CoStGcn(NativePlan, StreamReset, StreamMove, ContinualPreNorm, ContinualMo
     state_dict keys equal the reference's (``layers.layerK.0.1.gcn...``); a regular StGcn state_dict loads too
     (what ``map_state_dict`` does in the reference, base.py:200-224).  This class binds the state slab and steps on it; the
     native plan (co_plan.py: NativePlan), the per-stream reset (co_reset.py: StreamReset), moving streams between slabs
-    (co_migrate.py: StreamMove) and the input modality
+    (co_migrate.py: StreamMove), priming streams from buffered history with one clip pass (co_prime.py: StreamPrime) and the input modality
     (modality.py: ContinualModality -- bone / motion frames derived from the joint frames in front of every cycle) are base classes,
     and so is the pre-normalisation of raw joint frames (prenorm.py: ContinualPreNorm), which runs in front of the modality.
     """

@@ -155,6 +155,14 @@ class OnlineEnsemble:
         for net in self.nets:
             net.reset_streams(indices)
 
+    def prime_streams(self, x_hist, indices):
+        """``CoStGcn.prime_streams`` on every member with the same JOINT history ``x_hist`` (n, C, T, V, M): each member derives
+        its own modality from it, as it does from the frames it steps on.  Every member checks before any launches."""
+        for net in self.nets:
+            net._check_prime_streams(x_hist, indices)
+        for net in self.nets:
+            net.prime_streams(x_hist, indices)
+
     def streams_ready(self):
         """(N,) bool CPU tensor: the members agree (same delay and pooling), so this is the first one's."""
         return self.nets[0].streams_ready()

@@ -61,6 +61,7 @@ SIGNATURES = {
     "csk_co_plan_cycle": [_p, C.POINTER(C.c_int64), _i, _p, _i, _p, _p, _p, _p, _p],
     "csk_co_scrub_streams_f32": [_p, _i, _p, _i, _i, _p],
     "csk_co_move_streams_f32": [_p, _i, _p, _l, _p, _i, _i, _i, _p],
+    "csk_co_prime_pack_f32": [_p, _i, _p, _l, _i, _i, _i, _p],
     "csk_str_unit_f32": [_p, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _l, _l, _l, _l, _p],
 }
 RESTYPES = {"csk_co_plan_create": C.c_void_p, "csk_co_plan_destroy": None}
@@ -91,10 +92,17 @@ class MoveJob(C.Structure):
                 ("newest", C.c_int32), ("window", C.c_int32), ("seg", C.c_int32), ("kind", C.c_int32)]
 
 
+class PrimeJob(C.Structure):
+    """Mirror of ``csk_prime_job`` (include/cskel.h)."""
+    _fields_ = [("src", C.c_void_p), ("offset", C.c_int64), ("kind", C.c_int32), ("rows", C.c_int32), ("t_src", C.c_int32),
+                ("first", C.c_int32), ("window", C.c_int32), ("pad_", C.c_int32)]
+
+
 CO_MAX_CYCLE = 8        # CSK_CO_MAX_CYCLE: frames one cycle may carry = logits slices csk_co_plan_cycle may write
 SCRUB_MAX_JOBS = 24
 MOVE_MAX_JOBS = 32      # CSK_CO_MOVE_MAX_JOBS
 SCRUB_BLOCK_RING, SCRUB_POOL_RING = 0, 1
+PRIME_RING, PRIME_POOL, PRIME_WORDS = 0, 1, 2   # CSK_PRIME_*
 
 _lib = None
 

@@ -167,9 +167,9 @@ class StreamShards:
         ages = self.stream_ages()[idx] if idx else torch.zeros((0,), dtype=torch.int64)
         return co_migrate.StreamState(packed, ages, first.move_signature())
 
-    def import_streams(self, state, indices):
-        """``CoStGcn.import_streams`` for GLOBAL stream indices (record j goes to stream ``indices[j]``): every shard checks
-        its part before any shard launches, each scatters on its own HIP stream."""
+    def _check_import(self, state, indices):
+        """Every shard's host checks of an import; returns (global indices, per-shard local indices with -1 for the streams of
+        other shards, per-shard rows of ``state`` that are the shard's)."""
         idx, pairs = self._split_pairs("import_streams", indices)
         if isinstance(state, co_migrate.StreamState) and len(idx) != len(state):
             raise ValueError(f"import_streams: {len(idx)} indices for {len(state)} records")
@@ -180,11 +180,28 @@ class StreamShards:
                 if isinstance(state, co_migrate.StreamState) else state      # the checks read the ages, the signature, the length
             model._check_import(mine, [part[j] for j in rows])
             parts.append(rows)
+        return idx, pairs, parts
+
+    def import_streams(self, state, indices):
+        """``CoStGcn.import_streams`` for GLOBAL stream indices (record j goes to stream ``indices[j]``): every shard checks
+        its part before any shard launches, each scatters on its own HIP stream."""
+        idx, pairs, parts = self._check_import(state, indices)
         if not idx:
             return
         self._move_on_shards(state.packed, pairs, to_ring=True)
         for part, rows, model in zip(pairs, parts, self.models):
             model._adopt([part[j] for j in rows], state.ages[rows].tolist())
+
+    def prime_streams(self, x_hist, indices):
+        """``CoStGcn.prime_streams`` for GLOBAL stream indices: the first shard's model computes the records of ``x_hist``
+        (n, C, T, V, M) on the current stream (the shards hold the same weights), ``import_streams`` scatters record j to the
+        shard that owns stream ``indices[j]``.  Every host check -- the history's, then every shard's import checks -- runs
+        before the first launch."""
+        first = self.models[0]
+        t = first._check_prime(x_hist)
+        ages = torch.full((x_hist.shape[0],), t, dtype=torch.int64)
+        self._check_import(co_migrate.StreamState(torch.empty((x_hist.shape[0], 0)), ages, first.move_signature()), indices)
+        self.import_streams(first.prime_state(x_hist), indices)
 
     def streams_ready(self):
         """(N,) bool CPU tensor over the global stream axis (``CoStGcn.streams_ready`` of every shard, concatenated)."""

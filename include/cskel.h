@@ -28,7 +28,7 @@ extern "C" {
 #endif
 
 /* Stays 16 while entries are only added: csk_derive_modality_f32 / _frames_f32, csk_prenorm_f32 / _frames_f32,
- * csk_tcn_stage_wino_valid_f32, csk_tcn_stage_wino_valid_res_f32, csk_co_plan_set_delays and csk_gcn_stage_f32_route are additive (no existing entry, struct
+ * csk_tcn_stage_wino_valid_f32, csk_tcn_stage_wino_valid_res_f32, csk_co_plan_set_delays, csk_gcn_stage_f32_route and csk_co_prime_pack_f32 are additive (no existing entry, struct
  * or constant changed). */
 #define CSK_ABI_VERSION 16
 #define CSK_KC 8    /* channel-chunk of the K loop of the TCN kernels                                */
@@ -729,6 +729,39 @@ typedef struct csk_move_job {
 } csk_move_job;
 int csk_co_move_streams_f32(const csk_move_job *jobs, int n_jobs, void *packed, int64_t record_floats, const int32_t *streams,
                             int n_streams, int n_total, int to_ring, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Priming streams from buffered history: write the packed records csk_co_move_streams_f32 imports -- the same layout, job by
+ * job -- from the tensors of a CLIP pass over the streams' history instead of from a slab (co_prime.py).  One
+ * launch; record k of packed ([n_streams][record_floats], device) belongs to stream k of every source.  A job names
+ *   kind     CSK_PRIME_RING   src = clip tensor (n_streams * M, rows, t_src, V) contiguous: the job's floats are
+ *                             [frame first + i, i = 0 .. window - 1][row][m * V + v], window * rows * M * V per stream -- what
+ *                             a ring job of csk_co_move_streams_f32 holds for a ring whose frame j is clip frame j.  A frame
+ *                             index < 0 (first may be negative) is written as +0.0, the zero state of a fresh model's ring.
+ *                             Words travel as 32-bit patterns.
+ *            CSK_PRIME_POOL   src as above (the last layer's output): entry i is the spatial mean of frame first + i over the
+ *                             stream's M * V positions, rows floats per entry, window * rows per stream, in the arithmetic
+ *                             and summation order of csk_co_head_step_f32's pool (bit for bit its ring entry for the same
+ *                             feature frame); a frame index < 0 gives +0.0.
+ *            CSK_PRIME_WORDS  src = [n_streams][rows] 32-bit words (flags, fp64 halves, a raw frame): copied as they are;
+ *                             first = 0, t_src = 1, window = 1 (0: nothing)
+ *   offset   where the job's floats start inside one stream's record
+ * jobs is a HOST array of 1..CSK_CO_MOVE_MAX_JOBS jobs.  Checked on the host before anything is launched (csk_last_error
+ * set, -1): the job count, null and misaligned (4-byte) pointers, dims < 1, window < 0, first + window > t_src (no frame
+ * behind the source is ever read), offset < 0 or offset + size > record_floats.  The caller keeps the jobs disjoint.  Buffers
+ * need 4-byte alignment only; the stores are 16 bytes wide behind the leading unaligned words of a job's run.  n_streams == 0
+ * and empty windows launch nothing.
+ * ------------------------------------------------------------------------------------------------ */
+#define CSK_PRIME_RING 0
+#define CSK_PRIME_POOL 1
+#define CSK_PRIME_WORDS 2
+typedef struct csk_prime_job {
+    const void *src;
+    int64_t offset;
+    int32_t kind, rows, t_src, first, window, pad_;
+} csk_prime_job;
+int csk_co_prime_pack_f32(const csk_prime_job *jobs, int n_jobs, void *packed, int64_t record_floats, int n_streams, int M, int V,
+                          void *stream);
 
 /*
  * S-TR spatial-attention graph unit (GcnUnitAttention, models/s_tr/s_tr.py:303-477, in the configuration STr / CoSTr build:
