@@ -822,9 +822,16 @@ static bool gcn16_candidate(const GcnParams &p, bool sparse) { return sparse && 
 // the message set where no kernel takes the shape.  The ONE copy of the rule: gcn_stage_impl switches on it, the route query
 // reports it.  Host arithmetic: of the operands only the alignment is read (csk_gcn16_tile, csk_gcn_dense2_route).
 enum { ROUTE_UNIT = 1000000, ROUTE_SPARSE2 = 1, ROUTE_TILE16 = 2, ROUTE_DENSE2 = 3, ROUTE_DENSE128 = 4, ROUTE_GENERAL = 5 };
+// a split launch (p.ksplit > 1 ranges; gcn_stage_setup has refused everything but the sparse family): bit fields, csk_gcn_stage_splitk_f32_route
+enum { ROUTE_SPLIT = 1 << 30, ROUTE_SPLIT_MT128 = 1 << 29, ROUTE_SPLIT_CONVRES = 1 << 28, ROUTE_SPLIT_RANGES_SHIFT = 23, ROUTE_SPLIT_CPER_MASK = (1 << 23) - 1 };
 static int gcn_stage_route(const GcnParams &p, bool sparse, int n_seg) {
     const bool big = (p.Mpad % 128) == 0;
     const int MT = big ? 128 : 64, NT = 16384 / MT, V = p.V;
+    if (p.ksplit > 1) {
+        if (p.cper / 8 > ROUTE_SPLIT_CPER_MASK) CSK_FAIL("gcn_stage_splitk: %d channels per range exceed the split launch", p.cper);
+        return ROUTE_SPLIT | (big ? ROUTE_SPLIT_MT128 : 0) | (p.R == 4 ? ROUTE_SPLIT_CONVRES : 0) | ((p.ksplit - 1) << ROUTE_SPLIT_RANGES_SHIFT) |
+               (p.cper / 8);
+    }
     if (gcn16_candidate(p, sparse)) {     // slot-balanced 16x16x4 tiles where they pack the chip better (step16.hip; same sums)
         if (const int tile = csk_gcn16_tile(p, n_seg)) return ROUTE_TILE16 * ROUTE_UNIT + tile;
     }
@@ -868,7 +875,8 @@ static int gcn_stage_impl(const float *x, float *y, const float *w, const float 
     dim3 grid(p.qtiles * p.mtiles * n_seg);
     const int route = gcn_stage_route(p, sparse, n_seg);
     if (route < 0) return route;
-    const int family = route / ROUTE_UNIT;
+    const bool split = (route & ROUTE_SPLIT) != 0;
+    const int family = split ? ROUTE_SPARSE2 : route / ROUTE_UNIT;
     if (family == ROUTE_TILE16) return csk_launch_gcn16(p, n_seg, stream);
     if (family == ROUTE_SPARSE2) {
         const int R = p.R;
@@ -876,11 +884,13 @@ static int gcn_stage_impl(const float *x, float *y, const float *w, const float 
         void (*k)(GcnParams);
         // ping-pong LDS, trickled loads, 3 workgroups / CU
         lds2 = 2 * (size_t)(R * 8 * MT + 8 * p.ldb) * sizeof(float);
-        if (p.ksplit > 1) {
-            if ((int64_t)p.qtiles * p.mtiles * n_seg * p.ksplit >= (1ll << 31)) CSK_FAIL("gcn_stage: grid too large");
-            grid = dim3(p.qtiles * p.mtiles * n_seg * p.ksplit);
-            k = big ? (R == 4 ? gcn_stage_sparse2_kernel<128, true, 8, false, true> : gcn_stage_sparse2_kernel<128, false, 8, false, true>)
-                    : (R == 4 ? gcn_stage_sparse2_kernel<64, true, 8, false, true> : gcn_stage_sparse2_kernel<64, false, 8, false, true>);
+        if (split) {
+            const bool big2 = (route & ROUTE_SPLIT_MT128) != 0, convres = (route & ROUTE_SPLIT_CONVRES) != 0;
+            const int ranges = ((route >> ROUTE_SPLIT_RANGES_SHIFT) & 31) + 1;
+            if ((int64_t)p.qtiles * p.mtiles * n_seg * ranges >= (1ll << 31)) CSK_FAIL("gcn_stage: grid too large");
+            grid = dim3(p.qtiles * p.mtiles * n_seg * ranges);
+            k = big2 ? (convres ? gcn_stage_sparse2_kernel<128, true, 8, false, true> : gcn_stage_sparse2_kernel<128, false, 8, false, true>)
+                     : (convres ? gcn_stage_sparse2_kernel<64, true, 8, false, true> : gcn_stage_sparse2_kernel<64, false, 8, false, true>);
         } else {
             k = big ? (R == 4 ? gcn_stage_sparse2_kernel<128, true, 8> : gcn_stage_sparse2_kernel<128, false, 8>)
                     : (R == 4 ? gcn_stage_sparse2_kernel<64, true, 8> : gcn_stage_sparse2_kernel<64, false, 8>);
@@ -888,7 +898,7 @@ static int gcn_stage_impl(const float *x, float *y, const float *w, const float 
         const int e = csk_ensure_lds((const void *)k, lds2);
         if (e) return e;
         hipLaunchKernelGGL(k, grid, dim3(NTHREADS), lds2, (hipStream_t)stream, p);
-        if (p.ksplit > 1) {
+        if (split) {
             if (const int e2 = (int)hipGetLastError()) return e2;
             const int64_t work = (int64_t)c_out * Q;
             hipLaunchKernelGGL(gcn_reduce_kernel, dim3((unsigned)((work + 255) / 256), n_seg), dim3(256), 0, (hipStream_t)stream, p);
@@ -956,11 +966,32 @@ extern "C" int csk_gcn_stage_f32_route(const float *x, const float *y, const flo
     return gcn_stage_route(p, sparse, n_seg);
 }
 
+// what the split entry and its route query refuse before anything else
+static int gcn_splitk_args(int ksplit, const float *partial) {
+    if (ksplit < 1 || ksplit > 32 || (ksplit > 1 && !partial)) CSK_FAIL("gcn_stage_splitk: ksplit must be in [1, 32] and needs a partial-sum buffer");
+    return 0;
+}
+
+extern "C" int csk_gcn_stage_splitk_f32_route(const float *x, const float *y, const float *ell_val, const int32_t *ell_cnt, int ell_w, int n_seg,
+                                              int c_in, int c_out, int frames, int V, int64_t x_seg_stride, int64_t x_chan_stride,
+                                              int64_t y_seg_stride, int64_t y_chan_stride, int res_mode, int ksplit, const float *partial) {
+    if (const int rc = gcn_splitk_args(ksplit, partial)) return rc;
+    if (!ell_cnt) CSK_FAIL("gcn_stage: null pointer");
+    GcnParams p;
+    size_t lds;
+    bool sparse;
+    if (const int rc = gcn_stage_setup(x, const_cast<float *>(y), nullptr, nullptr, nullptr, ell_val, ell_cnt, ell_w, 0, 0, n_seg, c_in, c_out, frames,
+                                       V, x_seg_stride, x_chan_stride, y_seg_stride, y_chan_stride, res_mode, ksplit, const_cast<float *>(partial),
+                                       &p, &lds, &sparse))
+        return rc;
+    return gcn_stage_route(p, sparse, n_seg);
+}
+
 extern "C" int csk_gcn_stage_splitk_f32(const float *x, float *y, const float *w, const float *bias, const int32_t *ell_src,
                                         const float *ell_val, const int32_t *ell_cnt, int ell_w, int n_seg, int c_in, int c_out,
                                         int frames, int V, int64_t x_seg_stride, int64_t x_chan_stride, int64_t y_seg_stride,
                                         int64_t y_chan_stride, int res_mode, int ksplit, float *partial, void *stream) {
-    if (ksplit < 1 || ksplit > 32 || (ksplit > 1 && !partial)) CSK_FAIL("gcn_stage_splitk: ksplit must be in [1, 32] and needs a partial-sum buffer");
+    if (const int rc = gcn_splitk_args(ksplit, partial)) return rc;
     return gcn_stage_impl(x, y, w, bias, ell_src, ell_val, ell_cnt, ell_w, 0, 0, n_seg, c_in, c_out, frames, V, x_seg_stride,
                           x_chan_stride, y_seg_stride, y_chan_stride, res_mode, ksplit, partial, stream);
 }

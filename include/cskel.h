@@ -28,7 +28,7 @@ extern "C" {
 #endif
 
 /* Stays 16 while entries are only added: csk_derive_modality_f32 / _frames_f32, csk_prenorm_f32 / _frames_f32,
- * csk_tcn_stage_wino_valid_f32, csk_tcn_stage_wino_valid_res_f32, csk_co_plan_set_delays, csk_gcn_stage_f32_route and csk_co_prime_pack_f32 are additive (no existing entry, struct
+ * csk_tcn_stage_wino_valid_f32, csk_tcn_stage_wino_valid_res_f32, csk_co_plan_set_delays, csk_gcn_stage_f32_route, csk_gcn_stage_splitk_f32_route and csk_co_prime_pack_f32 are additive (no existing entry, struct
  * or constant changed). */
 #define CSK_ABI_VERSION 16
 #define CSK_KC 8    /* channel-chunk of the K loop of the TCN kernels                                */
@@ -130,6 +130,20 @@ int csk_gcn_stage_splitk_f32(const float *x, float *y, const float *w, const flo
                              const float *ell_val, const int32_t *ell_cnt, int ell_w, int n_seg, int c_in, int c_out,
                              int frames, int V, int64_t x_seg_stride, int64_t x_chan_stride, int64_t y_seg_stride,
                              int64_t y_chan_stride, int res_mode, int ksplit, float *partial, void *stream);
+
+/*
+ * The launch csk_gcn_stage_splitk_f32 makes for a call.  A request that collapses to ONE channel range (ksplit == 1, or c_in no larger
+ * than one range) runs the unsplit stage and no reduction: the value is csk_gcn_stage_f32_route's.  Otherwise
+ *   (1 << 30) | (MT == 128) << 29 | CONVRES << 28 | (ranges - 1) << 23 | cper / 8
+ * gcn_stage_sparse2_kernel<MT, CONVRES, 8, false, true> over `ranges` channel ranges of cper channels each (the last one what is left
+ * of c_in_pad) followed by gcn_reduce_kernel; cper = ceil(c_in_pad / ksplit) rounded up to a multiple of 8, ranges = ceil(c_in / cper)
+ * <= ksplit <= 32.  Arguments as the split entry's without w, bias, ell_src and stream; x, y, ell_val and partial are never
+ * dereferenced.  Host arithmetic only (no GPU); -1 (csk_last_error set) where csk_gcn_stage_splitk_f32 refuses the call.  The launcher
+ * switches on the function this entry reports.
+ */
+int csk_gcn_stage_splitk_f32_route(const float *x, const float *y, const float *ell_val, const int32_t *ell_cnt, int ell_w, int n_seg,
+                                   int c_in, int c_out, int frames, int V, int64_t x_seg_stride, int64_t x_chan_stride,
+                                   int64_t y_seg_stride, int64_t y_chan_stride, int res_mode, int ksplit, const float *partial);
 
 /*
  * TemporalConvolution.forward (models/base.py:302-304) fused with the tail of

@@ -210,7 +210,9 @@ def _draw(rng, tier, shape, lo, hi):
 
 def operands(c, tier):
     """-> dict: x [n, c_in, T, V], adj [matrices, 3, V(v), V(w)] (what the reference sums with), w [R, c_in, c_out], bias [c_out],
-    and the ELL image the kernel gets: ell_src [3, V(w), ell_w] int32, ell_val [matrices, 3, V(w), ell_w]"""
+    and the ELL image the kernel gets: ell_src [3, V(w), ell_w] int32, ell_val [matrices, 3, V(w), ell_w].  adj = "ell": the entries
+    e >= ell_cnt[r] of ell_val are NaN (their ell_src stays a joint: a kernel may load them, none may add them); ell_val_full is the
+    same graph with the drawn values in those places."""
     rng = np.random.default_rng(np.random.SeedSequence([c.V, c.c_in, c.c_out, c.frames, c.n_seg, c.res, len(c.adj), c.ell_w]))
     R = 4 if c.res == RES_CONV else 3
     x = _draw(rng, tier, (c.n_seg, c.c_in, c.frames, c.V), -2, 2)
@@ -226,6 +228,11 @@ def operands(c, tier):
             for wj in range(c.V):
                 for e in range(c.ell_cnt[r]):                     # the entries that count
                     adj[0, r, src[r, wj, e], wj] += val[0, r, wj, e]
+        full = np.asarray(val, dtype=f32)                         # the graph before its tails are poisoned
+        val = full.copy()
+        for r in range(3):
+            val[0, r, :, c.ell_cnt[r]:] = np.nan                  # an entry past ell_cnt must not be read into a sum
+        return dict(x=x, w=w, bias=bias, adj=np.asarray(adj), ell_src=src, ell_val=val, ell_val_full=full)
     else:
         adj = _draw(rng, tier, (nm, 3, c.V, c.V), -1, 2)
         src = np.broadcast_to(np.arange(c.V, dtype=np.int32), (3, c.V, c.V)).copy()
@@ -322,7 +329,11 @@ def is_integral_f32(a):
 def admissible_exact(c, ops, y_pre, mag, relu=True):
     """exact tier: integer operands, every partial sum below 2^24 (on sum |term|), ReLU clips 20 % .. 80 %"""
     for k in ("x", "w", "bias") + (("ell_val",) if "ell_val" in ops else ()):
-        assert is_integral_f32(ops[k]), (c.name, k)
+        a = np.asarray(ops[k])
+        assert is_integral_f32(a[~np.isnan(a)] if k == "ell_val" else a), (c.name, k)      # NaN: the tails past ell_cnt alone
+    if "ell_val_full" in ops:
+        assert is_integral_f32(ops["ell_val_full"]) and all(np.isnan(ops["ell_val"][0, r, :, c.ell_cnt[r]:]).all() and
+                                                            not np.isnan(ops["ell_val"][0, r, :, :c.ell_cnt[r]]).any() for r in range(3)), c.name
     assert float(mag.max()) < 2 ** 24, (c.name, float(mag.max()))
     if relu:
         share = float((y_pre < 0).mean())

@@ -82,8 +82,12 @@ def test_boundary_cases_differ_in_the_entries_that_count():
     refs = [fx.reference(c, fx.operands(c, "exact"))[0] for c in fx.BOUNDARY_CASES]
     assert not np.array_equal(refs[0], refs[1]) and not np.array_equal(refs[0], refs[2])
     ops = [fx.operands(c, "exact") for c in fx.BOUNDARY_CASES]
-    assert all(np.array_equal(ops[0][k], o[k]) for o in ops for k in ("x", "w", "bias", "ell_src", "ell_val"))   # ONE graph
-    assert (ops[0]["ell_val"] != 0).all()
+    assert all(np.array_equal(ops[0][k], o[k]) for o in ops for k in ("x", "w", "bias", "ell_src", "ell_val_full"))   # ONE graph
+    assert (ops[0]["ell_val_full"] != 0).all()
+    for c, o in zip(fx.BOUNDARY_CASES, ops):               # ... of which the kernel gets the entries that count; the rest is NaN
+        for r in range(3):
+            assert np.array_equal(o["ell_val"][0, r, :, :c.ell_cnt[r]], o["ell_val_full"][0, r, :, :c.ell_cnt[r]])
+            assert np.isnan(o["ell_val"][0, r, :, c.ell_cnt[r]:]).all()
 
 
 def test_float_cases_keep_the_bound_below_half_a_term():

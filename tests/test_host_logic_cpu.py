@@ -593,6 +593,49 @@ def test_round4_entry_points_validate_their_arguments_without_a_gpu():
     assert lib.csk_input_norm_frames_f32(srcs, dsts, 2, fake, fake, 2, 3, 25, 2, 100, None) == -1 and b"null frame" in lib.csk_last_error()
 
 
+def test_gcn_split_route_query_refuses_what_the_split_entry_refuses():
+    """csk_gcn_stage_splitk_f32_route and csk_gcn_stage_splitk_f32 on the same bad requests: ksplit outside [1, 32], no partial-sum
+    buffer, a graph or a tile the sparse kernel does not take with ksplit > 1, bad dimensions -- the same message from both, nothing
+    launched; and the query's answers for ksplit = 1 and for a request that collapses are csk_gcn_stage_f32_route's."""
+    import ctypes as C
+    lib = pkg.native.lib()
+    fake = C.c_void_p(0x10000)
+
+    def both(ksplit=4, partial=fake, cnt=(1, 1, 4), ell_w=4, n_seg=1, c_in=64, c_out=64, frames=2, V=25, res=1, cnt_ptr=True):
+        c = C.cast((C.c_int32 * 3)(*cnt), C.c_void_p) if cnt_ptr else None
+        q = frames * V
+        a = lib.csk_gcn_stage_splitk_f32_route(fake, fake, fake, c, ell_w, n_seg, c_in, c_out, frames, V, c_in * q, q, c_out * q, q, res, ksplit, partial)
+        ma = lib.csk_last_error()
+        if a >= 0:
+            return a, b""
+        b = lib.csk_gcn_stage_splitk_f32(fake, fake, fake, fake, fake, fake, c, ell_w, n_seg, c_in, c_out, frames, V, c_in * q, q, c_out * q, q, res,
+                                         ksplit, partial, None)
+        assert b == -1 and lib.csk_last_error() == ma, (ma, lib.csk_last_error())
+        return a, ma
+    for bad in (0, -1, 33):
+        rc, msg = both(ksplit=bad)
+        assert rc == -1 and b"ksplit must be in [1, 32]" in msg
+    rc, msg = both(partial=None)
+    assert rc == -1 and b"partial-sum buffer" in msg
+    for graph in (dict(cnt=(2, 1, 4)), dict(cnt=(1, 1, 5), ell_w=5), dict(V=50, c_out=128, c_in=128)):     # V = 50: ldb 200 > 192
+        rc, msg = both(**graph)
+        assert rc == -1 and b"skeleton-sparse" in msg, graph
+        assert both(ksplit=1, partial=None, **graph)[0] // 1000000 == 5                                     # unsplit: the general kernel
+    assert both(cnt_ptr=False) == (-1, b"gcn_stage: null pointer")
+    for bad in (dict(n_seg=0), dict(frames=0), dict(V=1, ell_w=1, cnt=(1, 1, 1)), dict(c_in=0, c_out=0)):
+        rc, msg = both(**bad)
+        assert rc == -1 and b"bad dims" in msg, bad
+    rc, msg = both(c_out=128)
+    assert rc == -1 and b"identity residual" in msg
+    # answers: (1 << 30) | MT128 << 29 | CONVRES << 28 | (ranges - 1) << 23 | cper / 8
+    assert both()[0] == (1 << 30) | 3 << 23 | 2
+    assert both(c_in=40, c_out=128, res=2)[0] == (1 << 30) | (1 << 29) | (1 << 28) | 2 << 23 | 2
+    assert both(ksplit=32, c_in=256, c_out=256)[0] == (1 << 30) | (1 << 29) | 31 << 23 | 1
+    assert both(ksplit=1, partial=None)[0] == 1000640 and both(c_in=3, res=2)[0] == 1000641                # one range: the unsplit route
+    cnt = C.cast((C.c_int32 * 3)(1, 1, 4), C.c_void_p)
+    assert lib.csk_gcn_stage_f32_route(fake, fake, fake, cnt, 4, 0, 0, 1, 3, 64, 2, 25, 150, 50, 3200, 50, 2) == 1000641
+
+
 def test_roofline_config_prices_n_ranks_against_n_peaks():
     """bench.py passes the WHOLE JOB's work (per-rank work x world) and the step time; the accounting must price it against
     world x one MI355X's peak.  With the round-4 driver timing (72.222 ms per batch-256 step) the fraction is 0.75 at one
