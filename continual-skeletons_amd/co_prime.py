@@ -98,9 +98,15 @@ class StreamPrime:
         if not isinstance(x_hist, torch.Tensor) or x_hist.dim() != 5:
             raise RuntimeError(f"prime_state takes an (n, C, T, V, M) history tensor, got "
                                f"{tuple(x_hist.shape) if isinstance(x_hist, torch.Tensor) else type(x_hist).__name__}")
-        n, c, t, v, m = x_hist.shape
-        if (c, v, m) != (self.input_shape[0], self.input_shape[2], self.input_shape[3]):
-            raise RuntimeError(f"history shape {tuple(x_hist.shape)} does not match input_shape {self.input_shape}")
+        if self.keypoint_intake:                        # keypoints.py: the history is an (n, T, P, V, 3) keypoint clip
+            t = x_hist.shape[1]
+            if tuple(x_hist.shape) != self._keypoint_shape(x_hist.shape[0], t):
+                raise RuntimeError(f"keypoint history shape {tuple(x_hist.shape)} does not match (n, T, {self._kp_people}, "
+                                   f"{self.input_shape[2]}, 3)")
+        else:
+            n, c, t, v, m = x_hist.shape
+            if (c, v, m) != (self.input_shape[0], self.input_shape[2], self.input_shape[3]):
+                raise RuntimeError(f"history shape {tuple(x_hist.shape)} does not match input_shape {self.input_shape}")
         if t % self.stride:
             raise ValueError(f"prime_state: a history of {t} frames is not a multiple of the total stride {self.stride}: the stride "
                              "phase of the strided blocks must match the slab's (drop the oldest frames)")
@@ -135,7 +141,9 @@ class StreamPrime:
 
     def _prime_chunk(self, x, packed):
         """Records of the streams ``x`` (n, C, T, V, M) into ``packed`` (n, record_floats): the clip pass with every block's
-        post-GCN tensor and output kept, then one pack launch."""
+        post-GCN tensor and output kept, then one pack launch.  With the keypoint intake on, ``x`` is the (n, T, P, V, 3)
+        keypoint history and the selected clip takes its place first."""
+        x = self._intake_clip(x)
         n, c, t, v, m = x.shape
         ops = self._packed_ops(x.device)
         xn, d = self._history_as_stepped(x)

@@ -34,6 +34,7 @@ from .co_plan import NativePlan
 from .co_migrate import StreamMove
 from .co_prime import StreamPrime
 from .co_reset import StreamReset
+from .keypoints import ContinualKeypointIntake
 from .modality import ContinualModality
 from .prenorm import ContinualPreNorm
 from .models import MOD_TEMPORAL_PADDING, layer_table, per_layer
@@ -562,7 +563,7 @@ def co_geometry(c_in=3, unpadded=False):
     return r, p, s
 
 
-class CoStGcn(NativePlan, StreamReset, StreamMove, StreamPrime, ContinualPreNorm, ContinualModality, _Folded):
+class CoStGcn(NativePlan, StreamReset, StreamMove, StreamPrime, ContinualKeypointIntake, ContinualPreNorm, ContinualModality, _Folded):
     """CoST-GCN: models/cost_gcn/cost_gcn.py:21-41 + CoModelBase (models/base.py:68-227) without the Ride shell.
 
     ``forward_step(x_t: (N, C, V, M))`` -> logits (N, classes) on the steps where the whole stack (10 blocks,
@@ -574,6 +575,8 @@ class CoStGcn(NativePlan, StreamReset, StreamMove, StreamPrime, ContinualPreNorm
     (co_migrate.py: StreamMove), priming streams from buffered history with one clip pass (co_prime.py: StreamPrime) and the input modality
     (modality.py: ContinualModality -- bone / motion frames derived from the joint frames in front of every cycle) are base classes,
     and so is the pre-normalisation of raw joint frames (prenorm.py: ContinualPreNorm), which runs in front of the modality.
+    The keypoint intake (keypoints.py: ContinualKeypointIntake; off by default) runs in front of both: with it the model is fed
+    ``(N, P, V, 3)`` keypoint frames / ``(N, T, P, V, 3)`` clips in the place of the channel-first ones named here.
     """
 
     # False: drive every launch from Python (same kernels, same results).  Read on every cycle: both engines step on the one
@@ -668,6 +671,7 @@ class CoStGcn(NativePlan, StreamReset, StreamMove, StreamPrime, ContinualPreNorm
         self._forget_resets()
         self._bind_modality(n, device)
         self._bind_prenorm(n, device)
+        self._bind_intake(n, device)
         self._build_plan(device)
 
     _frames = _counter(0, "input frames received")
@@ -711,10 +715,12 @@ class CoStGcn(NativePlan, StreamReset, StreamMove, StreamPrime, ContinualPreNorm
     def scratch_bytes(self):
         """Transient scratch, not state: the split-K partial sums (shared by the blocks that split their K loop) and, for
         adaptive graph convs, the per-skeleton-frame adjacencies of a launch (shared by all blocks); with a bone / motion input
-        modality, the derived frames of a cycle; with pre-normalisation, its normalised frames."""
-        adj, mod, pn = self.__dict__.get("_agcn_adj"), self._mod_scratch, self._pn_scratch
+        modality, the derived frames of a cycle; with pre-normalisation, its normalised frames; with the keypoint intake, its
+        selected frames."""
+        adj, mod, pn, kp = self.__dict__.get("_agcn_adj"), self._mod_scratch, self._pn_scratch, self._kp_scratch
         return 4 * ((self._scratch.numel() if self._scratch is not None else 0) + (adj.numel() if adj is not None else 0)
-                    + (mod.numel() if mod is not None else 0) + (pn.numel() if pn is not None else 0))
+                    + (mod.numel() if mod is not None else 0) + (pn.numel() if pn is not None else 0)
+                    + (kp.numel() if kp is not None else 0))
 
     def clean_state(self):
         if self._n is not None:
@@ -737,19 +743,24 @@ class CoStGcn(NativePlan, StreamReset, StreamMove, StreamPrime, ContinualPreNorm
         ``peek``: the caller puts the counters back (one step, update_state=False) -- the next real step rewrites and scrubs
         the same slots, so a peek does neither.  The engines step on ``_derive_frames(frames)``: the frames themselves for
         the joint modality, else the bone / motion frames of the pre-pass (a peek leaves its previous-frame state alone); with
-        pre-normalisation on, ``_prenorm_frames`` runs first and the modality derives from the normalised frames."""
+        pre-normalisation on, ``_prenorm_frames`` runs first and the modality derives from the normalised frames.  With the
+        keypoint intake on, the frames are (N, P, V, 3) keypoints, checked as such in the place of the check against
+        ``input_shape``, and ``_intake_frames`` runs in front of both (stateless: a peek runs it as well)."""
         self._require_eval()
         frames = list(frames)
         if not 1 <= len(frames) <= self.max_cycle:
             raise ValueError(f"a cycle holds 1..{self.max_cycle} frames (set_max_cycle), got {len(frames)}")
         x0 = frames[0]
-        for x_t in frames:
-            native.require_device_f32(x_t, "CoStGcn frame")
-            if x_t.shape != x0.shape or x_t.device != x0.device:
-                raise RuntimeError("all frames of a cycle must have the same shape and device")
-        n, c, v, m = x0.shape
-        if (c, v, m) != (self.input_shape[0], self.input_shape[2], self.input_shape[3]):
-            raise RuntimeError(f"frame shape {tuple(x0.shape)} does not match input_shape {self.input_shape}")
+        if self.keypoint_intake:
+            n = self._check_keypoint_frames(frames)
+        else:
+            for x_t in frames:
+                native.require_device_f32(x_t, "CoStGcn frame")
+                if x_t.shape != x0.shape or x_t.device != x0.device:
+                    raise RuntimeError("all frames of a cycle must have the same shape and device")
+            n, c, v, m = x0.shape
+            if (c, v, m) != (self.input_shape[0], self.input_shape[2], self.input_shape[3]):
+                raise RuntimeError(f"frame shape {tuple(x0.shape)} does not match input_shape {self.input_shape}")
         if self._n != n or self._xin0.device != x0.device:           # clean_state_on_shape_change (base.py:161-164)
             self._bind(n, x0.device)
         if any(b.precision != "f32" and b.step_precision == "f32" for b in self.layers.values()):
@@ -759,6 +770,7 @@ class CoStGcn(NativePlan, StreamReset, StreamMove, StreamPrime, ContinualPreNorm
             raise RuntimeError("the state was flushed by forward_steps(pad_end=True): the end padding has consumed ring slots "
                                "and advanced the blocks past the input frame count; call clean_state() before stepping on")
         engine = self._plan_cycle if self.use_native_plan and self.__dict__.get("_plan") else self._python_cycle
+        frames = self._intake_frames(frames)        # keypoints.py; off: the list itself
         if not self._cohorts or peek:              # nothing warms: the cycle is the one that runs without any reset
             return engine(self._derive_frames(self._prenorm_frames(frames, update=not peek), update=not peek))
         self._check_cycle_while_warming(len(frames))
@@ -860,19 +872,20 @@ class CoStGcn(NativePlan, StreamReset, StreamMove, StreamPrime, ContinualPreNorm
         through to every module as in the reference (base.py:187-190): each block's temporal conv is flushed with its
         ``padding`` zero frames, first block first, so that the stack emits what the clip stack computes for the same
         frames, and the temporal average pool is flushed with ``pool_padding`` zero features."""
+        axis = self.time_axis           # 2; 1 for the (N, T, P, V, 3) clips of the keypoint intake
         if not update_state:
-            self._ensure_bound(x[:, :, 0].contiguous())
+            self._ensure_bound(x.select(axis, 0).contiguous())
             with _snapshot(self._state_tensors(), self._position, self._set_position):
                 return self.forward_steps(x, pad_end, True)
         if pad_end and self._cohorts:
             raise RuntimeError("forward_steps(pad_end=True) while reset streams are warming up (streams_ready()): the end padding "
                                "flushes every block for every stream, live for the stream or not")
         outs = []
-        for t in range(x.shape[2]):
-            o = self.forward_step(x[:, :, t].contiguous())
+        for t in range(x.shape[axis]):
+            o = self.forward_step(x.select(axis, t).contiguous())
             if o is not None:
                 outs.append(o)
-        if pad_end and x.shape[2] > 0:
+        if pad_end and x.shape[axis] > 0:
             outs += self._flush()
             self._flushed = True                   # stepping on needs clean_state() (see _flush)
         if not outs:
@@ -910,6 +923,7 @@ class CoStGcn(NativePlan, StreamReset, StreamMove, StreamPrime, ContinualPreNorm
             self.clean_state()
             ret = self.forward_steps(x)
             return ret[:, :, 0]
+        x = self._intake_clip(x)        # keypoints.py; off: x itself
         n, c, t, v, m = x.shape
         h = self._clip_features(x)                                        # (N*M, 256, T', V)
         tp = h.shape[2]
@@ -948,7 +962,8 @@ class CoStGcn(NativePlan, StreamReset, StreamMove, StreamPrime, ContinualPreNorm
         c, _, v, m = self.input_shape
         frames = self.receptive_field - self.padding - 1 if frames is None else frames
         for _ in range(frames):
-            self.forward_step(torch.randn((n, c, v, m), device=device))
+            self.forward_step(torch.rand(self._keypoint_shape(n), device=device) if self.keypoint_intake
+                              else torch.randn((n, c, v, m), device=device))
 
 
 class CoStGcnMod(CoStGcn):

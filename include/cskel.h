@@ -28,7 +28,8 @@ extern "C" {
 #endif
 
 /* Stays 16 while entries are only added: csk_derive_modality_f32 / _frames_f32, csk_prenorm_f32 / _frames_f32,
- * csk_tcn_stage_wino_valid_f32, csk_tcn_stage_wino_valid_res_f32, csk_co_plan_set_delays, csk_gcn_stage_f32_route, csk_gcn_stage_splitk_f32_route and csk_co_prime_pack_f32 are additive (no existing entry, struct
+ * csk_tcn_stage_wino_valid_f32, csk_tcn_stage_wino_valid_res_f32, csk_co_plan_set_delays, csk_gcn_stage_f32_route, csk_gcn_stage_splitk_f32_route, csk_co_prime_pack_f32 and
+ * csk_select_people_f32 / _frames_f32 are additive (no existing entry, struct
  * or constant changed). */
 #define CSK_ABI_VERSION 16
 #define CSK_KC 8    /* channel-chunk of the K loop of the TCN kernels                                */
@@ -596,6 +597,38 @@ int csk_prenorm_f32(const float *x, float *out, int N, int T, int V, int M, int 
  */
 int csk_prenorm_frames_f32(const float *const *frames, float *const *dst, int r, double *rot, int32_t *has_rot, int update, int N,
                            int V, int M, int zaxis0, int zaxis1, int xaxis0, int xaxis1, void *stream);
+
+/*
+ * Kinetics keypoint intake (csrc/keypoints.hip): the arithmetic of the reference's offline Feeder_kinetics.__getitem__
+ * (datasets/data_preparation/kinetics400_prep.py:100-138) on the device.  k (N, T, P, V, 3) -> out (N, 3, T, V, M):
+ * k[n, t, p, v, :] = (x, y, s), the P people a pose estimator found in a frame, their V joints and per joint the two image
+ * coordinates in [0, 1] and the confidence score -- the reference's pose[0::2], pose[1::2] and score, person-major.
+ * Per (sample, frame), on its own (so the operation is causal and has no state):
+ *   1. S[p] = sum over v of s[p, v], accumulated in fp64 with v ascending (the reference sums in fp64; for fp32 scores the sum
+ *      is exact over any realistic range, so the order does not hang on rounding)
+ *   2. person p is placed before person q iff S[p] > S[q], or the two compare equal and p < q; a NaN sum goes behind every
+ *      number, NaN sums among themselves by index.  (numpy.argsort of -S, the reference's, agrees wherever the sums of the
+ *      people present are distinct; its order of ties is platform dependent, this one is fixed.)
+ *   3. for m < M, with p = order[m], per joint v:
+ *        out[0] = (s == 0) ? +0.0f : x - 0.5f
+ *        out[1] = (s == 0) ? +0.0f : -(y - 0.5f)       subtracted, then negated: y == 0.5 with a score gives -0.0, as the
+ *        out[2] = s                                     reference's; 0.5f - y would give +0.0
+ *      The zeroing is per joint (a score of -0.0 counts as 0) and does not enter S.
+ * Limits: 1 <= M <= P <= 8, 1 <= V <= 64.  out is another buffer than k.  One launch, no allocation, no synchronisation, no
+ * scratch, graph-capture safe.  Not reproduced: reading the estimator's JSON, and datasets/tools.py:openpose_match (tracking
+ * people across frames), which the reference's pipeline does not call.
+ * Returns -1 for a null pointer, out == k or a dim < 1; -2 for a violated limit (csk_last_error set, nothing launched).
+ */
+int csk_select_people_f32(const float *k, float *out, int N, int T, int P, int V, int M, void *stream);
+
+/*
+ * The same for the r = 1..8 frames of a launch cycle of the continual path in one launch: frames[i] (N, P, V, 3) -> dst[i]
+ * (N, 3, V, M); frames / dst are HOST arrays of device pointers, as for csk_prenorm_frames_f32; every dst[i] is a buffer of
+ * its own.  The arithmetic per (stream, frame) is csk_select_people_f32's, bit for bit.
+ * Returns -1 for a null pointer (frames, dst, a frame), a dim < 1 or a dst that is a source frame or another dst; -2 for r
+ * outside 1..8 or a violated limit (csk_last_error set, nothing launched).
+ */
+int csk_select_people_frames_f32(const float *const *frames, float *const *dst, int r, int N, int P, int V, int M, void *stream);
 
 /*
  * Multi-stream logit fusion + top-k support, scripts/multi_stream_eval.py:33-60: fused = left fold of add
