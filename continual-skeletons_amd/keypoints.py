@@ -56,6 +56,12 @@ def _check_model_shape(model, people_in):
     return people_in
 
 
+def _check_other_intake(model, enabled):
+    if enabled and getattr(model, "ntu_intake", False):        # ntu_intake.py: the clip models' other intake
+        raise ValueError("the NTU intake is on: a model runs one intake, switch it off first "
+                         "(ntu_intake.set_ntu_intake(model, enabled=False))")
+
+
 class KeypointIntake:
     """Base class of the clip models (``StGcn`` and its siblings): the switch and the clip pre-pass."""
 
@@ -138,8 +144,9 @@ def set_keypoint_intake(model, people_in: int = PEOPLE_IN, enabled: bool = True)
     Kinetics feeder does offline (default off: no launch, no buffer).  For ``StGcn`` / ``AGcn`` / ``STr``, ``CoStGcn`` /
     ``CoAGcn`` / ``CoSTr``, their ``*Mod`` forms and a ``StreamShards`` (every shard model).  The number of people kept is the
     model's ``input_shape[3]``.  The intake runs in front of the pre-normalisation and the modality pre-passes.
-    ``ValueError`` for a model that does not take C = 3 channels or ``people_in`` outside [M, 8]; a continual model that has
-    stepped (frame counter not 0) raises ``RuntimeError``: ``clean_state()`` first.  Returns ``model``."""
+    ``ValueError`` for a model that does not take C = 3 channels, ``people_in`` outside [M, 8] or a clip model whose NTU intake
+    (ntu_intake.py) is on; a continual model that has stepped (frame counter not 0) raises ``RuntimeError``: ``clean_state()``
+    first.  Returns ``model``."""
     if isinstance(model, parallel.StreamShards):
         for shard in model.models:      # all validated before any is switched: the shards step in lock step
             if not isinstance(shard, KeypointIntake):
@@ -153,5 +160,6 @@ def set_keypoint_intake(model, people_in: int = PEOPLE_IN, enabled: bool = True)
         return model
     if not isinstance(model, KeypointIntake):
         raise TypeError(f"{type(model).__name__} has no keypoint intake (StGcn, CoStGcn, their siblings, or a StreamShards)")
+    _check_other_intake(model, enabled)
     model._set_keypoint_intake(enabled, _check_model_shape(model, people_in))
     return model

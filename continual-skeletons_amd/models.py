@@ -12,6 +12,7 @@ from . import fold, native
 from .blocks import SpatioTemporalBlock, _Folded, init_weights
 from .keypoints import KeypointIntake
 from .modality import InputModality
+from .ntu_intake import NtuIntake
 from .prenorm import PreNorm
 
 
@@ -50,7 +51,7 @@ def per_layer(factory):
     return [factory] * 10
 
 
-class StGcn(KeypointIntake, PreNorm, InputModality, _Folded):
+class StGcn(NtuIntake, KeypointIntake, PreNorm, InputModality, _Folded):
     unpadded = False     # StGcnMod: the "*" layer table (stride 1, temporal padding 0, centred residual shrink)
 
     def __init__(self, graph_A, input_shape=(3, 300, 25, 2), num_classes=60, GraphConv=None):
@@ -113,7 +114,7 @@ class StGcn(KeypointIntake, PreNorm, InputModality, _Folded):
 
     def forward(self, x):
         self._require_eval()
-        x = self._intake_clip(x)        # keypoints.py; off: x itself
+        x = self._intake_clip(x)        # ntu_intake.py, else keypoints.py; both off: x itself
         n, c, t, v, m = x.shape
         return self.head(self.features(x), n, m)
 

@@ -54,6 +54,7 @@ SIGNATURES = {
     "csk_prenorm_frames_f32": [_p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     "csk_select_people_f32": [_p, _p, _i, _i, _i, _i, _i, _p],
     "csk_select_people_frames_f32": [_p, _p, _i, _i, _i, _i, _i, _p],
+    "csk_ntu_intake_f32": [_p, _p, _i, _i, _i, _i, _i, _i, _p],
 
     "csk_fuse_rank_f32": [_p, _i, _i, _i, _i, _l, _l, _p, _p, _p, _p],
     "csk_co_plan_create": [_i, _p, _p, _i, _i, _i, _i, _i, _l, _p, _p, _i, _p, _p, _i, _i, _p, _p],

@@ -9,7 +9,7 @@ model, and in front of the modality pre-pass (modality.py): the reference derive
 The centring is per frame, so it is causal; the two rotation matrices are latched from a stream's first frame.  That is
 per-stream state -- ``rot`` (N, 18) fp64 and ``has_rot`` (N,) int32 -- and it follows the rules of the rest of the continual
 state (``ContinualPreNorm``).  The arithmetic is stated in include/cskel.h and DESIGN.md section 3c; the reference's padding
-of null frames looks ahead and is not reproduced, in either form.
+of null frames looks ahead and is not reproduced, in either form (whole clips: the pre-pass of ntu_intake.py, in front of this one).
 """
 import ctypes
 

@@ -29,7 +29,7 @@ extern "C" {
 
 /* Stays 16 while entries are only added: csk_derive_modality_f32 / _frames_f32, csk_prenorm_f32 / _frames_f32,
  * csk_tcn_stage_wino_valid_f32, csk_tcn_stage_wino_valid_res_f32, csk_co_plan_set_delays, csk_gcn_stage_f32_route, csk_gcn_stage_splitk_f32_route, csk_co_prime_pack_f32 and
- * csk_select_people_f32 / _frames_f32 are additive (no existing entry, struct
+ * csk_select_people_f32 / _frames_f32 and csk_ntu_intake_f32 are additive (no existing entry, struct
  * or constant changed). */
 #define CSK_ABI_VERSION 16
 #define CSK_KC 8    /* channel-chunk of the K loop of the TCN kernels                                */
@@ -629,6 +629,35 @@ int csk_select_people_f32(const float *k, float *out, int N, int T, int P, int V
  * outside 1..8 or a violated limit (csk_last_error set, nothing launched).
  */
 int csk_select_people_frames_f32(const float *const *frames, float *const *dst, int r, int N, int P, int V, int M, void *stream);
+
+/*
+ * NTU RGB+D body intake for WHOLE CLIPS (csrc/ntu_intake.hip): what the reference's offline pipeline does to a
+ * recorded Kinect clip before it centres and rotates it -- read_xyz's choice of the max_body_true bodies with the largest motion
+ * energy (datasets/data_preparation/ntu60_prep.py:101-128), gendata's placement into max_frame frames (:169-177) and the
+ * null-frame padding that opens pre_normalization (preprocess.py:18-39).  csk_prenorm_f32 on the result is the rest of that
+ * function.  bodies (N, T, P, V, 3) -> out (N, 3, T_out, V, M): bodies[n, t, p, v, :] = (x, y, z) of joint v of the sensor's body
+ * slot p; a frame in which a body is not tracked is all zero (as read_xyz leaves it).  Per clip, on its own:
+ *   a. a frame of a body is NULL iff all its V * 3 values are +-0.  (The reference tests `sum == 0`, which also fires when
+ *      non-zero values cancel exactly; only all-zero data is acted on here, as in csk_prenorm_f32.)
+ *   b. E[p] = sum over the 3 coordinates of the population standard deviation (ddof 0) of that coordinate over (the body's
+ *      non-null frames x V); 0 for a body without a non-null frame.  fp64 from the fp32 values, two passes (the mean, then the
+ *      squared deviations), in a summation order that is a function of (T, V) only: bodies with the same data get the same
+ *      bits whatever their slot, and a clip's result does not depend on N or on its place in the batch.
+ *   c. output person m is the body of rank m by descending E; equal energies: the HIGHER slot first (numpy's
+ *      energy.argsort()[::-1], the reference's).  A NaN energy goes behind every number.
+ *   d. with b = the body of person m: an empty body gives +0 everywhere.  Frame 0 non-null: L = index of the last non-null
+ *      frame + 1, src(t) = t mod L (null frames inside stay null).  Frame 0 null: idx[0..L-1] = the non-null frames in order,
+ *      src(t) = idx[t mod L].  out[n, c, t, v, m] = bodies[n, src(t), b, v, c] for t in [0, T_out): a late body is moved to
+ *      the front, a short clip is filled by repeating itself.  Frames >= T of the input count as null.
+ *   e. NaN coordinates are outside the contract (the reference's own result then hangs on `person *= 0` leaving NaN behind);
+ *      the kernel takes every index from the null flags, so it stays inside its operands and the other clips keep their bits.
+ * The padding looks ahead: there is no frames form, the continual path cannot run it (prepare a history for priming with it).
+ * Limits: 1 <= M <= P <= 8, 1 <= V <= 64, T <= T_out <= CSK_NTU_MAX_FRAMES (the reference's max_frame is 300).  out is another
+ * buffer than bodies.  One launch (one workgroup per clip), no allocation, no synchronisation, no scratch, graph-capture safe.
+ * Returns -1 for a null pointer, out == bodies or a dim < 1; -2 for a violated limit (csk_last_error set, nothing launched).
+ */
+#define CSK_NTU_MAX_FRAMES 1024
+int csk_ntu_intake_f32(const float *bodies, float *out, int N, int T, int P, int V, int M, int T_out, void *stream);
 
 /*
  * Multi-stream logit fusion + top-k support, scripts/multi_stream_eval.py:33-60: fused = left fold of add
