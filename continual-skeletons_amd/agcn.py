@@ -91,6 +91,73 @@ class AdaptiveGraphConvolution(GraphConvolution):
         return y
 
     fuse_embed_attention = True     # False: two launches (csk_conv1x1_f32 + csk_agcn_attention_f32) -- for A/B measurements
+    fuse_framewise = True           # False: forward_framewise composes the per-frame launches -- for A/B measurements
+    # False: the frame-wise kernel only at the shapes where it measured faster than the composed launches
+    # (profiles/r23_agcn_framewise.md: V = 18 at inter 16; V = 25 at layer 1 and at inter 32 with the conv residual; the composed
+    # launches are 2-30 % faster at the others); True: wherever it is built -- for tests and A/B measurements
+    framewise_everywhere = False
+    # Bytes of per-frame adjacencies (3 V V floats per skeleton frame; + the embeddings on the two-launch route) the composed form
+    # of forward_framewise may hold at a time: the clip is taken in chunks of frames that stay below it (at least one frame)
+    framewise_budget_bytes = 256 << 20
+
+    def framewise_route(self, x):
+        """The instantiation of csk_agcn_stage_framewise_f32 ``forward_framewise(x)`` launches (INTER * 1000 + V * 10 + CONVRES), or
+        0 where it composes the per-frame launches.  Host arithmetic only."""
+        if not self.fuse_framewise:
+            return 0
+        ops = self._packed_ops(x.device)
+        n, c, t, v = x.shape
+        rc = native.lib().csk_agcn_stage_framewise_f32_route(native.ptr(x), n, c, self.out_channels, self.inter_c, t, v, c * t * v, t * v,
+                                                             ops["res_mode"])
+        native.check(min(rc, 0), "csk_agcn_stage_framewise_f32_route")
+        if rc and not self.framewise_everywhere:
+            conv = ops["res_mode"] == 2
+            faster = self.inter_c == 16 if v == 18 else ((self.inter_c == 16 and c <= 4) or (self.inter_c == 32 and conv))
+            return rc if faster else 0
+        return rc
+
+    def forward_framewise(self, x):
+        """(NM, C, T, V) -> (NM, C_out, T, V) with the attention formed per (skeleton, frame): for every frame what ``stage``
+        computes for it on a step (models/coa_gcn/coa_gcn.py:11-14), on a whole clip.  One launch of csk_agcn_stage_framewise_f32
+        where it is built (V in {18, 25}, inter in {16, 32, 64}) and measured faster (``framewise_everywhere``): the per-frame
+        adjacencies never reach memory.  Elsewhere the
+        per-frame launches of ``stage`` on chunks of frames whose adjacencies stay below ``framewise_budget_bytes``; a frame's
+        result does not depend on the chunking (every kernel involved forms a frame from that frame alone)."""
+        self._require_eval()
+        _check_input(x, self.in_channels, "AdaptiveGraphConvolution input")
+        x = x.contiguous()
+        ops = self._packed_ops(x.device)
+        n, c, t, v = x.shape
+        y = torch.empty((n, self.out_channels, t, v), device=x.device, dtype=torch.float32)
+        if self.framewise_route(x):
+            rc = native.lib().csk_agcn_stage_framewise_f32(
+                native.ptr(x), native.ptr(y), native.ptr(ops["w"]), native.ptr(ops["bias"]), native.ptr(ops["w_embed_pairs"]),
+                native.ptr(ops["b_embed_pairs"]), native.ptr(ops["a_sum"]), n, c, self.out_channels, self.inter_c, t, v, c * t * v, t * v,
+                self.out_channels * t * v, t * v, ops["res_mode"], native.stream_of(x))
+            native.check(rc, "csk_agcn_stage_framewise_f32")
+            return y
+        e_ch = 6 * self.inter_c
+        xs, ys = (c * t * v, t * v), (self.out_channels * t * v, t * v)
+        fused = self._fused_ok(v, x.data_ptr(), *xs)    # (a chunk starts t0 * V floats into a row: even for even V)
+        chunk = max(1, int(self.framewise_budget_bytes // (4 * n * (3 * v * v + (0 if fused else e_ch * v)))))
+        for t0 in range(0, t, chunk):
+            f = min(chunk, t - t0)
+            xc, yc = x[:, :, t0:], y[:, :, t0:]         # frames t0 .. of every channel: same strides, f frames taken
+            if fused:
+                adj = torch.empty((n * f, 3, v, v), device=x.device, dtype=torch.float32)
+                rc = native.lib().csk_agcn_embed_attention_f32(
+                    native.ptr(xc), native.ptr(ops["w_embed_pairs"]), native.ptr(ops["b_embed_pairs"]), native.ptr(ops["a_sum"]),
+                    native.ptr(adj), None, n, c, self.inter_c, f, v, 1, xs[0], xs[1], native.stream_of(x))
+                native.check(rc, "csk_agcn_embed_attention_f32")
+            else:
+                E = torch.empty((n, e_ch, f * v), device=x.device, dtype=torch.float32)
+                rc = native.lib().csk_conv1x1_f32(native.ptr(xc), native.ptr(E), native.ptr(ops["w_embed"]), native.ptr(ops["b_embed"]), n, c,
+                                                  e_ch, f, v, xs[0], xs[1], e_ch * f * v, f * v, native.stream_of(x))
+                native.check(rc, "csk_conv1x1_f32")
+                adj = self._attention(E, ops, n * f, 1, v, v, f * v, seg_per_group=f, e_group_stride=e_ch * f * v)
+            blocks.gcn_stage(xc, yc, dict(ops, ell_val=adj), n_seg=n, frames=f, x_strides=xs, y_strides=ys,
+                             adj_seg_stride=3 * v * v, adj_per_frame=1)
+        return y
 
     def _fused_ok(self, v, data_ptr, seg_stride, chan_stride):
         """Shapes csk_agcn_embed_attention_f32 is built for (even V: 8-byte aligned activation rows)."""
@@ -196,6 +263,72 @@ class CoAGcn(CoStGcn):
 
     def __init__(self, graph_A, input_shape=(3, 300, 25, 2), num_classes=60, pool_size=-1, pool_padding=-1):
         super().__init__(graph_A, input_shape, num_classes, pool_size, pool_padding, CoGraphConv=CoAdaptiveGraphConvolution)
+
+    # ---- a stored clip at the steps' arithmetic ---------------------------------------------------
+    def clip_as_steps_map(self, t, pad_end=False):
+        """Host only.  ``(frames, entries)`` for a fresh model stepped through ``t`` frames: layer 10 has emitted ``frames``
+        feature frames -- frame j of the clip pass -- (``prime_counts(t)[-1]``; with ``pad_end`` every block is flushed and all
+        ``prime_clip_frames(t)[-1]`` frames of the clip come out), the pooling window has taken them in order, followed with
+        ``pad_end`` by ``pool_padding`` zero entries; entry j (0-based) releases a prediction when j + 1 >= pool_size -
+        pool_padding, the mean over pool_size of entries max(0, j + 1 - pool_size) .. j (entries >= ``frames`` and the ones
+        before the first are zeros).  ``entries`` lists (first, last) of every prediction, inclusive, in order."""
+        frames = self.prime_clip_frames(t)[-1] if (pad_end and t > 0) else self.prime_counts(t)[-1]
+        total = frames + (self.pool_padding if (pad_end and t > 0) else 0)
+        first = max(0, self.pool_size - self.pool_padding - 1)
+        return frames, [(max(0, j + 1 - self.pool_size), j) for j in range(first, total)]
+
+    def features_clip_as_steps(self, x):
+        """(N, C, T, V, M) -> (N*M, 256, T', V): the layer-10 feature frames of ONE clip pass in which every adaptive graph conv
+        forms its attention per frame (``AdaptiveGraphConvolution.forward_framewise``) -- frame j is what the steps emit as
+        their j-th layer-10 frame, as long as they emit it (``clip_as_steps_map``); the frames behind it are the ones the end
+        padding releases.  Intake, pre-normalisation and modality as the steps apply them (a motion modality: the backward
+        difference, ``_history_as_stepped``).  Reads and writes no continual state."""
+        self._require_eval()
+        x = self._intake_clip(x)
+        native.require_device_f32(x, "CoAGcn input")
+        _, d = self._history_as_stepped(x)
+        n, c, t, v, m = d.shape
+        ops = self._packed_ops(x.device)
+        h = torch.empty((n * m, c, t, v), device=x.device, dtype=torch.float32)
+        rc = native.lib().csk_input_norm_f32(native.ptr(d), native.ptr(ops["scale"]), native.ptr(ops["shift"]), native.ptr(h),
+                                             n, c, t, v, m, c * t * v, t * v, native.stream_of(x))
+        native.check(rc, "csk_input_norm_f32")
+        for blk in self._blocks:
+            # the two stages of SpatioTemporalBlock.forward_parts, the first one frame-wise
+            h = blocks.SpatioTemporalBlock._tail(blk, h, blk.gcn.forward_framewise(h), None)
+        return h
+
+    def forward_clip_as_steps(self, x, pad_end=False):
+        """(N, C, T, V, M) -> (N, classes, n_predictions): what ``clean_state(); forward_steps(x, pad_end)`` returns (within the
+        clip-versus-steps tolerance), by one clip pass (``features_clip_as_steps``) and the continual head applied to the
+        feature frames in the steps' alignment (``clip_as_steps_map``): per-frame spatial pool, the zero-initialised pooling
+        window -- the summation order of the step kernel, oldest entry first -- and the FC.  Neither reads nor writes the
+        continual state; needs no bound slab."""
+        h = self.features_clip_as_steps(x)
+        n, t = x.shape[0], x.shape[self.time_axis]
+        _, _, v, m = self.input_shape
+        frames, entries = self.clip_as_steps_map(t, pad_end)
+        if h.shape[2] < frames:
+            raise RuntimeError(f"the clip pass gave {h.shape[2]} feature frames, the steps emit {frames}")
+        if not entries:
+            return torch.empty((n, self.num_classes, 0), device=x.device)
+        lib, stream, w = native.lib(), native.stream_of(h), self.pool_size
+        # entries of the pooling window, [entry][N][256]: the spatial pool of feature frame j, then zeros (end padding; slots
+        # the kernel never reads fill the array up to one window behind the last entry)
+        ring = torch.zeros((max(entries[-1][1] + 1, w) + w, n, 256), device=x.device, dtype=torch.float32)
+        if frames:
+            hf = h[:, :, :frames].permute(2, 0, 1, 3).contiguous()          # (frames, N*M, 256, V): a frame = N "samples" of M
+            native.check(lib.csk_pool_scaled_f32(native.ptr(hf), native.ptr(ring), frames * n, m, 256, v, 1.0, stream),
+                         "csk_pool_scaled_f32")
+        pooled = torch.empty((len(entries), n, 256), device=x.device, dtype=torch.float32)
+        for k, (first, last) in enumerate(entries):
+            # window slots first .. first + w - 1 of the array; the `count` newest end at entry `last`
+            native.check(lib.csk_co_window_mean_f32(native.ptr(ring[first]), native.ptr(pooled[k]), n * 256, w, last - first,
+                                                    last - first + 1, stream), "csk_co_window_mean_f32")
+        logits = torch.empty((len(entries), n, self.num_classes), device=x.device, dtype=torch.float32)
+        native.check(lib.csk_fc_f32(native.ptr(pooled), native.ptr(self.fc.weight.detach()), native.ptr(self.fc.bias.detach()),
+                                    native.ptr(logits), len(entries) * n, 256, self.num_classes, stream), "csk_fc_f32")
+        return logits.permute(1, 2, 0).contiguous()
 
 
 class AGcnMod(StGcnMod):

@@ -38,6 +38,8 @@ SIGNATURES = {
     "csk_pool_scaled_f32": [_p, _p, _i, _i, _i, _i, C.c_float, _p],
     "csk_agcn_attention_f32": [_p, _p, _p, _p, _i, _i, _i, _i, _l, _l, _i, _l, _p],
     "csk_agcn_embed_attention_f32": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _l, _l, _p],
+    "csk_agcn_stage_framewise_f32": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _l, _l, _l, _l, _i, _p],
+    "csk_agcn_stage_framewise_f32_route": [_p, _i, _i, _i, _i, _i, _i, _l, _l, _i],
     "csk_tcn_step_f32": [_p, _i, _i, _i, _i, _p, _p, _i, _i, _i, _p, _p, _p, _i, _i, _i, _i, _l, _i, _i, _i, _i, _i, _p, _p],
     "csk_tcn_step_f32_tile": [_i, _i, _i, _i, _i, _i, _i, _l, _i, _i, _i, _i],
     "csk_tcn_step_bf16x3": [_p, _i, _i, _i, _i, _p, _p, _i, _i, _i, _p, _p, _p, _i, _i, _i, _i, _l, _i, _i, _i, _i, _p],

@@ -376,6 +376,30 @@ int csk_agcn_embed_attention_f32(const float *x, const float *w_pairs, const flo
                                  float *scratch, int n_seg, int c_in, int inter, int frames, int V, int per_frame,
                                  int64_t x_seg_stride, int64_t x_chan_stride, void *stream);
 
+/*
+ * The adaptive graph-conv stage applied PER FRAME to a clip tensor in one launch (csrc/agcn_framewise.hip): for every (segment,
+ * frame) what csk_agcn_embed_attention_f32 (per_frame = 1) followed by csk_gcn_stage_f32 (adj_per_frame = 1) compute -- the step
+ * form of the module, models/coa_gcn/coa_gcn.py:11-14 -- with the per-frame adjacencies kept in LDS / registers: the entry takes
+ * no adjacency buffer.  With x_f = x[seg, :, f, :]:
+ *     E_f = W_e x_f + b_e;   L_i[v, w] = sum_k Ea_i[k, v] Eb_i[k, w] / inter;   adj_i = softmax over v of L_i + a_sum_i
+ *     y_f = ReLU( sum_i W'_i (x_f adj_i) + b' + gcn_residual(x_f) )
+ * x, y, w, bias, strides, res_mode as csk_gcn_stage_f32; w_pairs, b_pairs, a_sum as csk_agcn_embed_attention_f32.  The softmax
+ * arithmetic is that entry's; the aggregation sums even and odd joints in separate chains (csrc/gcn_dense.hip); the channel mix is
+ * exact-fp32 MFMA.  A frame's result does not depend on `frames`, on its position or on the other frames (bitwise).  Results
+ * differ from the two composed entries by fp32 summation order only.
+ * Built for V in {18, 25}, inter in {16, 32, 64} with c_out == 4 * inter, any c_in (even V: rows 8-byte aligned); fails with a
+ * message otherwise (callers then compose the two entries).
+ */
+int csk_agcn_stage_framewise_f32(const float *x, float *y, const float *w, const float *bias, const float *w_pairs,
+                                 const float *b_pairs, const float *a_sum, int n_seg, int c_in, int c_out, int inter, int frames,
+                                 int V, int64_t x_seg_stride, int64_t x_chan_stride, int64_t y_seg_stride, int64_t y_chan_stride,
+                                 int res_mode, void *stream);
+/* The instantiation agcn_stage_framewise_kernel<INTER, V, CONVRES> that call launches, as INTER * 1000 + V * 10 + CONVRES; 0 where
+ * the shape is not built (the call fails); -1 (csk_last_error set) on bad dims.  Host arithmetic only (no GPU): of x only the
+ * alignment is read.  The launcher switches on the function this entry reports. */
+int csk_agcn_stage_framewise_f32_route(const float *x, int n_seg, int c_in, int c_out, int inter, int frames, int V,
+                                       int64_t x_seg_stride, int64_t x_chan_stride, int res_mode);
+
 /* ------------------------------------------------------------------------------------------------
  * Continual (frame-by-frame) path.  The arithmetic the reference delegates to the third-party package
  * continual-inference (co.Conv2d / co.Delay / co.Residual / co.AvgPool1d, call sites models/base.py:73-101,
