@@ -330,6 +330,32 @@ class CoAGcn(CoStGcn):
                                     native.ptr(logits), len(entries) * n, 256, self.num_classes, stream), "csk_fc_f32")
         return logits.permute(1, 2, 0).contiguous()
 
+    # ---- priming from buffered history at the steps' arithmetic (DESIGN.md sections 3e, 3h) ------------------------------
+    @staticmethod
+    def _framewise_parts(blk, h):
+        """``(y, out)`` of a block with the attention formed per frame: the two stages ``features_clip_as_steps`` composes."""
+        y = blk.gcn.forward_framewise(h)
+        return y, blocks.SpatioTemporalBlock._tail(blk, h, y, None)
+
+    def prime_state_as_steps(self, x_hist):
+        """``prime_state`` for this family: the ``StreamState`` of ``n`` streams that have received the frames of ``x_hist``
+        (n, C, T, V, M), by the clip pass of ``prime_state`` with every adaptive graph conv run frame-wise
+        (``forward_framewise``: the post-GCN tensors are then the ones the steps' rings hold; the induction of 3e holds as it
+        stands, the graph conv being per frame) and the same single pack launch per chunk of streams.  Every check of
+        ``prime_state`` but the adaptive-graph-conv refusal, before anything launches; ``prime_state`` itself keeps refusing
+        this class.  ``framewise_everywhere`` / ``fuse_framewise`` pick the fused kernel or the composed launches per block; a
+        record's bits depend on neither, nor on the chunking.  Memory: ``prime_stream_bytes(T)`` of intermediates per stream,
+        in chunks under ``prime_budget_bytes``, plus -- where a block composes the per-frame launches -- that block's chunk
+        of per-frame adjacencies (and embeddings) under ``AdaptiveGraphConvolution.framewise_budget_bytes`` (256 MiB), one
+        block's at a time."""
+        return self._prime_records(x_hist, self._check_prime(x_hist, framewise=True), self._framewise_parts)
+
+    def prime_streams_as_steps(self, x_hist, indices):
+        """``import_streams(prime_state_as_steps(x_hist), indices)``; every host check of both halves runs before the first
+        launch."""
+        self._check_prime_streams(x_hist, indices, framewise=True)
+        self.import_streams(self.prime_state_as_steps(x_hist), indices)
+
 
 class AGcnMod(StGcnMod):
     """A-GCN*: models/a_gcn_mod/a_gcn_mod.py:67-124 -- StGcnMod's table, geometry (T >= 81, one feature frame per input frame from

@@ -82,13 +82,15 @@ class StreamPrime:
         return 4 * words
 
     # ---- checks (host only, before anything launches) ------------------------------------------------
-    def _check_prime(self, x_hist):
-        """Everything ``prime_state`` refuses; returns T."""
+    def _check_prime(self, x_hist, framewise=False):
+        """Everything ``prime_state`` refuses; returns T.  ``framewise``: the caller's clip pass forms the attention of an
+        adaptive graph conv per frame (``CoAGcn.prime_state_as_steps``, agcn.py), so that refusal is not made; every other
+        check is the same."""
         self._require_eval()
         if self.unpadded:
             raise NotImplementedError(f"prime_state is not built for the unpadded '*' models ({type(self).__name__}): their valid clip "
                                       "form shifts every frame index; that table is a follow-up -- reset_streams and step the history")
-        if any(any(k.__name__ == "AdaptiveGraphConvolution" for k in type(b.gcn).__mro__) for b in self._blocks):
+        if not framewise and any(any(k.__name__ == "AdaptiveGraphConvolution" for k in type(b.gcn).__mro__) for b in self._blocks):
             raise NotImplementedError(f"prime_state cannot serve {type(self).__name__}: the clip form of the adaptive graph conv forms one "
                                       "adjacency over all T frames, the steps one per frame (clip != step by design); reset_streams "
                                       "and step the history")
@@ -117,10 +119,10 @@ class StreamPrime:
         native.require_device_f32(x_hist, "history tensor")
         return t
 
-    def _check_prime_streams(self, x_hist, indices):
+    def _check_prime_streams(self, x_hist, indices, framewise=False):
         """The host checks of both halves of ``prime_streams``: ``prime_state``'s, then ``import_streams``' on a record-less
         stand-in with the lengths, ages and signature the real state will have."""
-        t = self._check_prime(x_hist)
+        t = self._check_prime(x_hist, framewise)
         ages = torch.full((x_hist.shape[0],), t, dtype=torch.int64)
         return self._check_import(StreamState(torch.empty((x_hist.shape[0], 0)), ages, self.move_signature()), indices)
 
@@ -139,10 +141,11 @@ class StreamPrime:
             d = shifted
         return xn, d
 
-    def _prime_chunk(self, x, packed):
+    def _prime_chunk(self, x, packed, parts=SpatioTemporalBlock.forward_parts):
         """Records of the streams ``x`` (n, C, T, V, M) into ``packed`` (n, record_floats): the clip pass with every block's
         post-GCN tensor and output kept, then one pack launch.  With the keypoint intake on, ``x`` is the (n, T, P, V, 3)
-        keypoint history and the selected clip takes its place first."""
+        keypoint history and the selected clip takes its place first.  ``parts(blk, h)`` yields ``(y, out)`` of a block: its
+        two clip stages, or a caller's form of them whose tensors are the steps' (agcn.py: the frame-wise graph conv)."""
         x = self._intake_clip(x)
         n, c, t, v, m = x.shape
         ops = self._packed_ops(x.device)
@@ -153,7 +156,7 @@ class StreamPrime:
         native.check(rc, "csk_input_norm_f32")
         clip = {"xin0": h}
         for i, blk in enumerate(self._blocks):
-            clip[f"y{i}"], h = SpatioTemporalBlock.forward_parts(blk, h)
+            clip[f"y{i}"], h = parts(blk, h)
             clip[f"out{i}"] = h
         small = {}
         if self.input_modality in MOTION:               # the last normalised raw frame; every stream has a previous frame
@@ -194,13 +197,17 @@ class StreamPrime:
         and at least D(10), the age from which every block of a fresh model is live (76 for the ten-block table).  Needs no
         bound slab and neither reads nor writes the continual state.  Memory: ``prime_stream_bytes(T)`` of intermediates per
         stream (84.8 MB for NTU at T = 300: 12 streams per chunk); the streams are primed in chunks that stay below ``prime_budget_bytes``
-        (1 GiB; at least one stream per chunk).  Not built for ``CoAGcn``, the '*' models and the 'bf16x3' clip precision."""
-        t = self._check_prime(x_hist)
+        (1 GiB; at least one stream per chunk).  Not built for the '*' models and the 'bf16x3' clip precision; ``CoAGcn`` is
+        refused under this name (its clip form is not its steps') and served by ``CoAGcn.prime_state_as_steps``."""
+        return self._prime_records(x_hist, self._check_prime(x_hist))
+
+    def _prime_records(self, x_hist, t, parts=SpatioTemporalBlock.forward_parts):
+        """``prime_state`` behind its checks: the chunks of streams under ``prime_budget_bytes``, each through ``_prime_chunk``."""
         n = x_hist.shape[0]
         packed = torch.empty((n, self.record_floats()), device=x_hist.device, dtype=torch.float32)
         chunk = max(1, int(self.prime_budget_bytes // self.prime_stream_bytes(t)))
         for lo in range(0, n, chunk):
-            self._prime_chunk(x_hist[lo:lo + chunk], packed[lo:lo + chunk])
+            self._prime_chunk(x_hist[lo:lo + chunk], packed[lo:lo + chunk], parts)
         return StreamState(packed, torch.full((n,), t, dtype=torch.int64), self.move_signature())
 
     def prime_streams(self, x_hist, indices):

@@ -30,6 +30,7 @@ import torch.nn as nn
 
 from . import blocks, fold, native
 from .blocks import GraphConvolution, SpatioTemporalBlock, TemporalConvolution, _Folded, init_weights, is_plain_graph_conv, unity, zero
+from .co_clip import ClipAsSteps
 from .co_plan import NativePlan
 from .co_migrate import StreamMove
 from .co_prime import StreamPrime
@@ -563,7 +564,7 @@ def co_geometry(c_in=3, unpadded=False):
     return r, p, s
 
 
-class CoStGcn(NativePlan, StreamReset, StreamMove, StreamPrime, ContinualKeypointIntake, ContinualPreNorm, ContinualModality, _Folded):
+class CoStGcn(NativePlan, StreamReset, StreamMove, StreamPrime, ClipAsSteps, ContinualKeypointIntake, ContinualPreNorm, ContinualModality, _Folded):
     """CoST-GCN: models/cost_gcn/cost_gcn.py:21-41 + CoModelBase (models/base.py:68-227) without the Ride shell.
 
     ``forward_step(x_t: (N, C, V, M))`` -> logits (N, classes) on the steps where the whole stack (10 blocks,
@@ -572,7 +573,8 @@ class CoStGcn(NativePlan, StreamReset, StreamMove, StreamPrime, ContinualKeypoin
     state_dict keys equal the reference's (``layers.layerK.0.1.gcn...``); a regular StGcn state_dict loads too
     (what ``map_state_dict`` does in the reference, base.py:200-224).  This class binds the state slab and steps on it; the
     native plan (co_plan.py: NativePlan), the per-stream reset (co_reset.py: StreamReset), moving streams between slabs
-    (co_migrate.py: StreamMove), priming streams from buffered history with one clip pass (co_prime.py: StreamPrime) and the input modality
+    (co_migrate.py: StreamMove), priming streams from buffered history with one clip pass (co_prime.py: StreamPrime), a stored clip at the
+    steps' arithmetic (co_clip.py: ClipAsSteps -- ``forward_clip_as_steps``) and the input modality
     (modality.py: ContinualModality -- bone / motion frames derived from the joint frames in front of every cycle) are base classes,
     and so is the pre-normalisation of raw joint frames (prenorm.py: ContinualPreNorm), which runs in front of the modality.
     The keypoint intake (keypoints.py: ContinualKeypointIntake; off by default) runs in front of both: with it the model is fed
@@ -944,7 +946,10 @@ class CoStGcn(NativePlan, StreamReset, StreamMove, StreamPrime, ContinualKeypoin
     def _clip_features(self, x):
         native.require_device_f32(x, "CoStGcn input")
         # pre-normalised joints (clip form; off: x itself), then the bone / motion clip (forward difference, as the reference's files)
-        x = self._derive_clip(self._prenorm_clip(x))
+        return self._clip_stack(self._derive_clip(self._prenorm_clip(x)))
+
+    def _clip_stack(self, x):
+        """Input norm and the ten clip blocks on the derived frames ``x`` (N, C, T, V, M) -> (N*M, 256, T', V)."""
         n, c, t, v, m = x.shape
         ops = self._packed_ops(x.device)
         h = torch.empty((n * m, c, t, v), device=x.device, dtype=torch.float32)

@@ -192,6 +192,170 @@ extern "C" int csk_co_head_step_f32(const float *h, float *pool_ring, float *poo
     return (int)hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------
+// The continual head over a whole CLIP in one call (csk_co_head_clip_f32, include/cskel.h): every prediction a
+// fresh model stepped through the clip would release, from the clip tensor of layer 10.  Two kernels inside one C call, no
+// host loop over predictions:
+//   pool pass    entries[j][n][c] = spatial mean of feature frame j < frames over the stream's M * V positions -- the arithmetic
+//                of co_head_kernel's pool (lane-strided partial sums over p = m * V + v, the xor butterfly 32 .. 1, one division
+//                by (float)(M * V)), on the clip layout (n * M, C, t_src, V) as the pool job of stream_prime.hip reads it.  A
+//                wave takes CLIP_FJ consecutive frames of one (n, c): their V-float runs are contiguous in memory.  Only the
+//                frames some prediction's window holds are pooled (j_lo .. j_hi - 1).
+//   window + FC  one workgroup per (stream, group of G predictions).  The entries the group's windows cover -- their union,
+//                at most window + G - 1 of them -- are staged in LDS, channel slice by channel slice (the table of a whole
+//                clip does not fit: 220 entries x 256 channels are 225 KB); an entry >= frames is +0.0, the end padding of
+//                the window, and is never read from memory.  Every prediction re-sums ITS window from LDS, oldest entry
+//                first, and divides by (float)window: co_window_mean_kernel's order (a running sum across predictions would
+//                change the bits).  Then fc_kernel's four interleaved chains, a chain per thread as in co_head_kernel, with
+//                the group's G accumulators per thread so that a weight is loaded once per group.
+// ------------------------------------------------------------------------------------------------
+static constexpr int CLIP_FJ = 8;          // frames of one (stream, channel) a wave pools together
+static constexpr int CLIP_G = 16;          // most predictions of one workgroup
+static constexpr int CLIP_LDS_FLOATS = 8192;   // of the staged entries, and of the group's pooled rows: 32 KB each
+
+__global__ __launch_bounds__(256) void co_head_clip_pool_kernel(const float *__restrict__ h, float *__restrict__ entries, int t_src,
+                                                                int j_lo, int j_hi, int N, int M, int C, int V, int jgroups,
+                                                                int64_t total) {
+    const int lane = threadIdx.x & 63, MV = M * V;
+    const int64_t chan = (int64_t)t_src * V;            // floats of one (sequence, channel) of the source
+    for (int64_t g = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6; g < total; g += (int64_t)gridDim.x * 4) {
+        const int c = (int)(g % C);
+        const int64_t r = g / C;
+        const int j0 = j_lo + (int)(r % jgroups) * CLIP_FJ;
+        const int64_t n = r / jgroups;
+        const float *src0 = h + (n * M * C + c) * chan;
+        float a[CLIP_FJ];
+#pragma unroll
+        for (int u = 0; u < CLIP_FJ; ++u) a[u] = 0.f;
+        for (int p = lane; p < MV; p += 64) {
+            const float *src = src0 + (int64_t)(p / V) * C * chan + p % V;
+#pragma unroll
+            for (int u = 0; u < CLIP_FJ; ++u) a[u] += src[(int64_t)min(j0 + u, j_hi - 1) * V];      // j_hi <= frames: no frame behind them is read
+        }
+#pragma unroll
+        for (int u = 0; u < CLIP_FJ; ++u) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) a[u] += __shfl_xor(a[u], o);
+            if (lane == 0 && j0 + u < j_hi) entries[((int64_t)(j0 + u) * N + n) * C + c] = a[u] / (float)MV;
+        }
+    }
+}
+
+// grid (groups of G predictions, N); LDS: staged entries [span][cc] | pooled rows of the group [G][C]
+__global__ __launch_bounds__(256) void co_head_clip_kernel(const float *__restrict__ entries, int frames, int window, int first_entry,
+                                                           int n_pred, int G, int cc, const float *__restrict__ w,
+                                                           const float *__restrict__ b, float *__restrict__ pooled,
+                                                           float *__restrict__ logits, int N, int C, int classes) {
+    extern __shared__ __attribute__((aligned(16))) float hs[];
+    const int tid = threadIdx.x, n = blockIdx.y;
+    const int k0 = blockIdx.x * G, ng = min(G, n_pred - k0);
+    const int64_t e_first = (int64_t)first_entry + k0;                     // the entry prediction k0 closes on
+    const int64_t e_lo = max((int64_t)0, e_first + 1 - window);            // oldest entry of the group's windows
+    const int span = (int)(e_first + ng - e_lo);                           // <= window + G - 1
+    float *stage = hs, *pool_s = hs + CLIP_LDS_FLOATS;
+    for (int c0 = 0; c0 < C; c0 += cc) {
+        const int cw = min(cc, C - c0);
+        if (c0) __syncthreads();                                           // the slice before has been summed
+        for (int i = tid; i < span * cw; i += 256) {
+            const int r = i / cw, c = i % cw;
+            const int64_t e = e_lo + r;
+            stage[i] = e < frames ? entries[(e * N + n) * C + c0 + c] : 0.f;
+        }
+        __syncthreads();
+        for (int i = tid; i < ng * cw; i += 256) {
+            const int kk = i / cw, c = i % cw;
+            const int64_t e = e_first + kk;
+            const int lo = (int)(max((int64_t)0, e + 1 - window) - e_lo), hi = (int)(e - e_lo);
+            float s = 0.f;
+#pragma unroll 8
+            for (int j = lo; j <= hi; ++j) s += stage[j * cw + c];         // oldest first
+            s = s / (float)window;
+            pooled[((int64_t)(k0 + kk) * N + n) * C + c0 + c] = s;
+            pool_s[kk * C + c0 + c] = s;
+        }
+    }
+    __syncthreads();
+    // FC: channel c goes to chain c mod 4, combined as (s0 + s1) + (s2 + s3); four neighbouring lanes share a class
+    const int chain = tid & 3;
+    for (int q0 = 0; q0 < classes; q0 += 64) {
+        const int q = q0 + (tid >> 2);
+        const float *wr = w + (int64_t)min(q, classes - 1) * C;
+        float acc[CLIP_G];
+#pragma unroll
+        for (int g = 0; g < CLIP_G; ++g) acc[g] = 0.f;
+        int c = chain;
+        for (; c + 28 < C; c += 32) {                                       // eight weight loads in flight
+            float wv[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) wv[u] = wr[c + 4 * u];
+#pragma unroll
+            for (int g = 0; g < CLIP_G; ++g)
+                if (g < ng) {
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) acc[g] = fmaf(pool_s[g * C + c + 4 * u], wv[u], acc[g]);
+                }
+        }
+        for (; c < C; c += 4) {
+            const float wv = wr[c];
+#pragma unroll
+            for (int g = 0; g < CLIP_G; ++g)
+                if (g < ng) acc[g] = fmaf(pool_s[g * C + c], wv, acc[g]);
+        }
+#pragma unroll
+        for (int g = 0; g < CLIP_G; ++g) {
+            float sc = acc[g];
+            sc += __shfl_xor(sc, 1);                                        // lanes 0 / 2 of a quad: s0 + s1, s2 + s3
+            sc += __shfl_xor(sc, 2);                                        // (s0 + s1) + (s2 + s3)
+            if (g < ng && chain == 0 && q < classes) logits[((int64_t)(k0 + g) * N + n) * classes + q] = sc + b[q];
+        }
+    }
+}
+
+extern "C" int csk_co_head_clip_f32(const float *h, int t_src, int frames, float *entries, int window, int first_entry, int n_pred,
+                                    const float *fc_w, const float *fc_b, float *pooled, float *logits, int N, int M, int C, int V,
+                                    int classes, void *stream) {
+    if (!h || !fc_w || !fc_b || !pooled || !logits) CSK_FAIL("co_head_clip: null pointer");
+    if (N < 1 || M < 1 || C < 1 || V < 1 || classes < 1 || t_src < 1)
+        CSK_FAIL("co_head_clip: bad dims (N %d, M %d, C %d, V %d, classes %d, t_src %d)", N, M, C, V, classes, t_src);
+    if (frames < 0 || frames > t_src) CSK_FAIL("co_head_clip: %d real frames of a source of %d", frames, t_src);
+    if (frames > 0 && !entries) CSK_FAIL("co_head_clip: null pointer (entries scratch of %d frames)", frames);
+    if (window < 1) CSK_FAIL("co_head_clip: a window of %d entries", window);
+    if (first_entry < 0) CSK_FAIL("co_head_clip: first_entry %d < 0", first_entry);
+    if (n_pred < 0) CSK_FAIL("co_head_clip: n_pred %d < 0", n_pred);
+    if ((int64_t)first_entry + n_pred > INT32_MAX) CSK_FAIL("co_head_clip: first_entry + n_pred overflows");
+    if ((int64_t)M * V > INT32_MAX) CSK_FAIL("co_head_clip: bad dims (M * V = %lld)", (long long)M * V);
+    if (N > 65535) CSK_FAIL("co_head_clip: at most 65535 streams per call, got %d", N);
+    const uintptr_t all = reinterpret_cast<uintptr_t>(h) | reinterpret_cast<uintptr_t>(entries) | reinterpret_cast<uintptr_t>(fc_w) |
+                          reinterpret_cast<uintptr_t>(fc_b) | reinterpret_cast<uintptr_t>(pooled) | reinterpret_cast<uintptr_t>(logits);
+    if (all & 3) CSK_FAIL("co_head_clip: a pointer is not 4-byte aligned");
+    // fc_kernel's rule: with C a multiple of 4 its rows are read 16 bytes at a time
+    if ((C & 3) == 0 && ((reinterpret_cast<uintptr_t>(pooled) & 15) || (reinterpret_cast<uintptr_t>(fc_w) & 15)))
+        CSK_FAIL("co_head_clip: pooled / fc_w must be 16-byte aligned when C is a multiple of 4");
+    // the group's pooled rows [G][C] and one channel of its staged entries [window + G - 1] must fit their 32 KB of LDS
+    if (C > CLIP_LDS_FLOATS) CSK_FAIL("co_head_clip: at most %d channels, got %d", CLIP_LDS_FLOATS, C);
+    const int G = CLIP_LDS_FLOATS / C < CLIP_G ? CLIP_LDS_FLOATS / C : CLIP_G;
+    if ((int64_t)window + G - 1 > CLIP_LDS_FLOATS) CSK_FAIL("co_head_clip: a window of %d entries (at most %d)", window, CLIP_LDS_FLOATS - G + 1);
+    if (n_pred == 0) return 0;
+    // the entries some window holds: from the oldest of prediction 0 to the one the last prediction closes on, as far as real
+    const int64_t lo64 = (int64_t)first_entry + 1 - window, hi64 = (int64_t)first_entry + n_pred;
+    const int j_lo = (int)(lo64 < 0 ? 0 : lo64), j_hi = (int)(hi64 < frames ? hi64 : frames);
+    if (j_lo < j_hi) {
+        const int jgroups = (j_hi - j_lo + CLIP_FJ - 1) / CLIP_FJ;
+        const int64_t total = (int64_t)N * C * jgroups, want = (total + 3) / 4;
+        hipLaunchKernelGGL(co_head_clip_pool_kernel, dim3((unsigned)(want < (1 << 20) ? want : (1 << 20))), dim3(256), 0, (hipStream_t)stream,
+                           h, entries, t_src, j_lo, j_hi, N, M, C, V, jgroups, total);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return (int)e;
+    }
+    // channels per staged slice: all of them where the union of a group's windows fits, else whole 64-channel runs, else what fits
+    const int span = window + G - 1;
+    int cc = CLIP_LDS_FLOATS / span;
+    cc = cc >= C ? C : (cc >= 64 ? cc & ~63 : cc);
+    hipLaunchKernelGGL(co_head_clip_kernel, dim3((unsigned)((n_pred + G - 1) / G), (unsigned)N), dim3(256), 2 * CLIP_LDS_FLOATS * sizeof(float),
+                       (hipStream_t)stream, entries, frames, window, first_entry, n_pred, G, cc, fc_w, fc_b, pooled, logits, N, C, classes);
+    return (int)hipGetLastError();
+}
+
 // input permute + data_bn of up to 8 frames of a launch cycle in ONE launch (continual form: T = 1 per frame):
 // frame f: x = src[f] (N, C, V, M) -> dst[f] channel-major (C, P)
 struct NormFrames {

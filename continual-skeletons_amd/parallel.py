@@ -203,6 +203,17 @@ class StreamShards:
         self._check_import(co_migrate.StreamState(torch.empty((x_hist.shape[0], 0)), ages, first.move_signature()), indices)
         self.import_streams(first.prime_state(x_hist), indices)
 
+    def prime_streams_as_steps(self, x_hist, indices):
+        """``CoAGcn.prime_streams_as_steps`` for GLOBAL stream indices: ``prime_streams`` with the first shard's
+        ``prime_state_as_steps`` (the clip pass whose adaptive graph convs form their attention per frame)."""
+        first = self.models[0]
+        if not hasattr(first, "prime_state_as_steps"):
+            raise NotImplementedError(f"prime_streams_as_steps serves CoAGcn shards; {type(first).__name__} takes prime_streams")
+        t = first._check_prime(x_hist, framewise=True)
+        ages = torch.full((x_hist.shape[0],), t, dtype=torch.int64)
+        self._check_import(co_migrate.StreamState(torch.empty((x_hist.shape[0], 0)), ages, first.move_signature()), indices)
+        self.import_streams(first.prime_state_as_steps(x_hist), indices)
+
     def streams_ready(self):
         """(N,) bool CPU tensor over the global stream axis (``CoStGcn.streams_ready`` of every shard, concatenated)."""
         return torch.cat([m.streams_ready() for m in self.models], dim=0)

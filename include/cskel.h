@@ -28,7 +28,7 @@ extern "C" {
 #endif
 
 /* Stays 16 while entries are only added: csk_derive_modality_f32 / _frames_f32, csk_prenorm_f32 / _frames_f32,
- * csk_tcn_stage_wino_valid_f32, csk_tcn_stage_wino_valid_res_f32, csk_co_plan_set_delays, csk_gcn_stage_f32_route, csk_gcn_stage_splitk_f32_route, csk_co_prime_pack_f32 and
+ * csk_tcn_stage_wino_valid_f32, csk_tcn_stage_wino_valid_res_f32, csk_co_plan_set_delays, csk_gcn_stage_f32_route, csk_gcn_stage_splitk_f32_route, csk_co_prime_pack_f32, csk_co_head_clip_f32 and
  * csk_select_people_f32 / _frames_f32 and csk_ntu_intake_f32 are additive (no existing entry, struct
  * or constant changed). */
 #define CSK_ABI_VERSION 16
@@ -536,6 +536,24 @@ int csk_co_window_mean_f32(const float *ring, float *pooled, int64_t n_elem, int
  * pooled [N][C], logits [N][classes]. */
 int csk_co_head_step_f32(const float *h, float *pool_ring, float *pooled, const float *fc_w, const float *fc_b, float *logits,
                          int N, int C, int MV, int64_t P, int window, int head, int count, int emit, int classes, void *stream);
+
+/* The continual head over a whole CLIP in one call: every prediction a fresh model stepped through the clip releases, from the
+ * clip tensor of the last block.  h (N*M, C, t_src, V) contiguous; its frames 0 .. frames-1 are real, the
+ * frames behind them are never read.  Entry j < frames of the pooling window is the spatial mean of frame j over the stream's
+ * M*V positions, in the arithmetic and summation order of csk_co_head_step_f32's pool (the CSK_PRIME_POOL job of
+ * csk_co_prime_pack_f32); entries >= frames are +0.0 (the window's end padding), entries < 0 do not exist.  Prediction
+ * k = 0 .. n_pred-1 closes on entry e = first_entry + k: pooled[k] = (sum of entries max(0, e + 1 - window) .. e, oldest first)
+ * / window -- csk_co_window_mean_f32's order, re-summed per prediction -- and logits[k] = pooled[k] @ fc_w^T + fc_b with
+ * csk_fc_f32's four interleaved chains: bit for bit the composition pool job -> csk_co_window_mean_f32 per prediction ->
+ * csk_fc_f32.  entries: caller-owned scratch [frames][N][C] (may be NULL when frames == 0), written by a pool kernel and read
+ * by a window + FC kernel (one workgroup per stream and group of 16 predictions), both issued by this call; pooled
+ * [n_pred][N][C], logits [n_pred][N][classes].  Checked on the host before anything is launched (-1, csk_last_error): null
+ * or misaligned pointers (4 bytes; pooled and fc_w 16 bytes when C % 4 == 0, csk_fc_f32's rule), a dim < 1, frames outside
+ * 0..t_src, window < 1, first_entry < 0, n_pred < 0; limits of this form: C <= 8192, window <= 8192 - 15, N <= 65535.
+ * n_pred == 0 launches nothing. */
+int csk_co_head_clip_f32(const float *h, int t_src, int frames, float *entries, int window, int first_entry, int n_pred,
+                         const float *fc_w, const float *fc_b, float *pooled, float *logits, int N, int M, int C, int V,
+                         int classes, void *stream);
 
 /* csk_input_norm_f32 for the r = 1..8 frames of a launch cycle in one launch (continual form, T = 1): frames[f] (N, C, V, M)
  * -> dst[f] channel-major (C, P) (models/base.py:73-82).  frames / dst are HOST arrays of device pointers. */
