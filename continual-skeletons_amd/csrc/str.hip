@@ -180,16 +180,32 @@ __global__ __launch_bounds__(NTHREADS) void str_attention_kernel(const float *__
 // part of its chunk) takes 128 rows where the packed width Mpad is a multiple of 128 (M = 96, 384; no tile reads weight columns
 // beyond Mpad); the output projection and M = 192 take 64 rows.  Measured at NTU batch 256 (profiles/HISTORY.md round 8): 128-row
 // tiles cut the 256-channel QKV launch from 3.21 to 2.69 ms but slowed every output projection (128 ch: 1.15 -> 1.65 ms).
+// The ONE copy of the rule: launch_str_gemm switches on it, csk_str_unit_f32_route reports it.  Host arithmetic only.
+struct StrGemmTiling {
+    int Mpad, mi;                    // packed width; MI of the instantiation (4: 128-row tiles, 2: 64-row tiles)
+    unsigned mtiles, ctiles, grid;
+};
+StrGemmTiling str_gemm_tiling(bool affine, int M, int ncols, int n_seg) {
+    StrGemmTiling t;
+    t.Mpad = round_up(M, SG_MT);
+    const bool wide = affine && M > 64 && t.Mpad % 128 == 0;
+    t.mi = wide ? 4 : 2;
+    t.mtiles = (unsigned)(t.Mpad / (wide ? 128 : 64));
+    t.ctiles = (unsigned)((ncols + SG_NT - 1) / SG_NT);
+    t.grid = t.mtiles * t.ctiles * (unsigned)n_seg;
+    return t;
+}
+
 template <bool AFFINE, bool RES, bool RELU>
 int launch_str_gemm(StrGemmParams &p, int n_seg, hipStream_t s) {
-    p.Mpad = round_up(p.M, SG_MT);
-    const bool wide = AFFINE && p.M > 64 && p.Mpad % 128 == 0;
-    p.mtiles = (unsigned)(p.Mpad / (wide ? 128 : 64));
-    p.ctiles = (unsigned)((p.ncols + SG_NT - 1) / SG_NT);
+    const StrGemmTiling t = str_gemm_tiling(AFFINE, p.M, p.ncols, n_seg);
+    p.Mpad = t.Mpad;
+    p.mtiles = t.mtiles;
+    p.ctiles = t.ctiles;
     p.vmagic = vmagic_of(p.V);
-    const dim3 grid(p.mtiles * p.ctiles * (unsigned)n_seg);
+    const dim3 grid(t.grid);
     if constexpr (AFFINE) {
-        if (wide) {
+        if (t.mi == 4) {
             hipLaunchKernelGGL((str_gemm_kernel<4, AFFINE, RES, RELU>), grid, dim3(NTHREADS), 0, s, p);
             return (int)hipGetLastError();
         }
@@ -223,6 +239,38 @@ int launch_str_attention_v(int dkh, const float *qkv, float *o, int n_seg, int f
         return -2;                                      \
     } while (0)
 
+// The shape arguments of the unit, refused or accepted in one place for the entry and for the route query: -1 / -2 with the message
+// set, or 0 with dkh and the row count of the qkv image.
+static int str_unit_shape(int n_seg, int c_in, int c_out, int frames, int V, bool has_res, int *dkh_out, int *rows_out) {
+    if (n_seg <= 0 || frames <= 0 || c_in <= 0 || c_out <= 0) CSK_FAIL("str_unit: n_seg, frames, c_in, c_out must be positive");
+    if (V != 18 && V != 25) CSK_UNSUPPORTED("str_unit: built for V in {18, 25}, got V = %d", V);
+    const int dk = c_out / 4, dkh = dk / 8;
+    if (c_out % 32 || (dkh != 1 && dkh != 2 && dkh != 4 && dkh != 8))
+        CSK_UNSUPPORTED("str_unit: built for C_out in {32, 64, 128, 256} (dkh = C_out / 32 in {1, 2, 4, 8}), got C_out = %d", c_out);
+    if (c_in % SG_KC) CSK_UNSUPPORTED("str_unit: C_in must be a multiple of %d, got %d", SG_KC, c_in);
+    if (has_res && c_in != c_out) CSK_FAIL("str_unit: the skip (res_scale) needs C_in == C_out (s_tr.py:468)");
+    const int64_t ncols = (int64_t)frames * V;
+    const int rows = 2 * dk + c_out;
+    if ((int64_t)n_seg * frames >= (1ll << 31) || (int64_t)rows * ncols >= (1ll << 31) ||
+        (int64_t)n_seg * ((ncols + SG_NT - 1) / SG_NT) * (round_up(rows, SG_MT) / SG_MT) >= (1ll << 31))
+        CSK_FAIL("str_unit: launch too large");
+    *dkh_out = dkh;
+    *rows_out = rows;
+    return 0;
+}
+
+extern "C" int csk_str_unit_f32_route(int n_seg, int c_in, int c_out, int frames, int V, int has_res, int32_t *route) {
+    if (!route) CSK_FAIL("str_unit_route: null route");
+    int dkh, rows;
+    if (const int rc = str_unit_shape(n_seg, c_in, c_out, frames, V, has_res != 0, &dkh, &rows)) return rc;
+    const int ncols = frames * V;
+    const StrGemmTiling a = str_gemm_tiling(true, rows, ncols, n_seg), b = str_gemm_tiling(false, c_out, ncols, n_seg);
+    const int32_t r[CSK_STR_ROUTE_WORDS] = {a.mi, (int32_t)a.mtiles, (int32_t)a.ctiles, (int32_t)a.grid, V, dkh, n_seg * frames,
+                                            has_res != 0, b.mi, (int32_t)b.mtiles, (int32_t)b.ctiles, (int32_t)b.grid};
+    for (int i = 0; i < CSK_STR_ROUTE_WORDS; ++i) route[i] = r[i];
+    return 0;
+}
+
 extern "C" int csk_str_unit_f32(const float *x, float *y, float *scratch, int64_t scratch_floats, const float *w_qkv,
                                 const float *b_qkv, const float *in_scale, const float *in_shift, const float *w_out,
                                 const float *b_out, const float *res_scale, int n_seg, int c_in, int c_out, int frames, int V,
@@ -230,23 +278,14 @@ extern "C" int csk_str_unit_f32(const float *x, float *y, float *scratch, int64_
                                 void *stream) {
     if (!x || !y || !scratch || !w_qkv || !b_qkv || !in_scale || !in_shift || !w_out || !b_out)
         CSK_FAIL("str_unit: null operand");
-    if (n_seg <= 0 || frames <= 0 || c_in <= 0 || c_out <= 0) CSK_FAIL("str_unit: n_seg, frames, c_in, c_out must be positive");
-    if (V != 18 && V != 25) CSK_UNSUPPORTED("str_unit: built for V in {18, 25}, got V = %d", V);
-    const int dk = c_out / 4, dkh = dk / 8;
-    if (c_out % 32 || (dkh != 1 && dkh != 2 && dkh != 4 && dkh != 8))
-        CSK_UNSUPPORTED("str_unit: built for C_out in {32, 64, 128, 256} (dkh = C_out / 32 in {1, 2, 4, 8}), got C_out = %d", c_out);
-    if (c_in % SG_KC) CSK_UNSUPPORTED("str_unit: C_in must be a multiple of %d, got %d", SG_KC, c_in);
-    if (res_scale && c_in != c_out) CSK_FAIL("str_unit: the skip (res_scale) needs C_in == C_out (s_tr.py:468)");
+    int dkh, rows;
+    if (const int rc = str_unit_shape(n_seg, c_in, c_out, frames, V, res_scale != nullptr, &dkh, &rows)) return rc;
     const int64_t ncols = (int64_t)frames * V;
     if (x_chan_stride < ncols || y_chan_stride < ncols) CSK_FAIL("str_unit: channel stride shorter than frames * V");
     if (x_seg_stride < 0 || y_seg_stride < 0) CSK_FAIL("str_unit: negative segment stride");
-    const int rows = 2 * dk + c_out;
     if (scratch_floats < (int64_t)n_seg * (rows + c_out) * ncols)
         CSK_FAIL("str_unit: scratch holds %lld floats, needs n_seg * (2 dk + 2 dv) * frames * V = %lld", (long long)scratch_floats,
                  (long long)((int64_t)n_seg * (rows + c_out) * ncols));
-    if ((int64_t)n_seg * frames >= (1ll << 31) || (int64_t)rows * ncols >= (1ll << 31) ||
-        (int64_t)n_seg * ((ncols + SG_NT - 1) / SG_NT) * (round_up(rows, SG_MT) / SG_MT) >= (1ll << 31))
-        CSK_FAIL("str_unit: launch too large");
     if ((reinterpret_cast<uintptr_t>(w_qkv) | reinterpret_cast<uintptr_t>(w_out)) & 15)
         CSK_FAIL("str_unit: packed weights must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;

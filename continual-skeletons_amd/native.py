@@ -70,6 +70,7 @@ SIGNATURES = {
     "csk_co_move_streams_f32": [_p, _i, _p, _l, _p, _i, _i, _i, _p],
     "csk_co_prime_pack_f32": [_p, _i, _p, _l, _i, _i, _i, _p],
     "csk_str_unit_f32": [_p, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _l, _l, _l, _l, _p],
+    "csk_str_unit_f32_route": [_i, _i, _i, _i, _i, _i, C.POINTER(C.c_int32)],
 }
 RESTYPES = {"csk_co_plan_create": C.c_void_p, "csk_co_plan_destroy": None}
 

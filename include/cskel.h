@@ -28,7 +28,7 @@ extern "C" {
 #endif
 
 /* Stays 16 while entries are only added: csk_derive_modality_f32 / _frames_f32, csk_prenorm_f32 / _frames_f32,
- * csk_tcn_stage_wino_valid_f32, csk_tcn_stage_wino_valid_res_f32, csk_co_plan_set_delays, csk_gcn_stage_f32_route, csk_gcn_stage_splitk_f32_route, csk_co_prime_pack_f32, csk_co_head_clip_f32 and
+ * csk_tcn_stage_wino_valid_f32, csk_tcn_stage_wino_valid_res_f32, csk_co_plan_set_delays, csk_gcn_stage_f32_route, csk_gcn_stage_splitk_f32_route, csk_co_prime_pack_f32, csk_co_head_clip_f32, csk_str_unit_f32_route and
  * csk_select_people_f32 / _frames_f32 and csk_ntu_intake_f32 are additive (no existing entry, struct
  * or constant changed). */
 #define CSK_ABI_VERSION 16
@@ -894,7 +894,12 @@ int csk_co_prime_pack_f32(const csk_prime_job *jobs, int n_jobs, void *packed, i
  *  w_qkv    packed [c_in][Mq], Mq = 2 dk + dv rounded up to 64, zero columns beyond 2 dk + dv; b_qkv [Mq]   (16-B aligned)
  *  s_in / t_in  [c_in][V]
  *  w_out    packed [c_out][Mo], Mo = c_out rounded up to 64; b_out [Mo]; res_scale [c_out] or NULL (no skip)
- *  scratch  >= n_seg * (2 dk + 2 dv) * frames * V floats (scratch_floats): the qkv and attention-output images
+ *  scratch  >= n_seg * (2 dk + 2 dv) * frames * V floats (scratch_floats): the qkv and attention-output images.  Their layout is
+ *           part of the contract (the stage-wise tests read both): both dense, rows of frames * V columns,
+ *             qkv [n_seg][2 dk + dv][frames V] at offset 0 (rows: dk of q, dk of k, dv of v; head h owns q / k rows
+ *                                                           h dkh .. and v rows h dvh .., dkh = dk / 8, dvh = dv / 8)
+ *             o   [n_seg][dv][frames V]        at offset n_seg (2 dk + dv) frames V
+ *           every element of both images is written by every call; nothing beyond n_seg (2 dk + 2 dv) frames V floats is touched.
  * Three launches (data_bn + QKV GEMM, attention, output GEMM + epilogue); fp32 MFMA for both GEMMs, exact fp32 throughout.
  * Returns -2 for shapes not built: V not in {18, 25}, C_out not in {32, 64, 128, 256}, C_in not a multiple of 16.
  */
@@ -902,6 +907,18 @@ int csk_str_unit_f32(const float *x, float *y, float *scratch, int64_t scratch_f
                      const float *b_qkv, const float *s_in, const float *t_in, const float *w_out, const float *b_out,
                      const float *res_scale, int n_seg, int c_in, int c_out, int frames, int V, int64_t x_seg_stride,
                      int64_t x_chan_stride, int64_t y_seg_stride, int64_t y_chan_stride, void *stream);
+
+/*
+ * What the three launches of csk_str_unit_f32 run for a shape (has_res: res_scale != NULL).  Host arithmetic only, no GPU call:
+ * the function the launchers switch on.  route[CSK_STR_ROUTE_WORDS]:
+ *   [0..3]   QKV GEMM (data_bn at staging, M = 2 dk + dv rows): MI (tile rows = 32 MI), row tiles, column tiles (256 columns), grid
+ *   [4..6]   attention: V, DKH, grid (= n_seg * frames, one frame per workgroup)
+ *   [7..11]  output projection (M = c_out rows): RES (the skip is fused), MI, row tiles, column tiles, grid
+ * grid = row tiles * column tiles * n_seg; workgroup id -> (row tile fastest, column tile, segment) after the XCD remap.
+ * Returns 0, or the value csk_str_unit_f32 returns for the same (n_seg, c_in, c_out, frames, V, has_res): -1 / -2.
+ */
+#define CSK_STR_ROUTE_WORDS 12
+int csk_str_unit_f32_route(int n_seg, int c_in, int c_out, int frames, int V, int has_res, int32_t *route);
 
 #ifdef __cplusplus
 }
