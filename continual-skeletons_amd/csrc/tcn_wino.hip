@@ -20,9 +20,11 @@
 // 950 pair columns (T = 75, V = 25) issues 1024 columns in wide tiles and 960 in tall ones; the host takes per layer the shape
 // that measures faster (wino_pick_mw: stride 2 the tall one, stride 1 the tall one where it saves 1/16 of the columns; the wide
 // one where c_out % 128 != 0).  Tall: 12 (13) weight rows x 8 x 128 staged per chunk, 48 (52) prefetch registers per thread,
-// 255 VGPRs, 60.5 KB (70 KB stride 2) LDS at V = 25.
+// up to 256 VGPRs, 60.5 KB (70 KB stride 2) LDS at V = 25.
 // K loop: 8-channel chunks as in tcn_stage_kernel (tcn.hip), the next chunk's loads trickled in three thirds in front of the
-// three group segments.  The weights stream from the host-transformed image, the staging types are those of mfma_core.h.
+// three group segments.  Inside a chunk the LDS operands run ahead of the MFMAs in registers (wino_chunk): A fragments two
+// MFMA pairs ahead, raw samples half a K step ahead, across the group segments.  The weights stream from the host-transformed
+// image, the staging types are those of mfma_core.h.
 // T odd: the last pair's second frame (t = T) is computed from zero padding and not stored.
 //
 // csk_tcn_stage_wino_ext_f32 adds two forms for the blocks the entry above leaves to the direct kernels:
@@ -153,24 +155,117 @@ struct WStageRes128 {
     __device__ __forceinline__ void commit(float *__restrict__ Wl) const { *reinterpret_cast<f32x4 *>(Wl + loff0) = v; }
 };
 
-// One group segment of a chunk for one wave: acc[i][mi] += U[4 g + i][kk][rows mi] x B_{g,i}[kk][this lane's column]
-// (Wl: the staged weights at this wave's first row; MT = rows of the staged tile)
-template <int VT, int G, int MW>
-__device__ __forceinline__ void wino_group(const float *__restrict__ Wl, const float *__restrict__ Bl, int off, int l31, int kh,
-                                           f32x16 (&acc)[4][2]) {
-    constexpr int LDB = wino_ldb<VT, MW>(), MT = WMT * MW;
-    const float *br = Bl + kh * LDB + off + 3 * G * VT;
-    const float *wr = Wl + 4 * G * (KC * MT) + kh * MT + l31;
+// The groups of a chunk: image row of a group's first point, raw frame of its first sample (samples FS frames apart), its points
+// (= the samples it reads: a 3-point group has a zero third tap and no d3), and which sample of the group in front is this
+// group's d0 (-1: none) -- that frame is read once and kept in a register from one group to the next.
+struct WinoGroupsS1 {          // stride 1: three 3-tap groups, sample f of group g at raw frame 3 g + f; 10 distinct frames
+    static constexpr int NG = 3, FS = 1;
+    static constexpr int row0(int g) { return 4 * g; }
+    static constexpr int frame0(int g) { return 3 * g; }
+    static constexpr int np(int) { return 4; }
+    static constexpr int carry(int g) { return g > 0 ? 3 : -1; }
+};
+struct WinoGroupsS2 {          // stride 2: E0, E1, O0, O1 (form B of the header comment); 11 distinct frames
+    static constexpr int NG = 4, FS = 2;
+    static constexpr int row0(int g) { return g == 0 ? 0 : 3 * g + 1; }
+    static constexpr int frame0(int g) { return g == 0 ? 0 : g == 1 ? 6 : g == 2 ? 1 : 5; }
+    static constexpr int np(int g) { return g == 0 ? 4 : 3; }
+    static constexpr int carry(int g) { return g == 1 ? 3 : g == 3 ? 2 : -1; }
+};
+
+template <int G>
+using group_c = std::integral_constant<int, G>;
+
+// One chunk for one wave, all groups: acc[i][mi] += U[row0(g) + i][kk][rows mi] x B_{g,i}[kk][this lane's column], groups in
+// ascending order, K steps s = 0 .. KC / 2 - 1 inside a group, points inside a step -- the order per accumulator element that
+// both workgroup shapes share.  (Wl: the staged weights at this wave's first row; MT = rows of the staged tile.)
+// Operands run ahead in registers: the A fragments AD MFMA pairs ahead of their own pair (1 <= AD <= 3; pairs counted through
+// the steps of the chunk), the raw samples of step (g, s) + 1 from the middle of step (g, s), across the group boundary too --
+// between(group_c<g + 1>) (the loads of the next chunk that go in front of group g + 1, between s_setprio 0 / 1) is called
+// behind the last MFMA of group g with the first operands of group g + 1 already on their way.  Only the chunk's first pairs
+// wait for LDS.  CARRY: a frame that two neighbouring groups share is read once (10 instead of 12 reads per K step at stride
+// 1, 11 instead of 13 at stride 2) at the price of KC / 2 registers across the group boundary.
+template <class GR, int VT, int LDB, int MT, int AD, bool CARRY, class Between>
+__device__ __forceinline__ void wino_chunk(const float *__restrict__ Wl, const float *__restrict__ Bl, int off, int l31, int kh,
+                                           f32x16 (&acc)[4][2], Between between) {
+    static_assert(AD >= 1 && AD <= 3, "a pair's fragment is read inside its own step or the one in front");
+    constexpr int NS = KC / 2, NSTEP = GR::NG * NS;
+    const float *br = Bl + kh * LDB + off;
+    const float *wr = Wl + kh * MT + l31;
+    float d[NSTEP][4], a[NSTEP][4][2], keep[NS];       // every index is a constant once unrolled: registers, live only briefly
+    auto read_d = [&](int t) {
+        const int g = t / NS, s = t % NS;
+        const float *p = br + 2 * s * LDB + GR::frame0(g) * VT;
 #pragma unroll
-    for (int s = 0; s < KC / 2; ++s) {
-        const float d0 = br[2 * s * LDB], d1 = br[2 * s * LDB + VT], d2 = br[2 * s * LDB + 2 * VT], d3 = br[2 * s * LDB + 3 * VT];
-        const float b[4] = {d0 - d2, d1 + d2, d2 - d1, d1 - d3};
+        for (int f = 0; f < 4; ++f)
+            d[t][f] = CARRY && f == 0 && GR::carry(g) >= 0 ? keep[s] : f < GR::np(g) ? p[f * GR::FS * VT] : 0.f;
+        if (CARRY && g + 1 < GR::NG && GR::carry(g + 1) >= 0) keep[s] = d[t][GR::carry(g + 1)];
+    };
+    // the A pair that stands j pairs behind pair 0 of step t (in its own step or the next one)
+    auto read_a = [&](int t, int j) {
+        const int n = GR::np(t / NS), tt = j < n ? t : t + 1, i = j < n ? j : j - n;
+        if (tt < NSTEP) {
+            const float *p = wr + (GR::row0(tt / NS) + i) * (KC * MT) + 2 * (tt % NS) * MT;
+            a[tt][i][0] = p[0];
+            a[tt][i][1] = p[32];
+        }
+    };
+    read_d(0);
+#pragma unroll
+    for (int j = 0; j < AD; ++j) read_a(0, j);
+#pragma unroll
+    for (int t = 0; t < NSTEP; ++t) {
+        const int g = t / NS;
+        // A step is a scheduling region of its own, its order pinned (left to itself the scheduler sinks every read back in
+        // front of its MFMA pair, and hoists the next step's transform up to the reads it then waits for): the transform of
+        // samples read half a step ago; behind each MFMA pair one ds_read2 for the pair AD further on, behind the second pair
+        // also the next step's samples (one or two instructions).  The chunk's first reads stand in front of its first step.
+        if (t > 0) __builtin_amdgcn_sched_barrier(0);
+        const float b[4] = {d[t][0] - d[t][2], d[t][1] + d[t][2], d[t][2] - d[t][1], d[t][1] - d[t][3]};
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const float a0 = wr[i * (KC * MT) + 2 * s * MT], a1 = wr[i * (KC * MT) + 2 * s * MT + 32];
-            acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b[i], acc[i][0], 0, 0, 0);
-            acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b[i], acc[i][1], 0, 0, 0);
+            if (i < GR::np(g)) {
+                acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t][i][0], b[i], acc[i][0], 0, 0, 0);
+                acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t][i][1], b[i], acc[i][1], 0, 0, 0);
+                read_a(t, i + AD);
+                if (i == 1 && t + 1 < NSTEP) read_d(t + 1);
+            }
         }
+        if (t == 0) __builtin_amdgcn_sched_group_barrier(0x100, AD + 2, 0);
+#pragma unroll
+        for (int i = 0; i < GR::np(g); ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+            if (i == 1) __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
+            else __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+        }
+        if (t + 1 < NSTEP && (t + 1) % NS == 0) {
+            if (g == 0) between(group_c<1>{});
+            else if (g == 1) between(group_c<2>{});
+            else if constexpr (GR::NG > 3) between(group_c<3>{});
+        }
+    }
+}
+
+// One chunk of a 1 x 1 conv residual for one wave: per K step two samples d0, d1 of the lane's column (FS frames apart) and one
+// A pair; SIGN-transformed into two accumulator sets (below).  Operands one step ahead, as in wino_chunk.
+template <int VT, int LDB, int MT, int FS, class Products>
+__device__ __forceinline__ void wino_res_steps(const float *__restrict__ Wl, const float *__restrict__ Bl, int off, int l31, int kh,
+                                               Products products) {
+    constexpr int NS = KC / 2;
+    const float *br = Bl + kh * LDB + off;
+    const float *wr = Wl + kh * MT + l31;
+    float d[2][2], a[2][2];
+    auto read = [&](int s, float (&dd)[2], float (&aa)[2]) {
+        dd[0] = br[2 * s * LDB];
+        dd[1] = br[2 * s * LDB + FS * VT];
+        aa[0] = wr[2 * s * MT];
+        aa[1] = wr[2 * s * MT + 32];
+    };
+    read(0, d[0], a[0]);
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        if (s + 1 < NS) read(s + 1, d[(s + 1) & 1], a[(s + 1) & 1]);
+        products(a[s & 1][0], a[s & 1][1], d[s & 1][0], d[s & 1][1]);
     }
 }
 
@@ -181,18 +276,13 @@ __device__ __forceinline__ void wino_group(const float *__restrict__ Wl, const f
 template <int VT, int MW>
 __device__ __forceinline__ void wino_valid_res_chunk(const float *__restrict__ Wl, const float *__restrict__ Bl, int off, int l31,
                                                      int kh, f32x16 (&acc)[4][2]) {
-    constexpr int LDB = wino_ldb<VT, MW>(), MT = WMT * MW;
-    const float *br = Bl + kh * LDB + off;
-    const float *wr = Wl + kh * MT + l31;
-#pragma unroll
-    for (int s = 0; s < KC / 2; ++s) {
-        const float d0 = br[2 * s * LDB], nd1 = -br[2 * s * LDB + VT];
-        const float a0 = wr[2 * s * MT], a1 = wr[2 * s * MT + 32];
+    wino_res_steps<VT, wino_ldb<VT, MW>(), WMT * MW, 1>(Wl, Bl, off, l31, kh, [&](float a0, float a1, float d0, float d1) {
+        const float nd1 = -d1;
         acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, d0, acc[0][0], 0, 0, 0);
         acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, d0, acc[0][1], 0, 0, 0);
         acc[3][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, nd1, acc[3][0], 0, 0, 0);
         acc[3][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, nd1, acc[3][1], 0, 0, 0);
-    }
+    });
 }
 
 // ---- epilogue: output transform, + bias (+ identity residual, RES), ReLU.  C/D map: column = lane & 31 (this lane's pair column),
@@ -261,6 +351,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void tcn_stage_wino_kernel(const TcnPa
     static_assert(!RESCONV || (VALID && !RES), "the conv-residual phase is built for the valid form");
     constexpr int LDB = wino_ldb<VT, MW>(), MT = WMT * MW, NT = WNT / MW;
     constexpr int NJ = (LDB + 63) / 64;
+    constexpr int AD = 2;                  // wino_chunk: A fragments two MFMA pairs ahead (three would spill in the tall shape)
+    constexpr bool CARRY = true;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *Wl = smem;
     float *Bl = smem + WTAPS * KC * MT;
@@ -311,26 +403,19 @@ __global__ __launch_bounds__(NTHREADS, 2) void tcn_stage_wino_kernel(const TcnPa
                 ws.template issue_part<0>(wnext);
                 bx.template issue_third<0>(seg_base, p.C, cs, cn, wave);
                 __builtin_amdgcn_s_setprio(1);
-                wino_group<VT, 0, MW>(Ww, Bl, off, l31, kh, acc);
-                __builtin_amdgcn_s_setprio(0);
-                ws.template issue_part<1>(wnext);
-                bx.template issue_third<1>(seg_base, p.C, cs, cn, wave);
-                __builtin_amdgcn_s_setprio(1);
-                wino_group<VT, 1, MW>(Ww, Bl, off, l31, kh, acc);
-                __builtin_amdgcn_s_setprio(0);
-                ws.template issue_part<2>(wnext);
-                bx.template issue_third<2>(seg_base, p.C, cs, cn, wave);
-                __builtin_amdgcn_s_setprio(1);
-                wino_group<VT, 2, MW>(Ww, Bl, off, l31, kh, acc);
+                wino_chunk<WinoGroupsS1, VT, LDB, MT, AD, CARRY>(Ww, Bl, off, l31, kh, acc, [&](auto g) {
+                    __builtin_amdgcn_s_setprio(0);
+                    ws.template issue_part<g()>(wnext);
+                    bx.template issue_third<g()>(seg_base, p.C, cs, cn, wave);
+                    __builtin_amdgcn_s_setprio(1);
+                });
                 __builtin_amdgcn_s_setprio(0);
             }
             __syncthreads();                         // peeled last chunk
             ws.commit(Wl);
             bx.commit(Bl, LDB, wave);
             __syncthreads();
-            wino_group<VT, 0, MW>(Ww, Bl, off, l31, kh, acc);
-            wino_group<VT, 1, MW>(Ww, Bl, off, l31, kh, acc);
-            wino_group<VT, 2, MW>(Ww, Bl, off, l31, kh, acc);
+            wino_chunk<WinoGroupsS1, VT, LDB, MT, AD, CARRY>(Ww, Bl, off, l31, kh, acc, [](auto) {});
         };
         // tiles whose staged span lies inside the sequence: 16-byte staging; the others (zero padding at either end) element-wise
         const bool interior = fa >= 0 && fa * VT + 4 * ((span + 3) / 4) <= TV;     // uniform
@@ -483,45 +568,17 @@ struct BStage4Tail {
     }
 };
 
-// One group segment of a chunk for one wave: image rows ROW0 .. ROW0 + NP - 1, phase samples d_i at raw frame F + 2 i of the
-// lane's column; NP = 3: the group's third tap is zero -- no point-inf product, d3 not read
-template <int VT, int ROW0, int F, int NP, int MW>
-__device__ __forceinline__ void wino2_group(const float *__restrict__ Wl, const float *__restrict__ Bl, int off, int l31, int kh,
-                                            f32x16 (&acc)[4][2]) {
-    constexpr int LDB = wino2_ldb<VT, MW>(), MT = WMT * MW;
-    const float *br = Bl + kh * LDB + off + F * VT;
-    const float *wr = Wl + ROW0 * (KC * MT) + kh * MT + l31;
-#pragma unroll
-    for (int s = 0; s < KC / 2; ++s) {
-        const float d0 = br[2 * s * LDB], d1 = br[2 * s * LDB + 2 * VT], d2 = br[2 * s * LDB + 4 * VT];
-        const float d3 = NP == 4 ? br[2 * s * LDB + 6 * VT] : 0.f;
-        const float b[4] = {d0 - d2, d1 + d2, d2 - d1, d1 - d3};
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            const float a0 = wr[i * (KC * MT) + 2 * s * MT], a1 = wr[i * (KC * MT) + 2 * s * MT + 32];
-            acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b[i], acc[i][0], 0, 0, 0);
-            acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b[i], acc[i][1], 0, 0, 0);
-        }
-    }
-}
-
 // One residual chunk: the staged row starts at raw frame 4 ja of x; d0 = x[4 j], d1 = x[4 j + 2]
 template <int VT, int MW>
 __device__ __forceinline__ void wino2_res_chunk(const float *__restrict__ Wl, const float *__restrict__ Bl, int off, int l31, int kh,
                                                 f32x16 (&acc)[4][2]) {
-    constexpr int LDB = wino2_ldb<VT, MW>(), MT = WMT * MW;
-    const float *br = Bl + kh * LDB + off;
-    const float *wr = Wl + kh * MT + l31;
-#pragma unroll
-    for (int s = 0; s < KC / 2; ++s) {
-        const float d0 = br[2 * s * LDB], d1 = br[2 * s * LDB + 2 * VT];
-        const float a0 = wr[2 * s * MT], a1 = wr[2 * s * MT + 32];
+    wino_res_steps<VT, wino2_ldb<VT, MW>(), WMT * MW, 2>(Wl, Bl, off, l31, kh, [&](float a0, float a1, float d0, float d1) {
         const float b0 = d0 - d1;
         acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
         acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[0][1], 0, 0, 0);
         acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, d1, acc[1][0], 0, 0, 0);
         acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, d1, acc[1][1], 0, 0, 0);
-    }
+    });
 }
 
 }  // namespace
@@ -532,6 +589,8 @@ template <int VT, bool RESCONV, int MW = 1>
 __global__ __launch_bounds__(NTHREADS, 2) void tcn_stage_wino_s2_kernel(const TcnParams p) {
     constexpr int LDB = wino2_ldb<VT, MW>(), MT = WMT * MW, NT = WNT / MW;
     constexpr int NJ = (LDB + 63) / 64;
+    constexpr int AD = 2;                  // wino_chunk: A fragments two MFMA pairs ahead (three would spill in the tall shape)
+    constexpr bool CARRY = true;
     constexpr int NJR = ((4 * ((NT + VT - 2) / VT) + 3) * VT + 63) / 64;      // residual rows: raw frames 4 ja .. 4 jb + 2
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *Wl = smem;
@@ -582,31 +641,19 @@ __global__ __launch_bounds__(NTHREADS, 2) void tcn_stage_wino_s2_kernel(const Tc
                 ws.template issue_part<0>(wnext);
                 bx.template issue_third<0>(seg_base, p.C, cs, cn, wave);
                 __builtin_amdgcn_s_setprio(1);
-                wino2_group<VT, 0, 0, 4, MW>(Ww, Bl, off, l31, kh, acc);
-                __builtin_amdgcn_s_setprio(0);
-                ws.template issue_part<1>(wnext);
-                bx.template issue_third<1>(seg_base, p.C, cs, cn, wave);
-                __builtin_amdgcn_s_setprio(1);
-                wino2_group<VT, 4, 6, 3, MW>(Ww, Bl, off, l31, kh, acc);
-                __builtin_amdgcn_s_setprio(0);
-                ws.template issue_part<2>(wnext);
-                bx.template issue_third<2>(seg_base, p.C, cs, cn, wave);
-                __builtin_amdgcn_s_setprio(1);
-                wino2_group<VT, 7, 1, 3, MW>(Ww, Bl, off, l31, kh, acc);
-                __builtin_amdgcn_s_setprio(0);
-                ws.template issue_part<3>(wnext);
-                __builtin_amdgcn_s_setprio(1);
-                wino2_group<VT, 10, 5, 3, MW>(Ww, Bl, off, l31, kh, acc);
+                wino_chunk<WinoGroupsS2, VT, LDB, MT, AD, CARRY>(Ww, Bl, off, l31, kh, acc, [&](auto g) {
+                    __builtin_amdgcn_s_setprio(0);
+                    ws.template issue_part<g()>(wnext);
+                    if constexpr (g() < 3) bx.template issue_third<g()>(seg_base, p.C, cs, cn, wave);
+                    __builtin_amdgcn_s_setprio(1);
+                });
                 __builtin_amdgcn_s_setprio(0);
             }
             __syncthreads();                         // peeled last chunk
             ws.commit(Wl);
             bx.commit(Bl, LDB, wave);
             __syncthreads();
-            wino2_group<VT, 0, 0, 4, MW>(Ww, Bl, off, l31, kh, acc);
-            wino2_group<VT, 4, 6, 3, MW>(Ww, Bl, off, l31, kh, acc);
-            wino2_group<VT, 7, 1, 3, MW>(Ww, Bl, off, l31, kh, acc);
-            wino2_group<VT, 10, 5, 3, MW>(Ww, Bl, off, l31, kh, acc);
+            wino_chunk<WinoGroupsS2, VT, LDB, MT, AD, CARRY>(Ww, Bl, off, l31, kh, acc, [](auto) {});
         };
         // tiles whose staged span lies inside the sequence: 16-byte staging; the others (zero padding at either end) element-wise
         const bool interior = fa >= 0 && fa * VT + 4 * ((span + 3) / 4) <= TVin;   // uniform
