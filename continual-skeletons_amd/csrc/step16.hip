@@ -243,7 +243,9 @@ __device__ __forceinline__ void gcn16_tile(const GcnParams &p, const int mt, con
 #pragma unroll
     for (int n = 0; n < NC; ++n) {
         const int col = c0 + n;
-        const int f = col / NPG, pos = min(col - f * NPG, nval - 1);
+        // (a tile of the fused stack that lies wholly in the padding between frames * V and the row's end has nval <= 0: it
+        // aggregates position 0 of its staged -- in-row -- quad and stores nothing)
+        const int f = col / NPG, pos = min(col - f * NPG, max(nval, 1) - 1);
         const int t = div_magic(pos, p.vmagic), w = pos - t * V, sb = f * NPG + t * V;
         ioff[n] = xt_off(sb + w);
 #pragma unroll
@@ -486,26 +488,39 @@ int csk_launch_gcn16(GcnParams p, int n_seg, void *stream) {
 }
 
 // ---- stack of 64-channel blocks ------------------------------------------------------------------------------------------
-// -2: not a shape the fused stack is built for (the caller issues the per-stage launches).  The blocks have passed check_co_block.
-int csk_launch_co_stack16(int n_blocks, const csk_co_block_args *b, int n_skel, int V, int64_t P, void *stream) {
-    if (n_blocks < 1 || n_blocks > CSK_CO_STACK_MAX || P < 8 || (P & 3)) return -2;
-    const int64_t Q = (int64_t)n_skel * V;
+// The instantiation co_stack16_kernel<NB> that carries blocks b[0 .. n_blocks - 1] (which have passed check_co_block) in ONE
+// launch, as NB (25 or 18; the grid is ceil(P / (4 NB)) workgroups), 0: not a shape the fused stack is built for.  Reads the
+// scalar fields of the blocks only.  The ONE copy of the rule: the launcher below switches on it, csk_co_stack_step_f32_route
+// reports it.
+int csk_co_stack16_tile(int n_blocks, const csk_co_block_args *b, int V, int64_t P) {
+    if (n_blocks < 1 || n_blocks > CSK_CO_STACK_MAX || P < 8 || (P & 3)) return 0;
     const int best_nb = pick_nb([&](int nb) { return (P + 4 * nb - 1) / (4 * nb); },
                                 [&](int nb) { return (4 * nb) % V == 0; });                     // tiles hold whole skeletons
+    if (!best_nb) return 0;
+    for (int i = 0; i < n_blocks; ++i) {
+        const csk_co_block_args &a = b[i];
+        // (c_out a multiple of CSK_CPAD: the stack's temporal step is the instantiation without padding rows)
+        if (a.c_out > 64 || (a.c_out % CSK_CPAD) || a.ell_cnt[0] > 1 || a.ell_cnt[1] > 1 || a.ell_cnt[2] > 4) return 0;
+        // a conv gcn_residual (c_in != c_out: the first block of a network) has a fourth operand subset and with it the register
+        // budget of a kernel of its own: such a block runs as its two launches
+        if (a.gcn_res_mode != CSK_RES_IDENTITY) return 0;
+        if ((int64_t)a.xin_slots * a.c_in * P * 4 >= (1ll << 32) || (int64_t)a.y_slots * a.c_out * P * 4 >= (1ll << 32) ||
+            (int64_t)a.out_slots * a.c_out * P * 4 >= (1ll << 32))
+            return 0;
+    }
+    return best_nb;
+}
+
+// -2: not a shape the fused stack is built for (the caller issues the per-stage launches).  The blocks have passed check_co_block.
+int csk_launch_co_stack16(int n_blocks, const csk_co_block_args *b, int n_skel, int V, int64_t P, void *stream) {
+    const int best_nb = csk_co_stack16_tile(n_blocks, b, V, P);
     if (!best_nb) return -2;
+    const int64_t Q = (int64_t)n_skel * V;
     const int NP = 16 * best_nb / 4;
     CoStackParams sp;
     sp.nblk = n_blocks;
     for (int i = 0; i < n_blocks; ++i) {
         const csk_co_block_args &a = b[i];
-        // (c_out a multiple of CSK_CPAD: the stack's temporal step is the instantiation without padding rows)
-        if (a.c_out > 64 || (a.c_out % CSK_CPAD) || a.ell_cnt[0] > 1 || a.ell_cnt[1] > 1 || a.ell_cnt[2] > 4) return -2;
-        // a conv gcn_residual (c_in != c_out: the first block of a network) has a fourth operand subset and with it the register
-        // budget of a kernel of its own: such a block runs as its two launches
-        if (a.gcn_res_mode != CSK_RES_IDENTITY) return -2;
-        if ((int64_t)a.xin_slots * a.c_in * P * 4 >= (1ll << 32) || (int64_t)a.y_slots * a.c_out * P * 4 >= (1ll << 32) ||
-            (int64_t)a.out_slots * a.c_out * P * 4 >= (1ll << 32))
-            return -2;
         // what co_block_cycle hands the two stage entries, but ring slots for slot runs and (no residual) the input ring as xres
         GcnParams &g = sp.b[i].g;
         g = gcn_params(a.xin, a.y_ring, a.gcn_w, a.gcn_bias, a.ell_src, a.ell_val, a.ell_cnt, a.ell_w, 0, a.c_in, a.c_out, n_skel, V,
@@ -588,7 +603,9 @@ extern "C" int csk_co_block_step_f32(const float *xin, int xin_slots, int xin_sl
     return csk_co_stack_step_f32(1, &a, n_skel, V, P, stream);      // one block: its checks, then co_block_cycle
 }
 
-extern "C" int csk_co_stack_step_f32(int n_blocks, const csk_co_block_args *b, int n_skel, int V, int64_t P, void *stream) {
+// The chain and every block of a csk_co_stack_step_f32 call, refused or accepted in one place for the entry and for the route
+// query: -1 with the message set, or 0.  Nothing is dereferenced but the array of blocks.
+static int check_co_stack(int n_blocks, const csk_co_block_args *b, int n_skel, int V, int64_t P) {
     if (!b || n_blocks < 1 || n_blocks > CSK_CO_STACK_MAX) CSK_FAIL("co_stack_step: 1..%d blocks expected", CSK_CO_STACK_MAX);
     for (int i = 0; i + 1 < n_blocks; ++i)
         if (b[i + 1].xin != b[i].out || b[i + 1].xin_slots != b[i].out_slots || b[i + 1].xin_slot0 != b[i].out_slot0 ||
@@ -596,11 +613,33 @@ extern "C" int csk_co_stack_step_f32(int n_blocks, const csk_co_block_args *b, i
             CSK_FAIL("co_stack_step: block %d does not read what block %d emits (ring, slot count, first slot, channels)", i + 1, i);
     for (int i = 0; i < n_blocks; ++i)
         if (const int rc = check_co_block(b[i], n_skel, V, P)) return rc;
+    return 0;
+}
+
+extern "C" int csk_co_stack_step_f32(int n_blocks, const csk_co_block_args *b, int n_skel, int V, int64_t P, void *stream) {
+    if (const int rc = check_co_stack(n_blocks, b, n_skel, V, P)) return rc;
     if (n_blocks > 1) {
         const int rc = csk_launch_co_stack16(n_blocks, b, n_skel, V, P, stream);
         if (rc != -2) return rc;
     }
     for (int i = 0; i < n_blocks; ++i)
         if (const int rc = co_block_cycle(b[i], n_skel, V, P, stream)) return rc;
+    return 0;
+}
+
+// What the call above launches (include/cskel.h), from the function its launcher switches on.  Host arithmetic only.
+extern "C" int csk_co_stack_step_f32_route(int n_blocks, const csk_co_block_args *b, int n_skel, int V, int64_t P, int32_t *route) {
+    if (!route) CSK_FAIL("co_stack_step_route: null route");
+    if (const int rc = check_co_stack(n_blocks, b, n_skel, V, P)) return rc;
+    const int whole = csk_co_stack16_tile(n_blocks, b, V, P);
+    int nb = whole;
+    for (int i = 0; i < CSK_CO_STACK_MAX; ++i) {
+        const int own = i < n_blocks && !whole ? csk_co_stack16_tile(1, b + i, V, P) : 0;
+        route[3 + i] = i < n_blocks ? (whole || own ? 1 : 0) : -1;
+        if (own) nb = own;
+    }
+    route[0] = whole ? 1 : 0;
+    route[1] = nb;
+    route[2] = nb ? (int32_t)((P + 4 * nb - 1) / (4 * nb)) : 0;
     return 0;
 }

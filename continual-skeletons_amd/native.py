@@ -45,6 +45,7 @@ SIGNATURES = {
     "csk_tcn_step_bf16x3": [_p, _i, _i, _i, _i, _p, _p, _i, _i, _i, _p, _p, _p, _i, _i, _i, _i, _l, _i, _i, _i, _i, _p],
     "csk_tcn_step_bf16x3_tile": [_i, _i, _l],
     "csk_co_stack_step_f32": [_i, _p, _i, _i, _l, _p],
+    "csk_co_stack_step_f32_route": [_i, _p, _i, _i, _l, C.POINTER(C.c_int32)],
     "csk_co_block_step_f32": [_p, _i, _i, _i, _p, _p, _p, _p, _p, _i, _i, _p, _i, _i, _p, _p, _i, _i, _p, _i, _i, _i, _i, _i, _l, _p],
     "csk_co_spatial_pool_f32": [_p, _p, _i, _i, _i, _l, _p],
     "csk_co_window_mean_f32": [_p, _p, _l, _i, _i, _i, _p],
@@ -86,6 +87,20 @@ class CoLayer(C.Structure):
                 ("y_ring", C.c_void_p), ("out_ring", C.c_void_p), ("tcn_partial", C.c_void_p),
                 ("agcn_inter", C.c_int32), ("agcn_pad_", C.c_int32), ("agcn_w_pairs", C.c_void_p), ("agcn_b_pairs", C.c_void_p),
                 ("agcn_a_sum", C.c_void_p), ("agcn_adj", C.c_void_p)]
+
+
+class CoBlockArgs(C.Structure):
+    """Mirror of ``csk_co_block_args`` (include/cskel.h)."""
+    _fields_ = [("xin", C.c_void_p), ("xin_slots", C.c_int32), ("xin_slot0", C.c_int32), ("c_in", C.c_int32),
+                ("gcn_w", C.c_void_p), ("gcn_bias", C.c_void_p), ("ell_src", C.c_void_p), ("ell_val", C.c_void_p),
+                ("ell_cnt", C.c_int32 * 3), ("ell_w", C.c_int32), ("gcn_res_mode", C.c_int32), ("y_ring", C.c_void_p),
+                ("y_slots", C.c_int32), ("y_slot0", C.c_int32), ("tcn_w", C.c_void_p), ("tcn_bias", C.c_void_p),
+                ("res_mode", C.c_int32), ("x_res_slot0", C.c_int32), ("out", C.c_void_p), ("out_slots", C.c_int32),
+                ("out_slot0", C.c_int32), ("c_out", C.c_int32)]
+
+
+CO_STACK_MAX = 4        # CSK_CO_STACK_MAX
+CO_ROUTE_WORDS = 3 + CO_STACK_MAX
 
 
 class ScrubJob(C.Structure):

@@ -28,7 +28,8 @@ extern "C" {
 #endif
 
 /* Stays 16 while entries are only added: csk_derive_modality_f32 / _frames_f32, csk_prenorm_f32 / _frames_f32,
- * csk_tcn_stage_wino_valid_f32, csk_tcn_stage_wino_valid_res_f32, csk_co_plan_set_delays, csk_gcn_stage_f32_route, csk_gcn_stage_splitk_f32_route, csk_co_prime_pack_f32, csk_co_head_clip_f32, csk_str_unit_f32_route and
+ * csk_tcn_stage_wino_valid_f32, csk_tcn_stage_wino_valid_res_f32, csk_co_plan_set_delays, csk_gcn_stage_f32_route, csk_gcn_stage_splitk_f32_route, csk_co_prime_pack_f32, csk_co_head_clip_f32, csk_str_unit_f32_route,
+ * csk_co_stack_step_f32_route and
  * csk_select_people_f32 / _frames_f32 and csk_ntu_intake_f32 are additive (no existing entry, struct
  * or constant changed). */
 #define CSK_ABI_VERSION 16
@@ -520,6 +521,20 @@ typedef struct csk_co_block_args {          /* the arguments of csk_co_block_ste
     int32_t out_slots, out_slot0, c_out;
 } csk_co_block_args;
 int csk_co_stack_step_f32(int n_blocks, const csk_co_block_args *blocks, int n_skel, int V, int64_t P, void *stream);
+
+/*
+ * What a csk_co_stack_step_f32 call (a csk_co_block_step_f32 call: n_blocks = 1) with these arguments launches -- the function the
+ * launcher switches on.  Host arithmetic only: no GPU call, and of the blocks only their scalar fields are read (the ring and
+ * operand pointers are checked as the entry checks them -- non-null, alignment, the chain -- and never dereferenced).  The same
+ * argument checks as the entry: -1 with the same message.
+ *  route[0]      1: the whole call is ONE launch of the fused stack kernel (csrc/step16.hip: co_stack16_kernel<NB>); 0: per block
+ *  route[1]      NB of the call's fused launches, 25 or 18: tiles of 4 NB positions x the four new frames (0: it has none)
+ *  route[2]      their grid, ceil(P / (4 NB)) workgroups (0: none)
+ *  route[3 + i]  block i: 1 = carried by a fused launch (the one launch if route[0], else a launch of its own), 0 = the tile
+ *                family's two stages (graph-conv launches per slot run, then the four emitting steps); -1 for i >= n_blocks
+ */
+#define CSK_CO_ROUTE_WORDS (3 + CSK_CO_STACK_MAX)
+int csk_co_stack_step_f32_route(int n_blocks, const csk_co_block_args *blocks, int n_skel, int V, int64_t P, int32_t *route);
 
 /* spatial_pool of CoModelBase (models/base.py:84) on a channel-major frame: feat[n, c] = mean of the MV = M*V
  * positions of stream n.  h (C, P); feat (N, C). */
