@@ -347,6 +347,16 @@ class TemporalConvolution(_Folded):
         return tcn_stage(x, ops["w"], ops["bias"], ops["c_out"], ops["k"], self.stride, self.padding, relu=False)
 
 
+# The Winograd entries behind tcn_stage's image keywords, in the keywords' order of precedence: (keyword, entry, rows of the image
+# by stride -- None: not checked --, -2 falls through to the next keyword and in the end to the direct entry)
+_WINO_ENTRIES = (
+    ("w_wino_valid_res", "csk_tcn_stage_wino_valid_res_f32", {1: 12}, True),
+    ("w_wino_valid", "csk_tcn_stage_wino_valid_f32", {1: 12}, False),
+    ("w_wino_ext", "csk_tcn_stage_wino_ext_f32", {1: 12, 2: 13}, False),
+    ("w_wino", "csk_tcn_stage_wino_f32", None, False),
+)
+
+
 def tcn_stage(y, w, bias, c_out, k, stride, pad, relu=True, res_mode=0, x_res=None, w_res=None, res_off=0, out=None,
               split=False, ksplit=1, scratch=None, w_wino=None, w_wino_ext=None, w_wino_valid=None, w_wino_valid_res=None):
     """csk_tcn_stage_f32, or with split=True csk_tcn_stage_bf16x3 (w / w_res are then the split operand images), or with
@@ -378,42 +388,22 @@ def tcn_stage(y, w, bias, c_out, k, stride, pad, relu=True, res_mode=0, x_res=No
             native.stream_of(y))
         native.check(rc, "csk_tcn_stage_splitk_f32")
         return out
-    if w_wino_valid_res is not None and not split:
-        if w_wino_valid_res.dim() != 3 or w_wino_valid_res.shape[0] != 12 or tuple(w_wino_valid_res.shape[1:]) != tuple(w.shape[1:]):
-            raise RuntimeError(f"tcn_stage: w_wino_valid_res must be the [12][c_pad][c_out_pad] image of the conv, got {tuple(w_wino_valid_res.shape)}")
-        rc = native.lib().csk_tcn_stage_wino_valid_res_f32(
-            native.ptr(y), native.ptr(x_res), native.ptr(w_res), native.ptr(bias), native.ptr(out),
-            n, c, c_out, t_in, v, k, stride, pad, res_mode, c_res, t_res, res_off, int(relu), native.ptr(w_wino_valid_res),
-            native.stream_of(y))
-        if rc != -2:
-            native.check(rc, "csk_tcn_stage_wino_valid_res_f32")
-            return out
-    if w_wino_valid is not None and not split:
-        if w_wino_valid.dim() != 3 or w_wino_valid.shape[0] != 12 or tuple(w_wino_valid.shape[1:]) != tuple(w.shape[1:]):
-            raise RuntimeError(f"tcn_stage: w_wino_valid must be the [12][c_pad][c_out_pad] image of the conv, got {tuple(w_wino_valid.shape)}")
-        rc = native.lib().csk_tcn_stage_wino_valid_f32(
-            native.ptr(y), native.ptr(w), native.ptr(x_res), native.ptr(w_res), native.ptr(bias), native.ptr(out),
-            n, c, c_out, t_in, v, k, stride, pad, res_mode, c_res, t_res, res_off, int(relu), native.ptr(w_wino_valid),
-            native.stream_of(y))
-        native.check(rc, "csk_tcn_stage_wino_valid_f32")
-        return out
-    if w_wino_ext is not None and not split:
-        rows = 13 if stride == 2 else 12                       # the entry is not told the image's size
-        if w_wino_ext.dim() != 3 or w_wino_ext.shape[0] != rows or tuple(w_wino_ext.shape[1:]) != tuple(w.shape[1:]):
-            raise RuntimeError(f"tcn_stage: w_wino_ext must be the [{rows}][c_pad][c_out_pad] image of a stride-{stride} conv, "
-                               f"got {tuple(w_wino_ext.shape)}")
-        rc = native.lib().csk_tcn_stage_wino_ext_f32(
-            native.ptr(y), native.ptr(w), native.ptr(x_res), native.ptr(w_res), native.ptr(bias), native.ptr(out),
-            n, c, c_out, t_in, v, k, stride, pad, res_mode, c_res, t_res, res_off, int(relu), native.ptr(w_wino_ext),
-            native.stream_of(y))
-        native.check(rc, "csk_tcn_stage_wino_ext_f32")
-        return out
-    if w_wino is not None and not split:
-        rc = native.lib().csk_tcn_stage_wino_f32(
-            native.ptr(y), native.ptr(w), native.ptr(x_res), native.ptr(w_res), native.ptr(bias), native.ptr(out),
-            n, c, c_out, t_in, v, k, stride, pad, res_mode, c_res, t_res, res_off, int(relu), native.ptr(w_wino),
-            native.stream_of(y))
-        native.check(rc, "csk_tcn_stage_wino_f32")
+    for img, (kw, entry, rows, falls_through) in zip((w_wino_valid_res, w_wino_valid, w_wino_ext, w_wino), _WINO_ENTRIES):
+        if img is None or split:
+            continue
+        if rows is not None:                                   # the entries are not told the image's size
+            rows = rows.get(stride, 12)
+            if img.dim() != 3 or img.shape[0] != rows or tuple(img.shape[1:]) != tuple(w.shape[1:]):
+                what = f"a stride-{stride} conv" if kw == "w_wino_ext" else "the conv"
+                raise RuntimeError(f"tcn_stage: {kw} must be the [{rows}][c_pad][c_out_pad] image of {what}, got {tuple(img.shape)}")
+        # the entry that does not fall back itself takes no direct image
+        direct = () if falls_through else (native.ptr(w),)
+        rc = getattr(native.lib(), entry)(
+            native.ptr(y), *direct, native.ptr(x_res), native.ptr(w_res), native.ptr(bias), native.ptr(out),
+            n, c, c_out, t_in, v, k, stride, pad, res_mode, c_res, t_res, res_off, int(relu), native.ptr(img), native.stream_of(y))
+        if rc == -2 and falls_through:
+            continue
+        native.check(rc, entry)
         return out
     fn = native.lib().csk_tcn_stage_bf16x3 if split else native.lib().csk_tcn_stage_f32
     rc = fn(native.ptr(y), native.ptr(w), native.ptr(x_res), native.ptr(w_res), native.ptr(bias), native.ptr(out),
@@ -546,7 +536,7 @@ def _forward_few_channels(self, x, out=None):
     if out is None:
         out = torch.empty((n, t["c_out"], tt, v), device=x.device, dtype=torch.float32)
     rc = native.lib().csk_block_few_channels_f32(
-        native.ptr(x.contiguous()), native.ptr(g["w"]), native.ptr(g["bias"]), native.ptr(g["ell_src"]), native.ptr(g["ell_val"]),
+        native.ptr(x), native.ptr(g["w"]), native.ptr(g["bias"]), native.ptr(g["ell_src"]), native.ptr(g["ell_val"]),
         native.ptr(g["ell_cnt_host"]), g["ell_w"], native.ptr(t["w"]), native.ptr(t["bias"]), native.ptr(out), n, c, g["c_out"],
         t["c_out"], tt, v, self.tcn.padding, native.stream_of(x))
     native.check(rc, "csk_block_few_channels_f32")

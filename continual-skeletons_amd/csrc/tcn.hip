@@ -338,47 +338,33 @@ __global__ __launch_bounds__(256) void tcn_reduce_kernel(const TcnParams p) {
     }
 }
 
-static int tcn_stage_impl(const float *y, const float *w, const float *x_res, const float *w_res,
-                          const float *bias, float *out, int n_seg, int c, int c_out, int t_in, int V, int k,
-                          int stride, int pad, int res_mode, int c_res, int t_res, int res_off, int relu, int ksplit,
-                          float *partial, void *stream) {
-    if (!y || !w || !bias || !out) CSK_FAIL("tcn_stage: null pointer");
-    if (n_seg <= 0 || c <= 0 || c_out <= 0 || t_in <= 0 || V < 2 || V > 64) CSK_FAIL("tcn_stage: bad dims");
-    if (k < 1 || k > 9 || stride < 1 || pad < 0 || pad >= k) CSK_FAIL("tcn_stage: bad k/stride/pad (k <= 9)");
-    if (t_in + 2 * pad < k) CSK_FAIL("tcn_stage: t_in too short for kernel");
-    const int t_out = (t_in + 2 * pad - k) / stride + 1;
-    if (res_mode != CSK_RES_NONE) {
-        if (!x_res) CSK_FAIL("tcn_stage: residual requested without x_res");
-        if (res_mode == CSK_RES_IDENTITY && c_res != c_out) CSK_FAIL("tcn_stage: identity residual needs c_res == c_out");
-        if (res_mode == CSK_RES_CONV && !w_res) CSK_FAIL("tcn_stage: conv residual without w_res");
-        if ((t_out - 1) * stride + res_off >= t_res || res_off < 0) CSK_FAIL("tcn_stage: residual frames out of range");
+// The kernel a checked launch runs and its tile geometry, from the shape fields of p alone (host arithmetic, no operand is read):
+// the ONE copy of the rule, tcn_stage_impl switches on it (tests/tcn_direct_fixture.py::select restates it independently).
+struct TcnRoute {
+    bool tile16;          // the 16x16x4 family (tcn16.hip) takes the launch: nothing below is set
+    int MT, NJ, VT;       // tcn_stage_kernel<MT, NJ, K9, SPLIT, VT>
+    bool K9, SPLIT;
+    int nt, ldb, ldb2;    // positions per tile, LDS row strides of the conv / the conv-residual phase
+    int ksplit;           // channel ranges launched: p.ksplit, or 1 where a split request collapses to the unsplit kernel
+    size_t lds;
+};
+
+// 0, or -1 with the message set where no kernel takes the shape
+static int tcn_stage_route(const TcnParams &p, int n_seg, TcnRoute *route) {
+    TcnRoute r = {};
+    const int V = p.V, k = p.K, stride = p.stride;
+    // the 16x16x4 tile family (tcn16.hip) for the shapes it is built for; stride 1 bitwise the same sums, stride 2 in its own summation order
+    if (p.ksplit == 1 && csk_tcn_stage16_takes(p)) {
+        r.tile16 = true;
+        *route = r;
+        return 0;
     }
-    if ((int64_t)t_in * V >= (1 << 26)) CSK_FAIL("tcn_stage: T*V too large for 32-bit position arithmetic");
-    if (ksplit < 1 || ksplit > 64) CSK_FAIL("tcn_stage: ksplit must be in [1, 64]");
-    if (ksplit > 1 && (!partial || ((uintptr_t)partial & 15))) CSK_FAIL("tcn_stage: split-K needs a 16-byte aligned partial-sum buffer");
-    if (ksplit > 1 && k != 9) CSK_FAIL("tcn_stage: the split-K form is built for the 9-tap conv");
-    TcnParams p;
-    p.y = y; p.w = w; p.xres = x_res ? x_res : y; p.wres = w_res; p.bias = bias; p.out = out;
-    p.C = c; p.Cpad = round_up(c, CSK_CPAD); p.Cout = c_out; p.Mpad = round_up(c_out, CSK_MT);
-    p.Tin = t_in; p.Tout = t_out; p.V = V; p.K = k; p.stride = stride; p.pad = pad;
-    p.res_mode = res_mode; p.Cres = c_res > 0 ? c_res : 1; p.CresPad = round_up(p.Cres, CSK_CPAD);
-    p.Tres = t_res > 0 ? t_res : 1; p.res_off = res_off; p.relu = relu; p.vmagic = vmagic_of(V);
-    p.ksplit = split_ranges(p.Cpad, c, ksplit, KC, &p.cper);
-    p.part = partial;
-    // 32-bit lane byte offsets: 4 * (4 * row_stride + position) must stay below 2^32
-    p.fast_epi = (int64_t)p.Tres * V < (1ll << 27) && (int64_t)t_out * V < (1ll << 27);
     // the register staging holds <= 9 (128-row tiles) / 14 (64-row tiles) x 64 positions of an activation row -- the
     // widest spill-free instantiations; tiles whose input span (stride * frames + k taps) * V is longer than that
     // (stride 2 with V > 32, stride 3, ...) are narrowed: a tile then covers nt < NT output positions and the remaining
     // MFMA columns idle.  Never the case for the ST-GCN shapes (V <= 25, stride <= 2).  Both tile heights are priced
     // (the 64-row kernel stages 14 sweeps: at V = 64, stride 2 it keeps 128 of its 256 columns where the 128-row kernel
-    // keeps 1 of 128) and the better MFMA-column utilisation wins; a shape that loses more than half the columns either
-    // way says so once on stderr.
-    // the 16x16x4 tile family (tcn16.hip) for the shapes it is built for; stride 1 bitwise the same sums, stride 2 in its own summation order (-2: not taken)
-    if (p.ksplit == 1) {
-        const int rc = csk_launch_tcn_stage16(p, n_seg, stream);
-        if (rc != -2) return rc;
-    }
+    // keeps 1 of 128) and the better MFMA-column utilisation wins.
     auto narrow = [&](int NT_, int nj_max_, int *ldb_) {
         int nt = NT_;
         for (;;) {
@@ -392,11 +378,83 @@ static int tcn_stage_impl(const float *y, const float *w, const float *x_res, co
     int ldb64 = 0, ldb128 = 0;
     const int nt64 = narrow(256, 14, &ldb64), nt128 = big ? narrow(128, 9, &ldb128) : 0;
     if (big && nt128 < 128 && nt64 * 128 > nt128 * 256) big = false;       // utilisation nt64 / 256 > nt128 / 128
-    const int MT = big ? 128 : 64, NT = 16384 / MT;
+    r.MT = big ? 128 : 64;
     const int nj_max = big ? 9 : 14;
-    p.nt = big ? nt128 : nt64;
-    p.ldb = big ? ldb128 : ldb64;
-    if (2 * p.nt < NT) {
+    r.nt = big ? nt128 : nt64;
+    r.ldb = big ? ldb128 : ldb64;
+    const int nj = (r.ldb + 63) / 64;
+    if (nj > nj_max) CSK_FAIL("tcn_stage: activation tile of %d positions per channel exceeds the staged maximum (%d)", r.ldb, 64 * nj_max);
+    r.lds = (size_t)(k * KC * r.MT + KC * r.ldb) * sizeof(float);
+    r.ldb2 = 4;
+    bool vt_ok = true;                     // the compile-time-V instantiations stage FOUR 8-channel groups per residual chunk
+    if (p.res_mode == CSK_RES_CONV) {
+        // conv-residual phase: G 8-channel groups per chunk (CresPad is a multiple of 16: G = 2 always divides it)
+        const int max_dt = (r.nt + V - 2) / V;
+        r.ldb2 = round_up((stride * max_dt + 1) * V, 4);
+        if (r.ldb2 > r.ldb) CSK_FAIL("tcn_stage: residual tile wider than the conv tile");
+        auto lds2 = [&](int G) { return (size_t)(G * KC * r.MT + G * KC * r.ldb2) * sizeof(float); };
+        vt_ok = p.CresPad % (4 * KC) == 0 && 2 * lds2(4) <= 160 * 1024;
+        const size_t need = lds2(vt_ok && k == 9 && (V == 25 || V == 18) ? 4 : 2);
+        if (need > r.lds) r.lds = need;
+    }
+    if (r.lds > 160 * 1024) CSK_FAIL("tcn_stage: LDS tile %zu B exceeds 160 KiB", r.lds);
+    // NJ = 64-lane sweeps of the activation staging per row: the smallest instantiation that covers the span (sweeps
+    // beyond it re-load and re-commit its last position: wasted load / LDS-write slots).  128x128 tiles of the
+    // stride-1 layers need 6 sweeps, not 9: -2.7 % on their tiles.  14 sweeps (64-row tiles only) exist in the generic form alone.
+    r.NJ = nj <= 6 ? 6 : nj <= 9 ? 9 : 14;
+    // the split-K instantiations stage <= 576 positions per channel and their reduction has the segment in grid.y: a request
+    // outside that (a stride-2 64-row tile at V = 18: 702 positions; > 65 535 sequences) runs the plain kernel -- one
+    // workgroup per tile walks the whole K loop, same result up to summation order, no partial sums, no reduction launch
+    r.ksplit = p.ksplit > 1 && (nj > 9 || n_seg > 65535) ? 1 : p.ksplit;
+    r.SPLIT = r.ksplit > 1;                // (the split-K entry takes k = 9 only)
+    // the 9-tap form with straight-line 3-tap MFMA segments
+    r.K9 = k == 9 && r.NJ != 14;
+    // the two skeleton sizes of the reference's datasets (NTU-25, OpenPose-18) with V as a compile-time constant: the tap
+    // shift of an LDS read becomes an immediate offset (+0.1 ... +0.8 % per launch)
+    r.VT = !r.SPLIT && r.K9 && (V == 25 || V == 18) && vt_ok ? V : 0;
+    *route = r;
+    return 0;
+}
+
+// the instantiations that exist: <64, 14> generic only; every other (MT, NJ) generic, 9-tap, 9-tap split-K and 9-tap with V = 25 / 18
+template <int MT, int NJ>
+static auto tcn_stage_kernel_of(const TcnRoute &r) -> void (*)(TcnParams) {
+    if constexpr (NJ == 14) return tcn_stage_kernel<MT, NJ>;
+    else {
+        if (r.SPLIT) return tcn_stage_kernel<MT, NJ, true, true>;
+        if (r.VT == 25) return tcn_stage_kernel<MT, NJ, true, false, 25>;
+        if (r.VT == 18) return tcn_stage_kernel<MT, NJ, true, false, 18>;
+        return r.K9 ? tcn_stage_kernel<MT, NJ, true> : tcn_stage_kernel<MT, NJ>;
+    }
+}
+
+static int tcn_stage_impl(const float *y, const float *w, const float *x_res, const float *w_res,
+                          const float *bias, float *out, int n_seg, int c, int c_out, int t_in, int V, int k,
+                          int stride, int pad, int res_mode, int c_res, int t_res, int res_off, int relu, int ksplit,
+                          float *partial, void *stream) {
+    int t_out;
+    auto kernel_limits = [&]() {
+        if (k < 1 || k > 9 || stride < 1 || pad < 0 || pad >= k) CSK_FAIL("tcn_stage: bad k/stride/pad (k <= 9)");
+        return 0;
+    };
+    if (const int rc = tcn_stage_check("tcn_stage", y, w, x_res, w_res, bias, out, n_seg, c, c_out, t_in, V, k, stride, pad, res_mode,
+                                       c_res, t_res, res_off, kernel_limits, &t_out))
+        return rc;
+    if (ksplit < 1 || ksplit > 64) CSK_FAIL("tcn_stage: ksplit must be in [1, 64]");
+    if (ksplit > 1 && (!partial || ((uintptr_t)partial & 15))) CSK_FAIL("tcn_stage: split-K needs a 16-byte aligned partial-sum buffer");
+    if (ksplit > 1 && k != 9) CSK_FAIL("tcn_stage: the split-K form is built for the 9-tap conv");
+    TcnParams p = tcn_params(y, w, x_res ? x_res : y, w_res, bias, out, c, c_out, t_in, t_out, V, k, stride, pad, res_mode,
+                             c_res > 0 ? c_res : 1, t_res > 0 ? t_res : 1, res_off, relu);
+    p.ksplit = split_ranges(p.Cpad, c, ksplit, KC, &p.cper);
+    p.part = partial;
+    // 32-bit lane byte offsets: 4 * (4 * row_stride + position) must stay below 2^32
+    p.fast_epi = (int64_t)p.Tres * V < (1ll << 27) && (int64_t)t_out * V < (1ll << 27);
+    TcnRoute r;
+    if (const int rc = tcn_stage_route(p, n_seg, &r)) return rc;
+    if (r.tile16) return csk_launch_tcn_stage16(p, n_seg, stream);
+    const int NT = 16384 / r.MT;
+    p.nt = r.nt; p.ldb = r.ldb; p.ldb2 = r.ldb2;
+    if (2 * p.nt < NT) {      // a shape that loses more than half the columns at either tile height says so once on stderr
         static bool warned = false;
         if (!warned) {
             warned = true;
@@ -404,59 +462,24 @@ static int tcn_stage_impl(const float *y, const float *w, const float *x_res, co
                             "exceeds the staged maximum): correct, but far below the kernel's rate\n", V, stride, k, p.nt, NT);
         }
     }
-    const int nj = (p.ldb + 63) / 64;
-    if (nj > nj_max) CSK_FAIL("tcn_stage: activation tile of %d positions per channel exceeds the staged maximum (%d)", p.ldb, 64 * nj_max);
-    size_t lds = (size_t)(k * KC * MT + KC * p.ldb) * sizeof(float);
-    p.ldb2 = 4;
-    bool vt_ok = true;                     // the compile-time-V instantiations stage FOUR 8-channel groups per residual chunk
-    if (res_mode == CSK_RES_CONV) {
-        // conv-residual phase: G 8-channel groups per chunk (CresPad is a multiple of 16: G = 2 always divides it)
-        const int max_dt = (p.nt + V - 2) / V;
-        p.ldb2 = round_up((stride * max_dt + 1) * V, 4);
-        if (p.ldb2 > p.ldb) CSK_FAIL("tcn_stage: residual tile wider than the conv tile");
-        auto lds2 = [&](int G) { return (size_t)(G * KC * MT + G * KC * p.ldb2) * sizeof(float); };
-        vt_ok = p.CresPad % (4 * KC) == 0 && 2 * lds2(4) <= 160 * 1024;
-        const size_t need = lds2(vt_ok && k == 9 && (V == 25 || V == 18) ? 4 : 2);
-        if (need > lds) lds = need;
-    }
-    if (lds > 160 * 1024) CSK_FAIL("tcn_stage: LDS tile %zu B exceeds 160 KiB", lds);
     const int Q = t_out * V;
-    p.qtiles = (Q + p.nt - 1) / p.nt; p.mtiles = p.Mpad / MT;
+    p.qtiles = (Q + p.nt - 1) / p.nt; p.mtiles = p.Mpad / r.MT;
     if ((int64_t)p.qtiles * p.mtiles * n_seg * p.ksplit >= (1ll << 31)) CSK_FAIL("tcn_stage: grid too large");
-    dim3 grid(p.qtiles * p.mtiles * n_seg * p.ksplit);
-    // NJ = 64-lane sweeps of the activation staging per row: the smallest instantiation that covers the span (sweeps
-    // beyond it re-load and re-commit its last position: wasted load / LDS-write slots).  128x128 tiles of the
-    // stride-1 layers need 6 sweeps, not 9: -2.7 % on their tiles.
-    void (*kern)(TcnParams) =
-        big ? (nj <= 6 ? tcn_stage_kernel<128, 6> : tcn_stage_kernel<128, 9>)
-            : (nj <= 6 ? tcn_stage_kernel<64, 6> : nj <= 9 ? tcn_stage_kernel<64, 9> : tcn_stage_kernel<64, 14>);
-    if (k == 9)     // the 9-tap form with straight-line 3-tap MFMA segments
-        kern = big ? (nj <= 6 ? tcn_stage_kernel<128, 6, true> : tcn_stage_kernel<128, 9, true>)
-                   : (nj <= 6 ? tcn_stage_kernel<64, 6, true> : nj <= 9 ? tcn_stage_kernel<64, 9, true> : tcn_stage_kernel<64, 14>);
-    // the two skeleton sizes of the reference's datasets (NTU-25, OpenPose-18) with V as a compile-time constant: the tap
-    // shift of an LDS read becomes an immediate offset (+0.1 ... +0.8 % per launch)
-    if (k == 9 && (V == 25 || V == 18) && vt_ok && nj <= 9) {
-        if (V == 25)
-            kern = big ? (nj <= 6 ? tcn_stage_kernel<128, 6, true, false, 25> : tcn_stage_kernel<128, 9, true, false, 25>)
-                       : (nj <= 6 ? tcn_stage_kernel<64, 6, true, false, 25> : tcn_stage_kernel<64, 9, true, false, 25>);
-        else
-            kern = big ? (nj <= 6 ? tcn_stage_kernel<128, 6, true, false, 18> : tcn_stage_kernel<128, 9, true, false, 18>)
-                       : (nj <= 6 ? tcn_stage_kernel<64, 6, true, false, 18> : tcn_stage_kernel<64, 9, true, false, 18>);
-    }
-    if (p.ksplit > 1 && (nj > 9 || n_seg > 65535)) {
-        // the split-K instantiations stage <= 576 positions per channel and their reduction has the segment in grid.y: a request
-        // outside that (a stride-2 64-row tile at V = 18: 702 positions; > 65 535 sequences) runs the plain kernel -- one
-        // workgroup per tile walks the whole K loop, same result up to summation order, no partial sums, no reduction launch
+    if (r.ksplit != p.ksplit) {            // collapsed to the unsplit kernel
         p.ksplit = 1;
         p.cper = p.Cpad;
-        grid = dim3(p.qtiles * p.mtiles * n_seg);
     }
-    if (p.ksplit > 1) {
-        kern = big ? (nj <= 6 ? tcn_stage_kernel<128, 6, true, true> : tcn_stage_kernel<128, 9, true, true>)
-                   : (nj <= 6 ? tcn_stage_kernel<64, 6, true, true> : tcn_stage_kernel<64, 9, true, true>);
+    const dim3 grid(p.qtiles * p.mtiles * n_seg * p.ksplit);
+    void (*kern)(TcnParams);
+    switch (r.MT + r.NJ) {
+        case 128 + 6: kern = tcn_stage_kernel_of<128, 6>(r); break;
+        case 128 + 9: kern = tcn_stage_kernel_of<128, 9>(r); break;
+        case 64 + 6: kern = tcn_stage_kernel_of<64, 6>(r); break;
+        case 64 + 9: kern = tcn_stage_kernel_of<64, 9>(r); break;
+        default: kern = tcn_stage_kernel_of<64, 14>(r); break;
     }
-    if (const int e = csk_ensure_lds((const void *)kern, lds)) return e;
-    hipLaunchKernelGGL(kern, grid, dim3(NTHREADS), lds, (hipStream_t)stream, p);
+    if (const int e = csk_ensure_lds((const void *)kern, r.lds)) return e;
+    hipLaunchKernelGGL(kern, grid, dim3(NTHREADS), r.lds, (hipStream_t)stream, p);
     if (p.ksplit > 1) {
         if (const int e = (int)hipGetLastError()) return e;
         const int64_t work = ((int64_t)c_out * Q + 3) / 4;

@@ -518,21 +518,25 @@ int launch_stage16(TcnParams p, int n_seg, hipStream_t s) {
 // exactly where the 32-wide tiles hold 180 of 192 (A-GCN clip forward, batch 64, same process: 16.74 -> 16.53 ms; C = 128 stride 1
 // 0.893 -> 0.837 ms, C = 256 stride 1 1.756 -> 1.672, C = 256 stride 2 1.897 -> 1.879).
 // CSK_TCN16 under CSK_DIAG=1: 1 = never, 2 = every shape the kernel supports (A/B runs, parity tests of the wide layers).
-int csk_launch_tcn_stage16(TcnParams p, int n_seg, void *stream) {
+bool csk_tcn_stage16_takes(const TcnParams &p) {
     const int mode = csk_diag_int("CSK_TCN16");
-    if (mode == 1) return -2;
-    if (mode != 2 && p.V != 18 && p.C > (p.stride == 2 ? 128 : 64)) return -2;
-    if (p.K != 9 || p.ksplit != 1 || (p.V != 25 && p.V != 18) || p.stride < 1 || p.stride > 2) return -2;
-    if ((p.pad * p.V) & 3) return -2;                            // the staged window starts on a 16-byte LDS boundary
-    if (p.C % 8 != 0 || p.C < 8) return -2;                      // whole chunks of real channels (the stack's convs: 64 / 128 / 256)
-    if (p.res_mode == CSK_RES_CONV && (p.Cres % 8 != 0 || p.Cres < 8)) return -2;
-    if (p.res_mode == CSK_RES_IDENTITY && p.stride != 1) return -2;
-    if (p.res_mode == CSK_RES_CONV && ((p.res_off * p.V) & 3)) return -2;
+    if (mode == 1) return false;
+    if (mode != 2 && p.V != 18 && p.C > (p.stride == 2 ? 128 : 64)) return false;
+    if (p.K != 9 || p.ksplit != 1 || (p.V != 25 && p.V != 18) || p.stride < 1 || p.stride > 2) return false;
+    if ((p.pad * p.V) & 3) return false;                         // the staged window starts on a 16-byte LDS boundary
+    if (p.C % 8 != 0 || p.C < 8) return false;                   // whole chunks of real channels (the stack's convs: 64 / 128 / 256)
+    if (p.res_mode == CSK_RES_CONV && (p.Cres % 8 != 0 || p.Cres < 8)) return false;
+    if (p.res_mode == CSK_RES_IDENTITY && p.stride != 1) return false;
+    if (p.res_mode == CSK_RES_CONV && ((p.res_off * p.V) & 3)) return false;
     // 32-bit byte offsets inside a segment
     if ((int64_t)p.C * p.Tin * p.V * 4 >= (1ll << 31) || (int64_t)p.Cout * p.Tout * p.V * 4 >= (1ll << 31) ||
         (int64_t)p.Cres * p.Tres * p.V * 4 >= (1ll << 31))
-        return -2;
-    if (p.Tin * p.V < 8 || (p.res_mode != CSK_RES_NONE && p.Tres * p.V < 8)) return -2;
+        return false;
+    return p.Tin * p.V >= 8 && (p.res_mode == CSK_RES_NONE || p.Tres * p.V >= 8);
+}
+
+int csk_launch_tcn_stage16(TcnParams p, int n_seg, void *stream) {
+    if (!csk_tcn_stage16_takes(p)) return -2;                    // (the kernels exist for these shapes only)
     hipStream_t s = (hipStream_t)stream;
     if (p.V == 25) return p.stride == 1 ? launch_stage16<25, 1>(p, n_seg, s) : launch_stage16<25, 2>(p, n_seg, s);
     return p.stride == 1 ? launch_stage16<18, 1>(p, n_seg, s) : launch_stage16<18, 2>(p, n_seg, s);
@@ -566,10 +570,7 @@ extern "C" int csk_block_few_channels_f32(const float *x, const float *gcn_w, co
     if (ell_cnt[0] > 1 || ell_cnt[1] > 1 || ell_cnt[2] > 4 || ell_w < 1) CSK_FAIL("block_few_channels: skeleton-sparse adjacency (<= 1 / 1 / 4 entries per column)");
     if ((int64_t)c_mid * t_in * V * 4 >= (1ll << 31) || (int64_t)c_out * t_in * V * 4 >= (1ll << 31)) CSK_FAIL("block_few_channels: segment too large");
     Fused1Params f{};
-    TcnParams &p = f.t;
-    p.w = tcn_w; p.bias = tcn_bias; p.out = out;
-    p.C = c_mid; p.Cpad = round_up(c_mid, CSK_CPAD); p.Cout = c_out; p.Mpad = round_up(c_out, CSK_MT);
-    p.Tin = t_in; p.Tout = t_in; p.V = V; p.K = 9; p.stride = 1; p.pad = pad; p.relu = 1; p.res_mode = CSK_RES_NONE; p.ksplit = 1;
+    f.t = tcn_params(nullptr, tcn_w, nullptr, nullptr, tcn_bias, out, c_mid, c_out, t_in, t_in, V, 9, 1, pad, CSK_RES_NONE, 0, 0, 0, 1);
     f.x = x; f.gw = gcn_w; f.gbias = gcn_bias; f.ell_src = ell_src; f.ell_val = ell_val;
     for (int k = 0; k < 3; ++k) f.ell_cnt[k] = ell_cnt[k];
     f.ell_w = ell_w; f.Cin = c_in; f.CinPad = round_up(c_in, CSK_CPAD); f.GMpad = round_up(c_mid, CSK_MT);

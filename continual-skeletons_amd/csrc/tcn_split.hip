@@ -19,6 +19,7 @@
 // the weights of a 16-channel chunk (9 x 16 x MT x 6 B = 110 KB at MT = 128) do not fit next to it, so they are
 // staged 3 taps at a time (36.9 KB per stage, two buffers).
 #include "split_core.h"
+#include "tcn_params.h"
 
 // Stride: a stride-s temporal conv reads, for tap r, the source frames s t + r - pad: the taps of one residue class
 // rho = r mod s read ONE de-interleaved set of frames (s t' + rho - pad), in which consecutive taps are one frame apart --
@@ -180,19 +181,15 @@ extern "C" int csk_tcn_stage_bf16x3(const float *y, const void *w_split, const f
                                     const float *bias, float *out, int n_seg, int c, int c_out, int t_in, int V, int k,
                                     int stride, int pad, int res_mode, int c_res, int t_res, int res_off, int relu,
                                     void *stream) {
-    if (!y || !w_split || !bias || !out) CSK_FAIL("tcn_stage_bf16x3: null pointer");
-    if (n_seg <= 0 || c <= 0 || c_out <= 0 || t_in <= 0 || V < 2 || V > 64) CSK_FAIL("tcn_stage_bf16x3: bad dims");
-    if (k != 9) CSK_FAIL("tcn_stage_bf16x3: the split kernel is built for the 9 x 1 temporal conv (k = %d); use csk_tcn_stage_f32", k);
-    if (stride < 1 || stride > 4 || pad < 0 || pad >= k) CSK_FAIL("tcn_stage_bf16x3: bad stride/pad (stride <= 4)");
-    if (t_in + 2 * pad < k) CSK_FAIL("tcn_stage_bf16x3: t_in too short for kernel");
-    const int t_out = (t_in + 2 * pad - k) / stride + 1;
-    if (res_mode != CSK_RES_NONE) {
-        if (!x_res) CSK_FAIL("tcn_stage_bf16x3: residual requested without x_res");
-        if (res_mode == CSK_RES_IDENTITY && c_res != c_out) CSK_FAIL("tcn_stage_bf16x3: identity residual needs c_res == c_out");
-        if (res_mode == CSK_RES_CONV && !w_res_split) CSK_FAIL("tcn_stage_bf16x3: conv residual without w_res");
-        if ((t_out - 1) * stride + res_off >= t_res || res_off < 0) CSK_FAIL("tcn_stage_bf16x3: residual frames out of range");
-    }
-    if ((int64_t)t_in * V >= (1 << 26)) CSK_FAIL("tcn_stage_bf16x3: T*V too large for 32-bit position arithmetic");
+    int t_out;
+    auto kernel_limits = [&]() {
+        if (k != 9) CSK_FAIL("tcn_stage_bf16x3: the split kernel is built for the 9 x 1 temporal conv (k = %d); use csk_tcn_stage_f32", k);
+        if (stride < 1 || stride > 4 || pad < 0 || pad >= k) CSK_FAIL("tcn_stage_bf16x3: bad stride/pad (stride <= 4)");
+        return 0;
+    };
+    if (const int rc = tcn_stage_check("tcn_stage_bf16x3", y, w_split, x_res, w_res_split, bias, out, n_seg, c, c_out, t_in, V, k, stride, pad,
+                                       res_mode, c_res, t_res, res_off, kernel_limits, &t_out))
+        return rc;
     if (((uintptr_t)w_split | (uintptr_t)(w_res_split ? w_res_split : w_split)) & 15) CSK_FAIL("tcn_stage_bf16x3: packed weights must be 16-byte aligned");
     TcnSplitParams p;
     p.y = y; p.w = (const u32x4 *)w_split; p.xres = x_res ? x_res : y; p.wres = (const u32x4 *)w_res_split; p.bias = bias; p.out = out;

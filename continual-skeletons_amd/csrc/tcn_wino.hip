@@ -717,174 +717,112 @@ static int wino_pick_mw(int qp, int c_out, int stride) {
     return 16 * tall <= 15 * wide ? 2 : 1;
 }
 
-// -2: the shape is not one the Winograd kernel is built for (the caller runs the direct kernels); 0 / error code otherwise.
-// res_none: form A of csk_tcn_stage_wino_ext_f32 (no residual) instead of the identity-residual form.
-static int tcn_stage_wino_launch(const float *y, const float *w_wino, const float *x_res, const float *bias, float *out, int n_seg,
-                                 int c, int c_out, int t_in, int V, int k, int stride, int pad, int res_mode, int c_res, int t_res,
-                                 int res_off, int relu, void *stream, bool res_none = false) {
-    if (!w_wino || !y || !bias || !out) return -2;
-    if (k != 9 || stride != 1 || pad != 4) return -2;
-    if (res_none ? res_mode != CSK_RES_NONE : (res_mode != CSK_RES_IDENTITY || res_off != 0 || !x_res || c_res != c_out || t_res != t_in))
-        return -2;
-    if ((V != 25 && V != 18) || c_out % WMT != 0 || c < 1 || n_seg < 1 || t_in < 1) return -2;
-    if ((int64_t)t_in * V >= (1 << 26)) return -2;                    // 32-bit position / lane byte offsets inside a segment
-    if (csk_diag_flag("CSK_TCN_WINO") && csk_diag_int("CSK_TCN_WINO") < 2) return -2;   // diagnostic A/B switch: the direct kernels
-    const int qp = (t_in + 1) / 2 * V;
-    const int mw = wino_pick_mw(qp, c_out, stride);
-    const int qtiles = (qp + WNT / mw - 1) / (WNT / mw), mtiles = c_out / (WMT * mw);
-    if ((int64_t)qtiles * mtiles * n_seg >= (1ll << 31)) return -2;
-    TcnParams p = {};
-    p.y = y; p.w = w_wino; p.xres = res_none ? nullptr : x_res; p.wres = nullptr; p.bias = bias; p.out = out;
-    p.C = c; p.Cpad = round_up(c, CSK_CPAD); p.Cout = c_out; p.Mpad = round_up(c_out, CSK_MT);
-    p.Tin = t_in; p.Tout = t_in; p.V = V; p.K = k; p.stride = 1; p.pad = pad;
-    p.res_mode = res_mode; p.Cres = res_none ? 0 : c_res; p.CresPad = round_up(p.Cres, CSK_CPAD); p.Tres = res_none ? 0 : t_res;
-    p.res_off = 0; p.relu = relu;
-    p.vmagic = vmagic_of(V); p.mtiles = (unsigned)mtiles; p.qtiles = (unsigned)qtiles; p.nt = qp;
+// The forms of the Winograd kernels: the 9-tap conv each computes and the residuals it takes with it.  Everything else -- V, the
+// channel counts, the workgroup shape, the LDS tile, the launch -- is common to them (tcn_stage_wino_launch).
+enum WinoFormId { WINO_PADDED_IDENT, WINO_PADDED_NONE, WINO_VALID, WINO_VALID_RES, WINO_S2 };
+struct WinoForm {
+    int stride, pad, t_min;   // the conv, and the fewest input frames the form takes
+    unsigned res_modes;       // bit m: residual mode m (CSK_RES_*) is a shape of the form
+    int res_off;              // a residual is read from this frame of x_res on (t_res == t_in frames, always)
+    int none_off;             // the res_off a call WITHOUT residual must come with; -1: any, it is not read
+    int cres_unit;            // conv residual: c_res a positive multiple of this (16: whole chunks of the direct w_res image)
+};
+constexpr unsigned WR_NONE = 1u << CSK_RES_NONE, WR_IDENT = 1u << CSK_RES_IDENTITY, WR_CONV = 1u << CSK_RES_CONV;
+constexpr WinoForm WINO_FORMS[] = {
+    /* WINO_PADDED_IDENT csk_tcn_stage_wino_f32               */ {1, 4, 1, WR_IDENT, 0, -1, 0},
+    /* WINO_PADDED_NONE  csk_tcn_stage_wino_ext_f32, form A   */ {1, 4, 1, WR_NONE, 0, -1, 0},
+    /* WINO_VALID        csk_tcn_stage_wino_valid_f32         */ {1, 0, 9, WR_IDENT | WR_NONE, 4, -1, 0},
+    /* WINO_VALID_RES    csk_tcn_stage_wino_valid_res_f32     */ {1, 0, 9, WR_CONV, 4, -1, 16},
+    /* WINO_S2           csk_tcn_stage_wino_ext_f32, form B   */ {2, 4, 1, WR_CONV | WR_NONE, 0, 0, 1},
+};
+
+// the kernel of (V, MW, form, residual), its LDS row and its (group, point) products per channel: every instantiation that exists
+struct WinoKernel {
     void (*kern)(TcnParams);
-    int ldb;
-    if (mw == 2) {
-        kern = res_none ? (V == 25 ? tcn_stage_wino_kernel<25, false, 2> : tcn_stage_wino_kernel<18, false, 2>)
-                        : (V == 25 ? tcn_stage_wino_kernel<25, true, 2> : tcn_stage_wino_kernel<18, true, 2>);
-        ldb = V == 25 ? wino_ldb<25, 2>() : wino_ldb<18, 2>();
-    } else {
-        kern = res_none ? (V == 25 ? tcn_stage_wino_kernel<25, false> : tcn_stage_wino_kernel<18, false>)
-                        : (V == 25 ? tcn_stage_wino_kernel<25> : tcn_stage_wino_kernel<18>);
-        ldb = V == 25 ? wino_ldb<25>() : wino_ldb<18>();
+    int ldb, taps;
+};
+template <int VT, int MW>
+static WinoKernel wino_kernel_of(WinoFormId form, int res_mode) {
+    const bool ident = res_mode == CSK_RES_IDENTITY, conv = res_mode == CSK_RES_CONV;
+    switch (form) {
+        case WINO_PADDED_IDENT: return {tcn_stage_wino_kernel<VT, true, MW>, wino_ldb<VT, MW>(), WTAPS};
+        case WINO_PADDED_NONE: return {tcn_stage_wino_kernel<VT, false, MW>, wino_ldb<VT, MW>(), WTAPS};
+        case WINO_VALID:
+            return {ident ? tcn_stage_wino_kernel<VT, true, MW, true> : tcn_stage_wino_kernel<VT, false, MW, true>, wino_ldb<VT, MW>(), WTAPS};
+        case WINO_VALID_RES: return {tcn_stage_wino_kernel<VT, false, MW, true, true>, wino_ldb<VT, MW>(), WTAPS};
+        default: return {conv ? tcn_stage_wino_s2_kernel<VT, true, MW> : tcn_stage_wino_s2_kernel<VT, false, MW>, wino2_ldb<VT, MW>(), W2TAPS};
     }
-    p.ldb = ldb;
-    const size_t lds = (size_t)(WTAPS * KC * WMT * mw + KC * ldb) * sizeof(float);
-    if (const int e = csk_ensure_lds((const void *)kern, lds)) return e;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(qtiles * mtiles * n_seg)), dim3(NTHREADS), lds, (hipStream_t)stream, p);
-    return (int)hipGetLastError();
 }
 
-// the valid form (pad 0, centred identity residual or none) of the stride-1 kernel: csk_tcn_stage_wino_valid_f32; -2 as above.
-// The workgroup shape is picked by the valid form's own column count ((t_in - 7) / 2 pairs per sequence, not (t_in + 1) / 2).
-// res_conv: csk_tcn_stage_wino_valid_res_f32 -- the conv residual on the centred shrink and nothing else (c_res a multiple of 16:
-// whole chunks of the direct w_res image); without it a conv residual is not a shape of this launcher.
-static int tcn_stage_wino_valid_launch(const float *y, const float *w_wino, const float *x_res, const float *bias, float *out,
-                                       int n_seg, int c, int c_out, int t_in, int V, int k, int stride, int pad, int res_mode,
-                                       int c_res, int t_res, int res_off, int relu, void *stream, bool res_conv = false,
-                                       const float *w_res = nullptr) {
-    if (!w_wino || !y || !bias || !out) return -2;
-    if (k != 9 || stride != 1 || pad != 0 || t_in < 9) return -2;
-    const bool res = res_mode == CSK_RES_IDENTITY;
-    if (res_conv ? res_mode != CSK_RES_CONV : (!res && res_mode != CSK_RES_NONE)) return -2;
-    if (res && (res_off != 4 || !x_res || c_res != c_out || t_res != t_in)) return -2;
-    if (res_conv && (res_off != 4 || !x_res || !w_res || c_res < CSK_CPAD || c_res % CSK_CPAD != 0 || t_res != t_in)) return -2;
+// -2: the shape is not one the form's kernel is built for (nothing launched; the caller runs the direct kernels); 0 / error code
+// otherwise.  w_img: the form's weight image (fold.pack_conv_weight_wino, stride 2: fold.pack_conv_weight_wino_s2).  The workgroup
+// shape is picked by the form's own column count ((t_out + 1) / 2 pairs per sequence).
+static int tcn_stage_wino_launch(WinoFormId form, const float *y, const float *w_img, const float *x_res, const float *w_res,
+                                 const float *bias, float *out, int n_seg, int c, int c_out, int t_in, int V, int k, int stride, int pad,
+                                 int res_mode, int c_res, int t_res, int res_off, int relu, void *stream) {
+    const WinoForm &f = WINO_FORMS[form];
+    if (!w_img || !y || !bias || !out) return -2;
+    if (k != 9 || stride != f.stride || pad != f.pad || t_in < f.t_min) return -2;
+    if (res_mode < 0 || res_mode > CSK_RES_CONV || !((f.res_modes >> res_mode) & 1)) return -2;
+    const bool res = res_mode != CSK_RES_NONE;
+    if (res ? (res_off != f.res_off || !x_res || t_res != t_in) : (f.none_off >= 0 && res_off != f.none_off)) return -2;
+    if (res_mode == CSK_RES_IDENTITY && c_res != c_out) return -2;
+    if (res_mode == CSK_RES_CONV && (!w_res || c_res < f.cres_unit || c_res % f.cres_unit != 0)) return -2;
     if ((V != 25 && V != 18) || c_out % WMT != 0 || c < 1 || n_seg < 1) return -2;
     if ((int64_t)t_in * V >= (1 << 26)) return -2;                    // 32-bit position / lane byte offsets inside a segment
     if (csk_diag_flag("CSK_TCN_WINO") && csk_diag_int("CSK_TCN_WINO") < 2) return -2;   // diagnostic A/B switch: the direct kernels
-    const int t_out = t_in - 8;
+    const int t_out = (t_in + 2 * pad - k) / stride + 1;
     const int qp = (t_out + 1) / 2 * V;
     const int mw = wino_pick_mw(qp, c_out, stride);
     const int qtiles = (qp + WNT / mw - 1) / (WNT / mw), mtiles = c_out / (WMT * mw);
     if ((int64_t)qtiles * mtiles * n_seg >= (1ll << 31)) return -2;
-    const bool xr = res || res_conv;
-    TcnParams p = {};
-    p.y = y; p.w = w_wino; p.xres = xr ? x_res : nullptr; p.wres = res_conv ? w_res : nullptr; p.bias = bias; p.out = out;
-    p.C = c; p.Cpad = round_up(c, CSK_CPAD); p.Cout = c_out; p.Mpad = round_up(c_out, CSK_MT);
-    p.Tin = t_in; p.Tout = t_out; p.V = V; p.K = k; p.stride = 1; p.pad = 0;
-    p.res_mode = res_mode; p.Cres = xr ? c_res : 0; p.CresPad = round_up(p.Cres, CSK_CPAD); p.Tres = xr ? t_res : 0;
-    p.res_off = xr ? 4 : 0; p.relu = relu;
-    p.vmagic = vmagic_of(V); p.mtiles = (unsigned)mtiles; p.qtiles = (unsigned)qtiles; p.nt = qp;
-    void (*kern)(TcnParams);
-    int ldb;
-    if (mw == 2) {
-        kern = res_conv ? (V == 25 ? tcn_stage_wino_kernel<25, false, 2, true, true> : tcn_stage_wino_kernel<18, false, 2, true, true>)
-               : res    ? (V == 25 ? tcn_stage_wino_kernel<25, true, 2, true> : tcn_stage_wino_kernel<18, true, 2, true>)
-                        : (V == 25 ? tcn_stage_wino_kernel<25, false, 2, true> : tcn_stage_wino_kernel<18, false, 2, true>);
-        ldb = V == 25 ? wino_ldb<25, 2>() : wino_ldb<18, 2>();
-    } else {
-        kern = res_conv ? (V == 25 ? tcn_stage_wino_kernel<25, false, 1, true, true> : tcn_stage_wino_kernel<18, false, 1, true, true>)
-               : res    ? (V == 25 ? tcn_stage_wino_kernel<25, true, 1, true> : tcn_stage_wino_kernel<18, true, 1, true>)
-                        : (V == 25 ? tcn_stage_wino_kernel<25, false, 1, true> : tcn_stage_wino_kernel<18, false, 1, true>);
-        ldb = V == 25 ? wino_ldb<25>() : wino_ldb<18>();
-    }
-    p.ldb = ldb;
-    const size_t lds = (size_t)(WTAPS * KC * WMT * mw + KC * ldb) * sizeof(float);
-    if (const int e = csk_ensure_lds((const void *)kern, lds)) return e;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(qtiles * mtiles * n_seg)), dim3(NTHREADS), lds, (hipStream_t)stream, p);
+    // a form without residual has always passed nullptr / 0 for the residual fields
+    TcnParams p = tcn_params(y, w_img, res ? x_res : nullptr, res_mode == CSK_RES_CONV ? w_res : nullptr, bias, out, c, c_out, t_in, t_out,
+                             V, k, stride, pad, res_mode, res ? c_res : 0, res ? t_res : 0, res ? f.res_off : 0, relu);
+    p.mtiles = (unsigned)mtiles; p.qtiles = (unsigned)qtiles; p.nt = qp;
+    const WinoKernel wk = V == 25 ? (mw == 2 ? wino_kernel_of<25, 2>(form, res_mode) : wino_kernel_of<25, 1>(form, res_mode))
+                                  : (mw == 2 ? wino_kernel_of<18, 2>(form, res_mode) : wino_kernel_of<18, 1>(form, res_mode));
+    p.ldb = wk.ldb;
+    const size_t lds = (size_t)(wk.taps * KC * WMT * mw + KC * wk.ldb) * sizeof(float);
+    if (const int e = csk_ensure_lds((const void *)wk.kern, lds)) return e;
+    hipLaunchKernelGGL(wk.kern, dim3((unsigned)(qtiles * mtiles * n_seg)), dim3(NTHREADS), lds, (hipStream_t)stream, p);
     return (int)hipGetLastError();
 }
 
-// form B of csk_tcn_stage_wino_ext_f32; -2 as above
-static int tcn_stage_wino_s2_launch(const float *y, const float *w_s2, const float *x_res, const float *w_res, const float *bias,
-                                    float *out, int n_seg, int c, int c_out, int t_in, int V, int k, int stride, int pad,
-                                    int res_mode, int c_res, int t_res, int res_off, int relu, void *stream) {
-    if (!w_s2 || !y || !bias || !out) return -2;
-    if (k != 9 || stride != 2 || pad != 4 || res_off != 0) return -2;
-    const bool conv = res_mode == CSK_RES_CONV;
-    if (!conv && res_mode != CSK_RES_NONE) return -2;
-    if (conv && (!x_res || !w_res || c_res < 1 || t_res != t_in)) return -2;
-    if ((V != 25 && V != 18) || c_out % WMT != 0 || c < 1 || n_seg < 1 || t_in < 1) return -2;
-    if ((int64_t)t_in * V >= (1 << 26)) return -2;                    // 32-bit position / lane byte offsets inside a segment
-    if (csk_diag_flag("CSK_TCN_WINO") && csk_diag_int("CSK_TCN_WINO") < 2) return -2;   // diagnostic A/B switch: the direct kernels
-    const int t_out = (t_in - 1) / 2 + 1;
-    const int qp = (t_out + 1) / 2 * V;
-    const int mw = wino_pick_mw(qp, c_out, stride);
-    const int qtiles = (qp + WNT / mw - 1) / (WNT / mw), mtiles = c_out / (WMT * mw);
-    if ((int64_t)qtiles * mtiles * n_seg >= (1ll << 31)) return -2;
-    TcnParams p = {};
-    p.y = y; p.w = w_s2; p.xres = conv ? x_res : nullptr; p.wres = conv ? w_res : nullptr; p.bias = bias; p.out = out;
-    p.C = c; p.Cpad = round_up(c, CSK_CPAD); p.Cout = c_out; p.Mpad = round_up(c_out, CSK_MT);
-    p.Tin = t_in; p.Tout = t_out; p.V = V; p.K = k; p.stride = 2; p.pad = pad;
-    p.res_mode = res_mode; p.Cres = conv ? c_res : 0; p.CresPad = round_up(p.Cres, CSK_CPAD); p.Tres = conv ? t_res : 0;
-    p.res_off = 0; p.relu = relu;
-    p.vmagic = vmagic_of(V); p.mtiles = (unsigned)mtiles; p.qtiles = (unsigned)qtiles; p.nt = qp;
-    void (*kern)(TcnParams);
-    int ldb;
-    if (mw == 2) {
-        kern = conv ? (V == 25 ? tcn_stage_wino_s2_kernel<25, true, 2> : tcn_stage_wino_s2_kernel<18, true, 2>)
-                    : (V == 25 ? tcn_stage_wino_s2_kernel<25, false, 2> : tcn_stage_wino_s2_kernel<18, false, 2>);
-        ldb = V == 25 ? wino2_ldb<25, 2>() : wino2_ldb<18, 2>();
-    } else {
-        kern = conv ? (V == 25 ? tcn_stage_wino_s2_kernel<25, true> : tcn_stage_wino_s2_kernel<18, true>)
-                    : (V == 25 ? tcn_stage_wino_s2_kernel<25, false> : tcn_stage_wino_s2_kernel<18, false>);
-        ldb = V == 25 ? wino2_ldb<25>() : wino2_ldb<18>();
-    }
-    p.ldb = ldb;
-    const size_t lds = (size_t)(W2TAPS * KC * WMT * mw + KC * ldb) * sizeof(float);
-    if (const int e = csk_ensure_lds((const void *)kern, lds)) return e;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(qtiles * mtiles * n_seg)), dim3(NTHREADS), lds, (hipStream_t)stream, p);
-    return (int)hipGetLastError();
+// the entries that fall back themselves: the form's kernel, else (-2) the direct kernels on the direct image w
+static int tcn_stage_wino_or_direct(int form, const float *y, const float *w, const float *x_res, const float *w_res, const float *bias,
+                                    float *out, int n_seg, int c, int c_out, int t_in, int V, int k, int stride, int pad, int res_mode,
+                                    int c_res, int t_res, int res_off, int relu, const float *w_img, void *stream) {
+    const int rc = form < 0 ? -2
+                            : tcn_stage_wino_launch((WinoFormId)form, y, w_img, x_res, w_res, bias, out, n_seg, c, c_out, t_in, V, k, stride,
+                                                    pad, res_mode, c_res, t_res, res_off, relu, stream);
+    if (rc != -2) return rc;
+    return csk_tcn_stage_f32(y, w, x_res, w_res, bias, out, n_seg, c, c_out, t_in, V, k, stride, pad, res_mode, c_res, t_res,
+                             res_off, relu, stream);
 }
 
 extern "C" int csk_tcn_stage_wino_f32(const float *y, const float *w, const float *x_res, const float *w_res, const float *bias,
                                       float *out, int n_seg, int c, int c_out, int t_in, int V, int k, int stride, int pad,
                                       int res_mode, int c_res, int t_res, int res_off, int relu, const float *w_wino, void *stream) {
-    const int rc = tcn_stage_wino_launch(y, w_wino, x_res, bias, out, n_seg, c, c_out, t_in, V, k, stride, pad, res_mode, c_res,
-                                         t_res, res_off, relu, stream);
-    if (rc != -2) return rc;
-    return csk_tcn_stage_f32(y, w, x_res, w_res, bias, out, n_seg, c, c_out, t_in, V, k, stride, pad, res_mode, c_res, t_res,
-                             res_off, relu, stream);
+    return tcn_stage_wino_or_direct(WINO_PADDED_IDENT, y, w, x_res, w_res, bias, out, n_seg, c, c_out, t_in, V, k, stride, pad, res_mode,
+                                    c_res, t_res, res_off, relu, w_wino, stream);
 }
 
 extern "C" int csk_tcn_stage_wino_ext_f32(const float *y, const float *w, const float *x_res, const float *w_res, const float *bias,
                                           float *out, int n_seg, int c, int c_out, int t_in, int V, int k, int stride, int pad,
                                           int res_mode, int c_res, int t_res, int res_off, int relu, const float *w_wino_ext,
                                           void *stream) {
-    int rc = -2;
-    if (stride == 1)
-        rc = tcn_stage_wino_launch(y, w_wino_ext, nullptr, bias, out, n_seg, c, c_out, t_in, V, k, stride, pad, res_mode, c_res,
-                                   t_res, res_off, relu, stream, true);
-    else if (stride == 2)
-        rc = tcn_stage_wino_s2_launch(y, w_wino_ext, x_res, w_res, bias, out, n_seg, c, c_out, t_in, V, k, stride, pad, res_mode,
-                                      c_res, t_res, res_off, relu, stream);
-    if (rc != -2) return rc;
-    return csk_tcn_stage_f32(y, w, x_res, w_res, bias, out, n_seg, c, c_out, t_in, V, k, stride, pad, res_mode, c_res, t_res,
-                             res_off, relu, stream);
+    // form A at stride 1, form B at stride 2, the direct kernels at any other
+    return tcn_stage_wino_or_direct(stride == 1 ? WINO_PADDED_NONE : stride == 2 ? WINO_S2 : -1, y, w, x_res, w_res, bias, out, n_seg, c,
+                                    c_out, t_in, V, k, stride, pad, res_mode, c_res, t_res, res_off, relu, w_wino_ext, stream);
 }
 
 extern "C" int csk_tcn_stage_wino_valid_f32(const float *y, const float *w, const float *x_res, const float *w_res, const float *bias,
                                             float *out, int n_seg, int c, int c_out, int t_in, int V, int k, int stride, int pad,
                                             int res_mode, int c_res, int t_res, int res_off, int relu, const float *w_wino,
                                             void *stream) {
-    const int rc = tcn_stage_wino_valid_launch(y, w_wino, x_res, bias, out, n_seg, c, c_out, t_in, V, k, stride, pad, res_mode,
-                                               c_res, t_res, res_off, relu, stream);
-    if (rc != -2) return rc;
-    return csk_tcn_stage_f32(y, w, x_res, w_res, bias, out, n_seg, c, c_out, t_in, V, k, stride, pad, res_mode, c_res, t_res,
-                             res_off, relu, stream);
+    return tcn_stage_wino_or_direct(WINO_VALID, y, w, x_res, w_res, bias, out, n_seg, c, c_out, t_in, V, k, stride, pad, res_mode, c_res,
+                                    t_res, res_off, relu, w_wino, stream);
 }
 
 // -2 where the shape is not the kernel's: no launch, the caller runs csk_tcn_stage_f32 (include/cskel.h)
@@ -892,6 +830,7 @@ extern "C" int csk_tcn_stage_wino_valid_res_f32(const float *y, const float *x_r
                                                 int n_seg, int c, int c_out, int t_in, int V, int k, int stride, int pad,
                                                 int res_mode, int c_res, int t_res, int res_off, int relu, const float *w_wino,
                                                 void *stream) {
-    return tcn_stage_wino_valid_launch(y, w_wino, x_res, bias, out, n_seg, c, c_out, t_in, V, k, stride, pad, res_mode, c_res, t_res,
-                                       res_off, relu, stream, true, w_res);
+    return tcn_stage_wino_launch(WINO_VALID_RES, y, w_wino, x_res, w_res, bias, out, n_seg, c, c_out, t_in, V, k, stride, pad, res_mode,
+                                 c_res, t_res, res_off, relu, stream);
 }
+

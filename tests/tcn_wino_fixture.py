@@ -3,7 +3,7 @@ tests/test_tcn_wino_fixture_cpu.py: the Winograd F(2, 3) clip temporal convs of 
 ("id"), csk_tcn_stage_wino_ext_f32 ("ext"), csk_tcn_stage_wino_valid_f32 ("valid") and csk_tcn_stage_wino_valid_res_f32
 ("valid_res").
 
-select() restates, from tcn_stage_wino_launch, tcn_stage_wino_valid_launch, tcn_stage_wino_s2_launch and wino_pick_mw, what a
+select() restates, from tcn_stage_wino_launch with its table of forms (WINO_FORMS) and wino_pick_mw, what a
 launch gets: whether the gate takes it, the template instantiation, the grid, and per column tile the pair range and the staging
 form.  Nothing is read from csrc.  reachable() sweeps select() over the launchers' domain.
 

@@ -674,6 +674,113 @@ def test_round5_split_k_tcn_entry_validates_its_arguments_without_a_gpu():
     assert tcn(c_res=32) == -1 and b"identity residual" in lib.csk_last_error()
 
 
+# The temporal-conv entries below are called with fake pointers and always with at least one fault that the direct entry refuses
+# before anything is launched.  Expected messages are the texts the entries have always reported (written out, not composed).
+_FAKE = ctypes.c_void_p(0x1000)
+
+
+def _tcn_args(t_in=20, k=9, stride=1, pad=4, res=1, c=64, c_out=64, c_res=64, t_res=20, res_off=0, v=25, n_seg=1):
+    return (n_seg, c, c_out, t_in, v, k, stride, pad, res, c_res, t_res, res_off, 1)
+
+
+def _wino_entries(lib):
+    """(name, call(**kw), shape the entry's Winograd gate would take but for the fault added to it)"""
+    def falling_back(fn):
+        return lambda y=_FAKE, x_res=_FAKE, w_res=_FAKE, **kw: fn(y, _FAKE, x_res, w_res, _FAKE, _FAKE, *_tcn_args(**kw), _FAKE, None)
+    return (("wino", falling_back(lib.csk_tcn_stage_wino_f32), dict(stride=1, pad=4, res=1, res_off=0)),
+            ("ext stride 1", falling_back(lib.csk_tcn_stage_wino_ext_f32), dict(stride=1, pad=4, res=0, res_off=0)),
+            ("ext stride 2", falling_back(lib.csk_tcn_stage_wino_ext_f32), dict(stride=2, pad=4, res=2, res_off=0)),
+            ("valid", falling_back(lib.csk_tcn_stage_wino_valid_f32), dict(stride=1, pad=0, res=1, res_off=4)))
+
+
+def _both_refuse_faults(base):
+    """faults added to a shape `base` (stride, pad, res, res_off) that the Winograd gates and the direct entry both refuse:
+    (keywords, the direct entry's message without its prefix)"""
+    short = dict(pad=0, t_in=5) if base["pad"] == 0 else dict(pad=3, t_in=2)          # t_in + 2 pad < 9 with t_in >= 1
+    ranged = dict(base, t_res=10) if base["res"] else dict(base, res=1, t_res=10)     # 10 residual frames: the last output frame reads past them
+    return ((dict(base, y=None), b"null pointer"),
+            (dict(base, res=1, c_res=32), b"identity residual needs c_res == c_out"),
+            (dict(base, **short), b"t_in too short for kernel"),
+            (ranged, b"residual frames out of range"))
+
+
+def test_winograd_entries_report_the_direct_entrys_errors_without_a_gpu():
+    """csk_tcn_stage_wino_f32 / _ext_f32 (both strides) / _valid_f32: a call their gate refuses (-2 inside) goes to csk_tcn_stage_f32,
+    and what that refuses comes back as -1 with its message; nothing is launched."""
+    lib = pkg.native.lib()
+    for name, call, base in _wino_entries(lib):
+        for kw, msg in _both_refuse_faults(base):
+            assert call(**kw) == -1, (name, kw)
+            assert lib.csk_last_error() == b"tcn_stage: " + msg, (name, kw, lib.csk_last_error())
+        # two faults: the first in the direct entry's order
+        assert call(**dict(base, y=None, res=1, c_res=32)) == -1 and lib.csk_last_error() == b"tcn_stage: null pointer", name
+        assert call(**dict(base, res=1, c_res=32, t_res=10)) == -1, name
+        assert lib.csk_last_error() == b"tcn_stage: identity residual needs c_res == c_out", name
+
+
+def test_winograd_valid_res_entry_refuses_without_falling_back_and_without_a_gpu():
+    """csk_tcn_stage_wino_valid_res_f32 answers -2 to what its kernel does not take -- the same faults, and c_res = 24 (not whole
+    16-channel chunks of the residual image) -- and leaves the direct entry to its caller."""
+    lib = pkg.native.lib()
+
+    def call(y=_FAKE, x_res=_FAKE, w_res=_FAKE, **kw):
+        return lib.csk_tcn_stage_wino_valid_res_f32(y, x_res, w_res, _FAKE, _FAKE, *_tcn_args(**kw), _FAKE, None)
+    base = dict(stride=1, pad=0, res=2, res_off=4)
+    for kw, _ in _both_refuse_faults(base):
+        assert call(**kw) == -2, kw
+    assert call(**dict(base, c_res=24)) == -2
+    assert call(**dict(base, c_res=8)) == -2
+    assert call(**dict(base, w_res=None)) == -2
+
+
+def test_direct_and_bf16x3_tcn_entries_share_their_argument_checks_each_under_its_own_name():
+    """csk_tcn_stage_f32 and csk_tcn_stage_bf16x3: every shared fault is reported, with the entry's own prefix; for a call with two
+    faults the first in the order the entries have always checked them is reported."""
+    lib = pkg.native.lib()
+
+    def entry(fn):
+        return lambda y=_FAKE, x_res=_FAKE, w_res=_FAKE, **kw: fn(y, _FAKE, x_res, w_res, _FAKE, _FAKE, *_tcn_args(**kw), None)
+    huge = dict(t_in=1 << 20, t_res=1 << 20, v=64)                    # t_in * V = 2^26
+    for prefix, call in ((b"tcn_stage: ", entry(lib.csk_tcn_stage_f32)), (b"tcn_stage_bf16x3: ", entry(lib.csk_tcn_stage_bf16x3))):
+        def first(msg, **kw):
+            assert call(**kw) == -1, (prefix, kw)
+            assert lib.csk_last_error() == prefix + msg, (prefix, kw, lib.csk_last_error())
+        first(b"null pointer", y=None)
+        for kw in (dict(n_seg=0), dict(c=0), dict(c_out=0), dict(t_in=0), dict(v=1), dict(v=65)):
+            first(b"bad dims", **kw)
+        first(b"t_in too short for kernel", pad=3, t_in=2)
+        first(b"residual requested without x_res", x_res=None)
+        first(b"identity residual needs c_res == c_out", c_res=32)
+        first(b"conv residual without w_res", res=2, w_res=None)
+        first(b"residual frames out of range", t_res=10)
+        first(b"residual frames out of range", res_off=-1)
+        first(b"T*V too large for 32-bit position arithmetic", **huge)
+        # two faults
+        first(b"null pointer", y=None, c=0)
+        first(b"bad dims", c=0, pad=9)
+        first(b"t_in too short for kernel", pad=3, t_in=2, x_res=None)
+        first(b"residual requested without x_res", x_res=None, c_res=32)
+        first(b"identity residual needs c_res == c_out", c_res=32, t_res=10)
+        first(b"conv residual without w_res", res=2, w_res=None, t_res=10)
+        first(b"residual frames out of range", **dict(huge, t_res=10))
+    f32, bf = entry(lib.csk_tcn_stage_f32), entry(lib.csk_tcn_stage_bf16x3)
+    # the checks that differ sit between the dims and t_in, in each entry
+    assert f32(k=10, t_in=1) == -1 and lib.csk_last_error() == b"tcn_stage: bad k/stride/pad (k <= 9)"
+    assert f32(stride=0, c=0) == -1 and lib.csk_last_error() == b"tcn_stage: bad dims"
+    assert f32(stride=0, pad=3, t_in=2) == -1 and lib.csk_last_error() == b"tcn_stage: bad k/stride/pad (k <= 9)"
+    assert bf(k=5, pad=2, stride=5) == -1
+    assert lib.csk_last_error() == b"tcn_stage_bf16x3: the split kernel is built for the 9 x 1 temporal conv (k = 5); use csk_tcn_stage_f32"
+    assert bf(stride=5, pad=3, t_in=2) == -1 and lib.csk_last_error() == b"tcn_stage_bf16x3: bad stride/pad (stride <= 4)"
+    assert bf(k=5, pad=2, c=0) == -1 and lib.csk_last_error() == b"tcn_stage_bf16x3: bad dims"
+    # ... and the entries' own later checks come after the shared ones
+    assert lib.csk_tcn_stage_bf16x3(_FAKE, ctypes.c_void_p(0x1004), _FAKE, _FAKE, _FAKE, _FAKE, *_tcn_args(**huge), None) == -1
+    assert lib.csk_last_error() == b"tcn_stage_bf16x3: T*V too large for 32-bit position arithmetic"
+    assert lib.csk_tcn_stage_bf16x3(_FAKE, ctypes.c_void_p(0x1004), _FAKE, _FAKE, _FAKE, _FAKE, *_tcn_args(), None) == -1
+    assert lib.csk_last_error() == b"tcn_stage_bf16x3: packed weights must be 16-byte aligned"
+    assert lib.csk_tcn_stage_splitk_f32(_FAKE, _FAKE, _FAKE, _FAKE, _FAKE, _FAKE, *_tcn_args(**huge), 0, _FAKE, None) == -1
+    assert lib.csk_last_error() == b"tcn_stage: T*V too large for 32-bit position arithmetic"
+
+
 def test_folded_operand_cache_sees_every_kind_of_weight_edit():
     """_Folded._packed_ops re-reads a snapshot of dict slots instead of walking parameters() on every call; every way the
     weights can change must still refold on the NEXT call: in-place edit, p.data = ..., replaced Parameter, swapped
