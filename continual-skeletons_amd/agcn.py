@@ -281,12 +281,12 @@ class CoAGcn(CoStGcn):
         """(N, C, T, V, M) -> (N*M, 256, T', V): the layer-10 feature frames of ONE clip pass in which every adaptive graph conv
         forms its attention per frame (``AdaptiveGraphConvolution.forward_framewise``) -- frame j is what the steps emit as
         their j-th layer-10 frame, as long as they emit it (``clip_as_steps_map``); the frames behind it are the ones the end
-        padding releases.  Intake, pre-normalisation and modality as the steps apply them (a motion modality: the backward
-        difference, ``_history_as_stepped``).  Reads and writes no continual state."""
+        padding releases.  The input pre-passes as the steps apply them (a motion modality: the backward difference;
+        ``_prepare_clip_as_stepped``).  Reads and writes no continual state."""
         self._require_eval()
         x = self._intake_clip(x)
         native.require_device_f32(x, "CoAGcn input")
-        _, d = self._history_as_stepped(x)
+        _, d = self._prepare_clip_as_stepped(x)
         n, c, t, v, m = d.shape
         ops = self._packed_ops(x.device)
         h = torch.empty((n * m, c, t, v), device=x.device, dtype=torch.float32)

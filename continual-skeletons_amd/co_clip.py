@@ -37,8 +37,8 @@ class ClipAsSteps:
 
     def features_clip_as_steps(self, x):
         """(N, C, T, V, M) -> (N*M, 256, T', V): the layer-10 feature frames of the model's own clip pass over the frames the
-        steps would have derived -- intake, pre-normalisation and modality as the steps apply them (a motion modality: the
-        backward difference, ``_history_as_stepped``).  Frame j is what the steps emit as their j-th layer-10 frame, as long
+        steps would have derived -- the input pre-passes as the steps apply them (a motion modality: the backward
+        difference; ``_prepare_clip_as_stepped``).  Frame j is what the steps emit as their j-th layer-10 frame, as long
         as they emit it (``clip_as_steps_map``); the frames behind it are the ones the end padding releases.  The unpadded
         '*' models need T >= 81, as their clip forward does.  Reads and writes no continual state."""
         self._check_clip_as_steps()
@@ -46,7 +46,7 @@ class ClipAsSteps:
         if self.unpadded and (x.dim() != 5 or x.shape[2] < self.receptive_field):
             raise ValueError(f"{type(self).__name__}'s clip forward needs T >= {self.receptive_field} frames, got {tuple(x.shape)}")
         native.require_device_f32(x, f"{type(self).__name__} input")
-        return self._clip_stack(self._history_as_stepped(x)[1])
+        return self._clip_stack(self._prepare_clip_as_stepped(x)[1])
 
     def forward_clip_as_steps(self, x, pad_end=False):
         """(N, C, T, V, M) -> (N, classes, n_predictions): what ``clean_state(); forward_steps(x, pad_end)`` returns (within the

@@ -93,8 +93,7 @@ class StreamMove:
                 ("layers", tuple((b.in_channels, b.out_channels, b.stride, b.kernel_size, b.delay, b.kind) for b in blks)),
                 ("input_cvm", (c, v, m)),
                 ("pool_size", self.pool_size), ("pool_padding", self.pool_padding),
-                ("input_modality", self.input_modality),
-                ("pre_normalization", (int(self.pre_normalization),) + tuple(self._pn_joints)),
+                *(entry for stage in self._record_stages for entry in stage.signature()),
                 ("split_k", tuple((b._pick_ksplit(0), b._pick_gcn_ksplit(0)) for b in blks)),
                 ("step_precision", tuple("bf16x3" if b._use_split_step() else "f32" for b in blks)))
 
@@ -111,10 +110,8 @@ class StreamMove:
             if i + 1 < len(blks):
                 out.append((f"out{i}", blk.out_channels, mv, (blks[i + 1].kernel_size - 1) // 2))
         out.append(("pool", 1, blks[-1].out_channels, self.pool_size))
-        if self.input_modality in ("joint_motion", "bone_motion"):
-            out += [("mod_prev", 1, c * v * m, 1), ("mod_flags", 1, 1, 1)]
-        if self.pre_normalization:
-            out += [("pn_rot", 1, 36, 1), ("pn_flags", 1, 1, 1)]      # (18,) fp64 = 36 words
+        for stage in self._record_stages:               # the input pre-passes (input_stage.py)
+            out += stage.windows()
         return out
 
     def record_floats(self):
@@ -127,7 +124,7 @@ class StreamMove:
         rings = {"xin0": (self._xin0, self._frames)}
         for i, st in enumerate(blk._state for blk in self._blocks):
             rings[f"y{i}"], rings[f"out{i}"] = (st.y, st.s), (st.out, st.e)
-        arrays = {"mod_prev": self._mod_prev, "mod_flags": self._mod_flags, "pn_rot": self._pn_rot, "pn_flags": self._pn_flags}
+        arrays = dict(pair for stage in self._record_stages for pair in stage.state())
         jobs, offset = [], 0
         for name, rows, seg, window in self._move_windows():
             if name == "pool":                          # [pool_size][N][C]: stream n owns row n of every entry

@@ -17,7 +17,6 @@ import torch
 from . import native
 from .blocks import SpatioTemporalBlock
 from .co_migrate import StreamState
-from .modality import MOTION
 
 
 class StreamPrime:
@@ -100,15 +99,7 @@ class StreamPrime:
         if not isinstance(x_hist, torch.Tensor) or x_hist.dim() != 5:
             raise RuntimeError(f"prime_state takes an (n, C, T, V, M) history tensor, got "
                                f"{tuple(x_hist.shape) if isinstance(x_hist, torch.Tensor) else type(x_hist).__name__}")
-        if self.keypoint_intake:                        # keypoints.py: the history is an (n, T, P, V, 3) keypoint clip
-            t = x_hist.shape[1]
-            if tuple(x_hist.shape) != self._keypoint_shape(x_hist.shape[0], t):
-                raise RuntimeError(f"keypoint history shape {tuple(x_hist.shape)} does not match (n, T, {self._kp_people}, "
-                                   f"{self.input_shape[2]}, 3)")
-        else:
-            n, c, t, v, m = x_hist.shape
-            if (c, v, m) != (self.input_shape[0], self.input_shape[2], self.input_shape[3]):
-                raise RuntimeError(f"history shape {tuple(x_hist.shape)} does not match input_shape {self.input_shape}")
+        t = self._fed().check_history(x_hist)           # channel-first, or the layout of the intake that is on
         if t % self.stride:
             raise ValueError(f"prime_state: a history of {t} frames is not a multiple of the total stride {self.stride}: the stride "
                              "phase of the strided blocks must match the slab's (drop the oldest frames)")
@@ -127,29 +118,16 @@ class StreamPrime:
         return self._check_import(StreamState(torch.empty((x_hist.shape[0], 0)), ages, self.move_signature()), indices)
 
     # ---- the clip pass -----------------------------------------------------------------------------------
-    def _history_as_stepped(self, x):
-        """The frames the steps would have derived from the history: pre-normalised (``_prenorm_clip``; off: ``x``), then the
-        modality.  A motion modality steps on the BACKWARD difference (3b): frame 0 is zero and frame s is the forward
-        difference of the clip form at s - 1 -- the same subtraction, shifted by one frame.  Returns (normalised joints,
-        derived frames)."""
-        xn = self._prenorm_clip(x)
-        d = self._derive_clip(xn)
-        if self.input_modality in MOTION:
-            shifted = torch.empty_like(d)
-            shifted[:, :, 0] = 0.0
-            shifted[:, :, 1:] = d[:, :, :-1]
-            d = shifted
-        return xn, d
-
     def _prime_chunk(self, x, packed, parts=SpatioTemporalBlock.forward_parts):
         """Records of the streams ``x`` (n, C, T, V, M) into ``packed`` (n, record_floats): the clip pass with every block's
-        post-GCN tensor and output kept, then one pack launch.  With the keypoint intake on, ``x`` is the (n, T, P, V, 3)
-        keypoint history and the selected clip takes its place first.  ``parts(blk, h)`` yields ``(y, out)`` of a block: its
+        post-GCN tensor and output kept, then one pack launch.  With an intake on, ``x`` is the history in its layout and
+        the channel-first clip takes its place first; the blocks run on the frames the steps would have derived from it
+        (``_prepare_clip_as_stepped``), and every pre-pass with state gives its part of the record (``prime``).  ``parts(blk, h)`` yields ``(y, out)`` of a block: its
         two clip stages, or a caller's form of them whose tensors are the steps' (agcn.py: the frame-wise graph conv)."""
         x = self._intake_clip(x)
         n, c, t, v, m = x.shape
         ops = self._packed_ops(x.device)
-        xn, d = self._history_as_stepped(x)
+        entered, d = self._prepare_clip_as_stepped(x)
         h = torch.empty((n * m, c, t, v), device=x.device, dtype=torch.float32)
         rc = native.lib().csk_input_norm_f32(native.ptr(d), native.ptr(ops["scale"]), native.ptr(ops["shift"]), native.ptr(h),
                                              n, c, t, v, m, c * t * v, t * v, native.stream_of(x))
@@ -159,18 +137,8 @@ class StreamPrime:
             clip[f"y{i}"], h = parts(blk, h)
             clip[f"out{i}"] = h
         small = {}
-        if self.input_modality in MOTION:               # the last normalised raw frame; every stream has a previous frame
-            small["mod_prev"] = xn[:, :, t - 1].contiguous()
-            small["mod_flags"] = torch.ones((n,), device=x.device, dtype=torch.int32)
-        if self.pre_normalization:
-            # the rotations a stream latches from its first frame, by the step entry itself (the bits of the steps)
-            first, rot = x[:, :, 0].contiguous(), torch.zeros((n, 18), device=x.device, dtype=torch.float64)
-            flags, sink = torch.zeros((n,), device=x.device, dtype=torch.int32), torch.empty((n, c, v, m), device=x.device)
-            rc = native.lib().csk_prenorm_frames_f32((ctypes.c_void_p * 1)(first.data_ptr()), (ctypes.c_void_p * 1)(sink.data_ptr()), 1,
-                                                     native.ptr(rot), native.ptr(flags), 1, n, v, m, *self._pn_joints,
-                                                     native.stream_of(x))
-            native.check(rc, "csk_prenorm_frames_f32")
-            small["pn_rot"], small["pn_flags"] = rot, flags
+        for stage in reversed(entered):                 # record order (``_record_stages``)
+            small.update(stage.prime(entered[stage], t))
         table = {name: (source, first) for name, source, _, first, _ in self.prime_table(t)}
         jobs, offset = [], 0
         for name, rows, seg, window in self._move_windows():

@@ -125,8 +125,8 @@ class StreamReset:
         for st in (blk._state for blk in self._blocks):
             jobs += [self._ring_job(st.y, 0, st.y.shape[0]), self._ring_job(st.out, 0, st.out.shape[0])]
         jobs.append(self._pool_job(0, self.pool_size))
-        jobs += self._modality_reset_jobs()        # a motion modality: the streams' next frame is a first frame (modality.py)
-        jobs += self._prenorm_reset_jobs()         # pre-normalisation: the next frame latches the rotations anew (prenorm.py)
+        for stage in self._record_stages:          # the input pre-passes with state: the streams' next frame is a first frame
+            jobs += stage.reset_jobs()
         self._scrub(jobs, dev, len(idx))
         self._leave_cohorts(idx)                                   # a stream reset again leaves its earlier cohort
         at = self._frames

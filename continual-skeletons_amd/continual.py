@@ -35,9 +35,10 @@ from .co_plan import NativePlan
 from .co_migrate import StreamMove
 from .co_prime import StreamPrime
 from .co_reset import StreamReset
-from .keypoints import ContinualKeypointIntake
-from .modality import ContinualModality
-from .prenorm import ContinualPreNorm
+from .input_stage import InputChain
+from .keypoints import KeypointIntake
+from .modality import InputModality
+from .prenorm import PreNorm
 from .models import MOD_TEMPORAL_PADDING, layer_table, per_layer
 
 MAX_CYCLE = native.CO_MAX_CYCLE
@@ -564,7 +565,7 @@ def co_geometry(c_in=3, unpadded=False):
     return r, p, s
 
 
-class CoStGcn(NativePlan, StreamReset, StreamMove, StreamPrime, ClipAsSteps, ContinualKeypointIntake, ContinualPreNorm, ContinualModality, _Folded):
+class CoStGcn(NativePlan, StreamReset, StreamMove, StreamPrime, ClipAsSteps, InputChain, _Folded):
     """CoST-GCN: models/cost_gcn/cost_gcn.py:21-41 + CoModelBase (models/base.py:68-227) without the Ride shell.
 
     ``forward_step(x_t: (N, C, V, M))`` -> logits (N, classes) on the steps where the whole stack (10 blocks,
@@ -574,23 +575,25 @@ class CoStGcn(NativePlan, StreamReset, StreamMove, StreamPrime, ClipAsSteps, Con
     (what ``map_state_dict`` does in the reference, base.py:200-224).  This class binds the state slab and steps on it; the
     native plan (co_plan.py: NativePlan), the per-stream reset (co_reset.py: StreamReset), moving streams between slabs
     (co_migrate.py: StreamMove), priming streams from buffered history with one clip pass (co_prime.py: StreamPrime), a stored clip at the
-    steps' arithmetic (co_clip.py: ClipAsSteps -- ``forward_clip_as_steps``) and the input modality
-    (modality.py: ContinualModality -- bone / motion frames derived from the joint frames in front of every cycle) are base classes,
-    and so is the pre-normalisation of raw joint frames (prenorm.py: ContinualPreNorm), which runs in front of the modality.
-    The keypoint intake (keypoints.py: ContinualKeypointIntake; off by default) runs in front of both: with it the model is fed
-    ``(N, P, V, 3)`` keypoint frames / ``(N, T, P, V, 3)`` clips in the place of the channel-first ones named here.
+    steps' arithmetic (co_clip.py: ClipAsSteps -- ``forward_clip_as_steps``) are base classes.  The input pre-passes are the
+    stage objects of ``STAGES`` (input_stage.py: InputChain), all off by default and run in that order in front of every cycle:
+    the keypoint intake (keypoints.py; with it the model is fed ``(N, P, V, 3)`` keypoint frames / ``(N, T, P, V, 3)`` clips in the
+    place of the channel-first ones named here), the pre-normalisation of raw joint frames (prenorm.py) and the input modality
+    (modality.py: bone / motion frames derived from the joint frames).
     """
 
     # False: drive every launch from Python (same kernels, same results).  Read on every cycle: both engines step on the one
     # counter buffer, so they may alternate; the plan itself is built when the slab is bound with the attribute set
     use_native_plan = True
     unpadded = False        # CoStGcnMod: the "*" layer table (stride 1, block padding 0 -> delay 8 per block)
+    STAGES = (KeypointIntake, PreNorm, InputModality)   # the input pre-passes, in order (the NTU intake has no step form)
 
     def __init__(self, graph_A, input_shape=(3, 300, 25, 2), num_classes=60, pool_size=-1, pool_padding=-1,
                  CoGraphConv=CoGraphConvolution):
         super().__init__()
         (c_in, t, v, m) = input_shape
         self.input_shape, self.num_classes = tuple(input_shape), num_classes
+        self._init_stages()
         self.data_bn = nn.BatchNorm1d(m * c_in * v)
         convs = [CoGraphConvolution if f is None else f for f in per_layer(CoGraphConv)]   # one factory, or ten (None: default)
         self.layers = nn.ModuleDict(OrderedDict(
@@ -671,10 +674,12 @@ class CoStGcn(NativePlan, StreamReset, StreamMove, StreamPrime, ClipAsSteps, Con
         self._pooled = torch.empty((n, 256), device=device, dtype=torch.float32)
         self._flushed = False
         self._forget_resets()
-        self._bind_modality(n, device)
-        self._bind_prenorm(n, device)
-        self._bind_intake(n, device)
+        for stage in self._record_stages:
+            stage.bind(n, device, mc)
         self._build_plan(device)
+
+    def _slab(self):
+        return None if self._n is None else (self._n, self._xin0.device, self.max_cycle, self._frames)
 
     _frames = _counter(0, "input frames received")
     _feats = _counter(1, "layer-10 emissions the head has taken")
@@ -709,20 +714,17 @@ class CoStGcn(NativePlan, StreamReset, StreamMove, StreamPrime, ClipAsSteps, Con
         self._n = None
 
     def state_bytes(self):
-        """Persistent continual state (input ring, per-block rings, pooling window; previous frame and flags of a motion modality;
-        latched rotations and flags of the pre-normalisation)."""
+        """Persistent continual state (input ring, per-block rings, pooling window; the state of the input pre-passes: previous
+        frame and flags of a motion modality, latched rotations and flags of the pre-normalisation)."""
         return (sum(blk._state.nbytes() for blk in self._blocks) + 4 * (self._xin0.numel() + self._pool_ring.numel())
-                + 4 * sum(t.numel() for t in self._modality_tensors()) + self._prenorm_state_bytes())
+                + sum(t.numel() * t.element_size() for t in self._stage_tensors()))
 
     def scratch_bytes(self):
         """Transient scratch, not state: the split-K partial sums (shared by the blocks that split their K loop) and, for
-        adaptive graph convs, the per-skeleton-frame adjacencies of a launch (shared by all blocks); with a bone / motion input
-        modality, the derived frames of a cycle; with pre-normalisation, its normalised frames; with the keypoint intake, its
-        selected frames."""
-        adj, mod, pn, kp = self.__dict__.get("_agcn_adj"), self._mod_scratch, self._pn_scratch, self._kp_scratch
-        return 4 * ((self._scratch.numel() if self._scratch is not None else 0) + (adj.numel() if adj is not None else 0)
-                    + (mod.numel() if mod is not None else 0) + (pn.numel() if pn is not None else 0)
-                    + (kp.numel() if kp is not None else 0))
+        adaptive graph convs, the per-skeleton-frame adjacencies of a launch (shared by all blocks); for every input pre-pass
+        that is on, the frames of a cycle behind it."""
+        buffers = [self._scratch, self.__dict__.get("_agcn_adj")] + [stage.scratch for stage in self.stages]
+        return 4 * sum(t.numel() for t in buffers if t is not None)
 
     def clean_state(self):
         if self._n is not None:
@@ -730,8 +732,8 @@ class CoStGcn(NativePlan, StreamReset, StreamMove, StreamPrime, ClipAsSteps, Con
             for blk in self._blocks:
                 blk.clean_state()
             self._pool_ring.zero_()
-            self._clean_modality()
-            self._clean_prenorm()
+            for stage in self._record_stages:
+                stage.clean()
             self._set_counters([0] * 22)
             self._flushed = False
             self._forget_resets()
@@ -743,26 +745,16 @@ class CoStGcn(NativePlan, StreamReset, StreamMove, StreamPrime, ClipAsSteps, Con
         (None, 0) if none) and the list of predictions.  While reset streams warm up (``reset_streams``) the cycle must not
         cross a multiple of the total stride, and what the not-yet-live blocks wrote for them is zeroed after its launches;
         ``peek``: the caller puts the counters back (one step, update_state=False) -- the next real step rewrites and scrubs
-        the same slots, so a peek does neither.  The engines step on ``_derive_frames(frames)``: the frames themselves for
-        the joint modality, else the bone / motion frames of the pre-pass (a peek leaves its previous-frame state alone); with
-        pre-normalisation on, ``_prenorm_frames`` runs first and the modality derives from the normalised frames.  With the
-        keypoint intake on, the frames are (N, P, V, 3) keypoints, checked as such in the place of the check against
-        ``input_shape``, and ``_intake_frames`` runs in front of both (stateless: a peek runs it as well)."""
+        the same slots, so a peek does neither.  The engines step on ``_stage_frames(frames)``: the frames themselves with
+        every input pre-pass off, else what the chain makes of them (a peek runs it with ``update=False``: the stages' state
+        stays).  The frames are checked in the layout the model is fed (``_fed``): channel-first against ``input_shape``, or
+        that of the intake that is on."""
         self._require_eval()
         frames = list(frames)
         if not 1 <= len(frames) <= self.max_cycle:
             raise ValueError(f"a cycle holds 1..{self.max_cycle} frames (set_max_cycle), got {len(frames)}")
         x0 = frames[0]
-        if self.keypoint_intake:
-            n = self._check_keypoint_frames(frames)
-        else:
-            for x_t in frames:
-                native.require_device_f32(x_t, "CoStGcn frame")
-                if x_t.shape != x0.shape or x_t.device != x0.device:
-                    raise RuntimeError("all frames of a cycle must have the same shape and device")
-            n, c, v, m = x0.shape
-            if (c, v, m) != (self.input_shape[0], self.input_shape[2], self.input_shape[3]):
-                raise RuntimeError(f"frame shape {tuple(x0.shape)} does not match input_shape {self.input_shape}")
+        n = self._fed().check_frames(frames)
         if self._n != n or self._xin0.device != x0.device:           # clean_state_on_shape_change (base.py:161-164)
             self._bind(n, x0.device)
         if any(b.precision != "f32" and b.step_precision == "f32" for b in self.layers.values()):
@@ -772,12 +764,11 @@ class CoStGcn(NativePlan, StreamReset, StreamMove, StreamPrime, ClipAsSteps, Con
             raise RuntimeError("the state was flushed by forward_steps(pad_end=True): the end padding has consumed ring slots "
                                "and advanced the blocks past the input frame count; call clean_state() before stepping on")
         engine = self._plan_cycle if self.use_native_plan and self.__dict__.get("_plan") else self._python_cycle
-        frames = self._intake_frames(frames)        # keypoints.py; off: the list itself
         if not self._cohorts or peek:              # nothing warms: the cycle is the one that runs without any reset
-            return engine(self._derive_frames(self._prenorm_frames(frames, update=not peek), update=not peek))
+            return engine(self._stage_frames(frames, update=not peek))
         self._check_cycle_while_warming(len(frames))
         before = self._counters()
-        res = engine(self._derive_frames(self._prenorm_frames(frames)))
+        res = engine(self._stage_frames(frames))
         self._scrub_cycle(before)
         return res
 
@@ -797,7 +788,11 @@ class CoStGcn(NativePlan, StreamReset, StreamMove, StreamPrime, ClipAsSteps, Con
 
     def _state_tensors(self):
         return ([self._xin0, self._pool_ring, self._pooled] + [t for blk in self._blocks for t in (blk._state.y, blk._state.out)]
-                + self._modality_tensors() + self._prenorm_tensors())
+                + self._stage_tensors())
+
+    def _stage_tensors(self):
+        """The per-stream state of the input pre-passes, in record order."""
+        return [t for stage in self._record_stages for t in stage.tensors()]
 
     def _ensure_bound(self, x_t):
         native.require_device_f32(x_t, "CoStGcn frame")
@@ -925,7 +920,7 @@ class CoStGcn(NativePlan, StreamReset, StreamMove, StreamPrime, ClipAsSteps, Con
             self.clean_state()
             ret = self.forward_steps(x)
             return ret[:, :, 0]
-        x = self._intake_clip(x)        # keypoints.py; off: x itself
+        x = self._intake_clip(x)        # the intake that is on (input_stage.py); none: x itself
         n, c, t, v, m = x.shape
         h = self._clip_features(x)                                        # (N*M, 256, T', V)
         tp = h.shape[2]
@@ -945,8 +940,7 @@ class CoStGcn(NativePlan, StreamReset, StreamMove, StreamPrime, ClipAsSteps, Con
 
     def _clip_features(self, x):
         native.require_device_f32(x, "CoStGcn input")
-        # pre-normalised joints (clip form; off: x itself), then the bone / motion clip (forward difference, as the reference's files)
-        return self._clip_stack(self._derive_clip(self._prenorm_clip(x)))
+        return self._clip_stack(self._prepare_clip(x))      # the pre-passes on channel-first input, clip form; all off: x itself
 
     def _clip_stack(self, x):
         """Input norm and the ten clip blocks on the derived frames ``x`` (N, C, T, V, M) -> (N*M, 256, T', V)."""
@@ -964,11 +958,9 @@ class CoStGcn(NativePlan, StreamReset, StreamMove, StreamPrime, ClipAsSteps, Con
         """Feed ``receptive_field - padding - 1`` random frames (models/base.py:144-159) so that the next
         frame produces layer-10 output."""
         self.clean_state()
-        c, _, v, m = self.input_shape
         frames = self.receptive_field - self.padding - 1 if frames is None else frames
         for _ in range(frames):
-            self.forward_step(torch.rand(self._keypoint_shape(n), device=device) if self.keypoint_intake
-                              else torch.randn((n, c, v, m), device=device))
+            self.forward_step(self._fed().random_frame(n, device))
 
 
 class CoStGcnMod(CoStGcn):

@@ -13,11 +13,10 @@ model only owns a scratch ``[max_cycle](N, 3, V, M)`` for the selected frames of
 rule are stated in include/cskel.h and DESIGN.md section 3f; tracking people across frames (``datasets/tools.py:openpose_match``,
 which the reference's pipeline does not call) and reading the estimator's JSON are not reproduced.
 """
-import ctypes
-
 import torch
 
-from . import native, parallel
+from . import native
+from .input_stage import InputStage, check_one_intake, switch_stage
 
 PEOPLE_IN = 5                       # the reference's num_person_in; num_person_out is the model's M
 MAX_PEOPLE, MAX_JOINTS = 8, 64      # limits of the entries (include/cskel.h)
@@ -56,84 +55,75 @@ def _check_model_shape(model, people_in):
     return people_in
 
 
-def _check_other_intake(model, enabled):
-    if enabled and getattr(model, "ntu_intake", False):        # ntu_intake.py: the clip models' other intake
-        raise ValueError("the NTU intake is on: a model runs one intake, switch it off first "
-                         "(ntu_intake.set_ntu_intake(model, enabled=False))")
+class KeypointIntake(InputStage):
+    """The keypoint intake of one model (input_stage.py): the switch, ``people`` (P), the clip pre-pass and the step pre-pass.
+    ``scratch`` [max_cycle](N, 3, V, M) takes the selected frames of a cycle, allocated when the slab is bound and only when
+    the switch is on.  There is no state: ``update`` is ignored and a peek (``update_state=False``) runs the same launch.
+    With the switch on, the stage also says what the model is fed: the frame, clip and history shapes and their error texts."""
 
+    name, what, intake, time_axis = "keypoints", "keypoint intake", True, 1
+    off_call = "keypoints.set_keypoint_intake(model, enabled=False)"
+    def __init__(self, shape):
+        super().__init__(shape)
+        self.on, self.people = False, PEOPLE_IN
 
-class KeypointIntake:
-    """Base class of the clip models (``StGcn`` and its siblings): the switch and the clip pre-pass."""
+    @property
+    def enabled(self):
+        return self.on
 
-    keypoint_intake = False
-    _kp_people = PEOPLE_IN
+    @property
+    def settings(self):
+        return self.on, self.people
 
-    def _set_keypoint_intake(self, enabled, people_in):
-        self.keypoint_intake = bool(enabled)
-        self._kp_people = people_in
+    def set(self, settings):
+        self.on, self.people = settings
 
-    def _keypoint_shape(self, n, t=None):
+    def fed_shape(self, n, t=None):
         """The input shape with the switch on: (n, P, V, 3) frames, (n, t, P, V, 3) clips."""
-        return (n,) + (() if t is None else (t,)) + (self._kp_people, self.input_shape[2], 3)
+        return (n,) + (() if t is None else (t,)) + (self.people, self.shape[2], 3)
 
-    def _intake_clip(self, k):
+    def clip(self, k):
         """The keypoint clip -> the channel-first clip the model runs on (the tensor itself when the switch is off)."""
-        if not self.keypoint_intake:
+        if not self.on:
             return k
         native.require_device_f32(k, "model input")
-        if k.dim() != 5 or tuple(k.shape) != self._keypoint_shape(k.shape[0], k.shape[1]):
-            raise RuntimeError(f"keypoint intake: expected an (N, T, {self._kp_people}, {self.input_shape[2]}, 3) keypoint clip, "
+        if k.dim() != 5 or tuple(k.shape) != self.fed_shape(k.shape[0], k.shape[1]):
+            raise RuntimeError(f"keypoint intake: expected an (N, T, {self.people}, {self.shape[2]}, 3) keypoint clip, "
                                f"got {tuple(k.shape)}")
-        return select_people_clip(k, self.input_shape[3])
+        return select_people_clip(k, self.shape[3])
 
+    def bind(self, n, device, max_cycle):
+        _, _, v, m = self.shape
+        self.scratch = torch.empty((max_cycle, n, 3, v, m), device=device, dtype=torch.float32) if self.on else None
 
-class ContinualKeypointIntake(KeypointIntake):
-    """Base class of ``CoStGcn``: the step pre-pass.  ``_kp_scratch`` [max_cycle](N, 3, V, M) takes the selected frames of a
-    cycle; it is scratch, allocated when the slab is bound (``_bind``) and only when the switch is on.  There is no state:
-    a peek (``update_state=False``) runs the same launch."""
-
-    _kp_scratch = None
-    time_axis = property(lambda self: 1 if self.keypoint_intake else 2, doc="the frame axis of the clips the model is fed")
-
-    def _set_keypoint_intake(self, enabled, people_in):
-        if bool(enabled) == self.keypoint_intake and people_in == self._kp_people:
-            return
-        if self._n is not None and self._frames != 0:
-            raise RuntimeError(f"the model has stepped {self._frames} frames with the keypoint intake "
-                               f"{'on' if self.keypoint_intake else 'off'}: its rings hold features of that input; call "
-                               "clean_state() before changing the keypoint intake")
-        super()._set_keypoint_intake(enabled, people_in)
-        if self._n is not None:
-            self._bind_intake(self._n, self._xin0.device)
-
-    def _bind_intake(self, n, device):
-        _, _, v, m = self.input_shape
-        self._kp_scratch = None
-        if self.keypoint_intake:
-            self._kp_scratch = torch.empty((self.max_cycle, n, 3, v, m), device=device, dtype=torch.float32)
-
-    def _check_keypoint_frames(self, frames):
-        """Host checks of a cycle's keypoint frames; returns the stream count."""
+    def check_frames(self, frames):
         x0 = frames[0]
         for x_t in frames:
             native.require_device_f32(x_t, "CoStGcn keypoint frame")
             if x_t.shape != x0.shape or x_t.device != x0.device:
                 raise RuntimeError("all frames of a cycle must have the same shape and device")
-        if x0.dim() != 4 or tuple(x0.shape) != self._keypoint_shape(x0.shape[0]):
-            raise RuntimeError(f"keypoint intake: frame shape {tuple(x0.shape)} does not match (N, {self._kp_people}, "
-                               f"{self.input_shape[2]}, 3)")
+        if x0.dim() != 4 or tuple(x0.shape) != self.fed_shape(x0.shape[0]):
+            raise RuntimeError(f"keypoint intake: frame shape {tuple(x0.shape)} does not match (N, {self.people}, "
+                               f"{self.shape[2]}, 3)")
         return x0.shape[0]
 
-    def _intake_frames(self, frames):
+    def check_history(self, x_hist):
+        t = x_hist.shape[1]
+        if tuple(x_hist.shape) != self.fed_shape(x_hist.shape[0], t):
+            raise RuntimeError(f"keypoint history shape {tuple(x_hist.shape)} does not match (n, T, {self.people}, "
+                               f"{self.shape[2]}, 3)")
+        return t
+
+    def random_frame(self, n, device):
+        return torch.rand(self.fed_shape(n), device=device)
+
+    def frames(self, frames, update=True):
         """The cycle's keypoint frames -> the selected channel-first frames (the list itself when the switch is off)."""
-        if not self.keypoint_intake:
+        if not self.on:
             return frames
-        r = len(frames)
         n, p, v, _ = frames[0].shape
-        out = [self._kp_scratch[i] for i in range(r)]
-        srcs = (ctypes.c_void_p * r)(*[x_t.data_ptr() for x_t in frames])
-        dsts = (ctypes.c_void_p * r)(*[o.data_ptr() for o in out])
-        rc = native.lib().csk_select_people_frames_f32(srcs, dsts, r, n, p, v, self.input_shape[3], native.stream_of(frames[0]))
+        out, srcs, dsts = self._into_scratch(frames)
+        rc = native.lib().csk_select_people_frames_f32(srcs, dsts, len(frames), n, p, v, self.shape[3], native.stream_of(frames[0]))
         native.check(rc, "csk_select_people_frames_f32")
         return out
 
@@ -147,19 +137,7 @@ def set_keypoint_intake(model, people_in: int = PEOPLE_IN, enabled: bool = True)
     ``ValueError`` for a model that does not take C = 3 channels, ``people_in`` outside [M, 8] or a clip model whose NTU intake
     (ntu_intake.py) is on; a continual model that has stepped (frame counter not 0) raises ``RuntimeError``: ``clean_state()``
     first.  Returns ``model``."""
-    if isinstance(model, parallel.StreamShards):
-        for shard in model.models:      # all validated before any is switched: the shards step in lock step
-            if not isinstance(shard, KeypointIntake):
-                raise TypeError(f"{type(shard).__name__} has no keypoint intake")
-            _check_model_shape(shard, people_in)
-            changes = bool(enabled) != shard.keypoint_intake or people_in != shard._kp_people
-            if isinstance(shard, ContinualKeypointIntake) and changes and shard._n is not None and shard._frames:
-                raise RuntimeError("a shard has stepped: call clean_state() on every shard model before changing the keypoint intake")
-        for shard in model.models:
-            shard._set_keypoint_intake(enabled, people_in)
-        return model
-    if not isinstance(model, KeypointIntake):
-        raise TypeError(f"{type(model).__name__} has no keypoint intake (StGcn, CoStGcn, their siblings, or a StreamShards)")
-    _check_other_intake(model, enabled)
-    model._set_keypoint_intake(enabled, _check_model_shape(model, people_in))
-    return model
+    def check(m, stage):
+        check_one_intake(m, stage, enabled)
+        return bool(enabled), _check_model_shape(m, people_in)
+    return switch_stage(model, "keypoints", KeypointIntake.what, check)

@@ -10,14 +10,15 @@ Clip forwards keep the reference's forward difference.  The continual path is ca
 step form is the backward difference ``m'[s] = x[s] - x[s-1]`` with ``m' = 0`` on a stream's first frame, i.e.
 ``m'[s] = m[s-1]`` -- a motion model's continual predictions are those of the forward-difference stream one frame later
 (DESIGN.md).  That needs state: the previous raw frame and a per-stream "has a previous frame" flag, which follow the
-rules of the rest of the continual state (``ContinualModality``).
+rules of the rest of the continual state (``InputModality``).
 """
 import ctypes
 
 import numpy as np
 import torch
 
-from . import graph, native, parallel
+from . import graph, native
+from .input_stage import InputStage, switch_stage
 
 MODALITIES = ("joint", "bone", "joint_motion", "bone_motion")
 MODE = {name: code for code, name in enumerate(MODALITIES)}       # CSK_MODALITY_* (include/cskel.h)
@@ -66,82 +67,88 @@ def derive_clip(x: torch.Tensor, modality: str, parents=None) -> torch.Tensor:
     return out
 
 
-class InputModality:
-    """Base class of the clip models (``StGcn`` and its siblings): the mode and the clip pre-pass."""
-
-    input_modality = "joint"
-
-    def _set_input_modality(self, modality):
-        self.__dict__["_mod_parents"] = _parents_arg(modality, self.input_shape[2])     # raises for an unknown skeleton
-        self.input_modality = modality
-
-    def _derive_clip(self, x):
-        if self.input_modality == "joint":
-            return x
-        native.require_device_f32(x, "model input")
-        return derive_clip(x, self.input_modality, self.__dict__["_mod_parents"])
-
-
-class ContinualModality(InputModality):
-    """Base class of ``CoStGcn``: the step pre-pass and its state.  ``_mod_scratch`` [max_cycle](N, C, V, M) takes the derived
-    frames of a cycle (scratch, any non-joint mode); ``_mod_prev`` (N, C, V, M), the last raw frame, and ``_mod_flags`` (N,)
-    int32, "this stream has a previous frame", are continual state of the two motion modes:
-      * allocated when the slab is bound (``_bind``), only for the modes that need them;
+class InputModality(InputStage):
+    """The modality of one model (input_stage.py): ``mode``, the clip pre-pass and the step pre-pass with its state.
+    ``scratch`` [max_cycle](N, C, V, M) takes the derived frames of a cycle (any non-joint mode); ``prev`` (N, C, V, M), the
+    last raw frame, and ``flags`` (N,) int32, "this stream has a previous frame", are continual state of the two motion modes:
+      * allocated when the slab is bound, only for the modes that need them;
       * ``clean_state`` clears them; ``reset_streams`` clears the flags of the reset streams in its own launch;
       * the single-step peek ``forward_step(update_state=False)`` runs the pre-pass with ``update = 0`` (nothing is written);
-      * the snapshot of ``forward_steps(update_state=False)`` holds them (``_state_tensors``)."""
+      * the snapshot of ``forward_steps(update_state=False)`` holds them."""
 
-    _mod_scratch = _mod_prev = _mod_flags = None
+    name, what = "modality", "input modality"
+    def __init__(self, shape):
+        super().__init__(shape)
+        self.mode, self.parents = "joint", None     # ``parents``: the host table of a bone mode, as the entries take it
+        self.prev = None
 
-    def _set_input_modality(self, modality):
-        if modality == self.input_modality:
-            return
-        if self._n is not None and self._frames != 0:
-            raise RuntimeError(f"the model has stepped {self._frames} frames in modality {self.input_modality!r}: its rings hold "
-                               "features of that input; call clean_state() before changing the input modality")
-        super()._set_input_modality(modality)
-        if self._n is not None:
-            self._bind_modality(self._n, self._xin0.device)
+    @property
+    def enabled(self):
+        return self.mode != "joint"
 
-    def _bind_modality(self, n, device):
-        c, _, v, m = self.input_shape
-        mode = self.input_modality
-        self._mod_scratch = self._mod_prev = self._mod_flags = None
-        if mode != "joint":
-            self._mod_scratch = torch.empty((self.max_cycle, n, c, v, m), device=device, dtype=torch.float32)
-        if mode in MOTION:
-            self._mod_prev = torch.zeros((n, c, v, m), device=device, dtype=torch.float32)
-            self._mod_flags = torch.zeros((n,), device=device, dtype=torch.int32)
+    @property
+    def settings(self):
+        return self.mode
 
-    def _clean_modality(self):
-        if self._mod_prev is not None:
-            self._mod_prev.zero_()
-            self._mod_flags.zero_()
+    def set(self, mode):
+        self.parents = _parents_arg(mode, self.shape[2])        # raises for an unknown skeleton
+        self.mode = mode
 
-    def _modality_tensors(self):
-        return [] if self._mod_prev is None else [self._mod_prev, self._mod_flags]
+    def stepped_with(self):
+        return f"in modality {self.mode!r}"
 
-    def _modality_reset_jobs(self):
-        """Scrub job (co_reset.py) that clears the flags of the streams being reset: the flag array as a ring of one slot and
-        one row in which every stream owns one 4-byte element (the all-zero pattern is int32 0)."""
-        if self._mod_flags is None:
-            return []
-        n = self._mod_flags.shape[0]
-        return [native.ScrubJob(self._mod_flags.data_ptr(), n, 1, 1, 0, 1, 1, native.SCRUB_BLOCK_RING)]
+    def clip(self, x):
+        if self.mode == "joint":
+            return x
+        native.require_device_f32(x, "model input")
+        return derive_clip(x, self.mode, self.parents)
 
-    def _derive_frames(self, frames, update=True):
+    def clip_as_stepped(self, x):
+        """A motion mode steps on the BACKWARD difference: frame 0 is zero and frame s is the forward difference of the clip
+        form at s - 1 -- the same subtraction, shifted by one frame."""
+        d = self.clip(x)
+        if self.mode in MOTION:
+            shifted = torch.empty_like(d)
+            shifted[:, :, 0] = 0.0
+            shifted[:, :, 1:] = d[:, :, :-1]
+            d = shifted
+        return d
+
+    def bind(self, n, device, max_cycle):
+        c, _, v, m = self.shape
+        self.scratch = self.prev = self.flags = None
+        if self.mode != "joint":
+            self.scratch = torch.empty((max_cycle, n, c, v, m), device=device, dtype=torch.float32)
+        if self.mode in MOTION:
+            self.prev = torch.zeros((n, c, v, m), device=device, dtype=torch.float32)
+            self.flags = torch.zeros((n,), device=device, dtype=torch.int32)
+
+    def state(self):
+        return [] if self.prev is None else [("mod_prev", self.prev), ("mod_flags", self.flags)]
+
+    def windows(self):
+        c, _, v, m = self.shape
+        return [("mod_prev", 1, c * v * m, 1), ("mod_flags", 1, 1, 1)] if self.mode in MOTION else []
+
+    def signature(self):
+        return [("input_modality", self.mode)]
+
+    def prime(self, x_in, t):
+        """The last frame that entered the stage; every stream has a previous frame."""
+        if self.mode not in MOTION:
+            return {}
+        return {"mod_prev": x_in[:, :, t - 1].contiguous(),
+                "mod_flags": torch.ones((x_in.shape[0],), device=x_in.device, dtype=torch.int32)}
+
+    def frames(self, frames, update=True):
         """The cycle's joint frames -> the frames the model steps on (the list itself for "joint").  ``update=False``: the
         previous-frame buffer and the flags stay as they are."""
-        mode = self.input_modality
-        if mode == "joint":
+        if self.mode == "joint":
             return frames
-        r = len(frames)
         n, c, v, m = frames[0].shape
-        out = [self._mod_scratch[i] for i in range(r)]
-        srcs = (ctypes.c_void_p * r)(*[x_t.data_ptr() for x_t in frames])
-        dsts = (ctypes.c_void_p * r)(*[o.data_ptr() for o in out])
-        rc = native.lib().csk_derive_modality_frames_f32(srcs, dsts, r, MODE[mode], self.__dict__["_mod_parents"],
-                                                         native.ptr(self._mod_prev), native.ptr(self._mod_flags), int(update),
+        out, srcs, dsts = self._into_scratch(frames)
+        rc = native.lib().csk_derive_modality_frames_f32(srcs, dsts, len(frames), MODE[self.mode], self.parents,
+                                                         native.ptr(self.prev), native.ptr(self.flags), int(update),
                                                          n, c, v, m, native.stream_of(frames[0]))
         native.check(rc, "csk_derive_modality_frames_f32")
         return out
@@ -154,17 +161,6 @@ def set_input_modality(model, modality: str = "joint"):
     (``Graph.bone_parents``: 25 or 18 joints); a model with another joint count raises here.  A continual model that has
     stepped (frame counter not 0) raises ``RuntimeError``: ``clean_state()`` first.  Returns ``model``."""
     _check_modality(modality)
-    if isinstance(model, parallel.StreamShards):
-        for shard in model.models:      # all validated before any is switched: the shards step in lock step
-            if not isinstance(shard, InputModality):
-                raise TypeError(f"{type(shard).__name__} has no input modality")
-            if isinstance(shard, ContinualModality) and modality != shard.input_modality and shard._n is not None and shard._frames:
-                raise RuntimeError("a shard has stepped: call clean_state() on every shard model before changing the input modality")
-            _parents_arg(modality, shard.input_shape[2])
-        for shard in model.models:
-            shard._set_input_modality(modality)
-        return model
-    if not isinstance(model, InputModality):
-        raise TypeError(f"{type(model).__name__} has no input modality (StGcn, CoStGcn, their siblings, or a StreamShards)")
-    model._set_input_modality(modality)
-    return model
+
+    return switch_stage(model, "modality", InputModality.what, lambda m, stage: modality,
+                        then=lambda m, mode: _parents_arg(mode, m.input_shape[2]))      # a bone mode: raises for an unknown skeleton

@@ -10,6 +10,7 @@ import torch.nn as nn
 
 from . import fold, native
 from .blocks import SpatioTemporalBlock, _Folded, init_weights
+from .input_stage import InputChain
 from .keypoints import KeypointIntake
 from .modality import InputModality
 from .ntu_intake import NtuIntake
@@ -51,8 +52,9 @@ def per_layer(factory):
     return [factory] * 10
 
 
-class StGcn(NtuIntake, KeypointIntake, PreNorm, InputModality, _Folded):
+class StGcn(InputChain, _Folded):
     unpadded = False     # StGcnMod: the "*" layer table (stride 1, temporal padding 0, centred residual shrink)
+    STAGES = (NtuIntake, KeypointIntake, PreNorm, InputModality)     # the input pre-passes, in order (input_stage.py)
 
     def __init__(self, graph_A, input_shape=(3, 300, 25, 2), num_classes=60, GraphConv=None):
         """graph_A: (3, V, V) adjacency; input_shape = (C, T, V, M) as datasets/datasets.py:128-134.  ``GraphConv``: the
@@ -62,6 +64,7 @@ class StGcn(NtuIntake, KeypointIntake, PreNorm, InputModality, _Folded):
         pad = {"temporal_padding": MOD_TEMPORAL_PADDING} if self.unpadded else {}
         (num_channels, num_frames, num_vertices, num_skeletons) = input_shape
         self.input_shape = tuple(input_shape)
+        self._init_stages()
         self.num_classes = num_classes
         convs = per_layer(GraphConv)
         self.data_bn = nn.BatchNorm1d(num_skeletons * num_channels * num_vertices)
@@ -95,8 +98,7 @@ class StGcn(NtuIntake, KeypointIntake, PreNorm, InputModality, _Folded):
         return h
 
     def features(self, x):
-        # pre-normalised joints first (prenorm.py; off: x itself), then the bone / motion clip (modality.py; joint: x itself)
-        h = self.input_norm(self._derive_clip(self._prenorm_clip(x)))
+        h = self.input_norm(self._prepare_clip(x))      # the pre-passes on channel-first input; all off: x itself
         for i in range(len(self.layers)):
             h = self.layers[f"layer{i + 1}"](h)
         return h
@@ -114,7 +116,7 @@ class StGcn(NtuIntake, KeypointIntake, PreNorm, InputModality, _Folded):
 
     def forward(self, x):
         self._require_eval()
-        x = self._intake_clip(x)        # ntu_intake.py, else keypoints.py; both off: x itself
+        x = self._intake_clip(x)        # the intake that is on (input_stage.py); none: x itself
         n, c, t, v, m = x.shape
         return self.head(self.features(x), n, m)
 

@@ -20,6 +20,7 @@ selection for live streams.
 import torch
 
 from . import native, parallel
+from .input_stage import InputStage, check_one_intake, switch_stage
 
 BODIES_IN = 4                                   # the reference's max_body_kinect; max_body_true is the model's M
 MAX_BODIES, MAX_JOINTS, MAX_FRAMES = 8, 64, 1024    # limits of the entry (include/cskel.h; CSK_NTU_MAX_FRAMES)
@@ -68,25 +69,35 @@ def _check_model_shape(model, bodies_in):
     return bodies_in
 
 
-class NtuIntake:
-    """Base class of the clip models (``StGcn`` and its siblings), in front of ``KeypointIntake``: the switch and the clip
-    pre-pass.  With the switch off ``_intake_clip`` is the next class's."""
+class NtuIntake(InputStage):
+    """The NTU intake of one clip model (input_stage.py), in front of the keypoint intake: the switch, ``bodies`` (P) and the
+    clip pre-pass.  It has no step form: the continual models' chains do not hold it."""
 
-    ntu_intake = False
-    _ntu_bodies = BODIES_IN
+    name, what, intake, time_axis = "ntu", "NTU intake", True, 1
+    off_call = "ntu_intake.set_ntu_intake(model, enabled=False)"
+    def __init__(self, shape):
+        super().__init__(shape)
+        self.on, self.bodies = False, BODIES_IN
 
-    def _set_ntu_intake(self, enabled, bodies_in):
-        self.ntu_intake = bool(enabled)
-        self._ntu_bodies = bodies_in
+    @property
+    def enabled(self):
+        return self.on
 
-    def _intake_clip(self, x):
+    @property
+    def settings(self):
+        return self.on, self.bodies
+
+    def set(self, settings):
+        self.on, self.bodies = settings
+
+    def clip(self, x):
         """The body clip -> the channel-first clip of ``input_shape[1]`` frames the model runs on."""
-        if not self.ntu_intake:
-            return super()._intake_clip(x)
+        if not self.on:
+            return x
         native.require_device_f32(x, "model input")
-        _, t, v, m = self.input_shape
-        if x.dim() != 5 or tuple(x.shape[2:]) != (self._ntu_bodies, v, 3) or not 1 <= x.shape[1] <= t:
-            raise RuntimeError(f"NTU intake: expected an (N, T <= {t}, {self._ntu_bodies}, {v}, 3) body clip, got {tuple(x.shape)}")
+        _, t, v, m = self.shape
+        if x.dim() != 5 or tuple(x.shape[2:]) != (self.bodies, v, 3) or not 1 <= x.shape[1] <= t:
+            raise RuntimeError(f"NTU intake: expected an (N, T <= {t}, {self.bodies}, {v}, 3) body clip, got {tuple(x.shape)}")
         return select_bodies_clip(x, t, m)
 
 
@@ -104,11 +115,9 @@ def set_ntu_intake(model, enabled: bool = True, bodies_in: int = BODIES_IN):
                         "bodies is a whole-clip statistic and the padding repeats frames that come later.  It runs on whole clips "
                         "only; to start streams from recorded frames, prepare the history with ntu_intake.select_bodies_clip and "
                         "hand it to prime_streams")
-    if not isinstance(model, NtuIntake):
-        raise TypeError(f"{type(model).__name__} has no NTU intake (StGcn, AGcn, STr or their '*' forms)")
-    _check_model_shape(model, bodies_in)
-    if enabled and model.keypoint_intake:
-        raise ValueError("the keypoint intake is on: a model runs one intake, switch it off first "
-                         "(keypoints.set_keypoint_intake(model, enabled=False))")
-    model._set_ntu_intake(enabled, bodies_in)
-    return model
+
+    def check(m, stage):
+        _check_model_shape(m, bodies_in)
+        check_one_intake(m, stage, enabled)
+        return bool(enabled), bodies_in
+    return switch_stage(model, "ntu", NtuIntake.what, check, family="StGcn, AGcn, STr or their '*' forms")

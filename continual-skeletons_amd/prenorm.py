@@ -8,14 +8,13 @@ model, and in front of the modality pre-pass (modality.py): the reference derive
 
 The centring is per frame, so it is causal; the two rotation matrices are latched from a stream's first frame.  That is
 per-stream state -- ``rot`` (N, 18) fp64 and ``has_rot`` (N,) int32 -- and it follows the rules of the rest of the continual
-state (``ContinualPreNorm``).  The arithmetic is stated in include/cskel.h and DESIGN.md section 3c; the reference's padding
+state (``PreNorm``).  The arithmetic is stated in include/cskel.h and DESIGN.md section 3c; the reference's padding
 of null frames looks ahead and is not reproduced, in either form (whole clips: the pre-pass of ntu_intake.py, in front of this one).
 """
-import ctypes
-
 import torch
 
-from . import native, parallel
+from . import native
+from .input_stage import InputStage, frame_pointers, switch_stage
 
 ZAXIS, XAXIS = (0, 1), (8, 4)       # the reference's defaults: hip -> spine on z, right -> left shoulder on x (NTU RGB+D)
 
@@ -58,86 +57,82 @@ def _check_model_shape(model, zaxis, xaxis):
     return _check_joints(v, zaxis, xaxis)
 
 
-class PreNorm:
-    """Base class of the clip models (``StGcn`` and its siblings): the switch and the clip pre-pass."""
+class PreNorm(InputStage):
+    """The pre-normalisation of one model (input_stage.py): the switch, the four joints, the clip pre-pass and the step
+    pre-pass with its state.  ``scratch`` [max_cycle](N, 3, V, M) takes the normalised frames of a cycle; ``rot`` (N, 18)
+    fp64, a stream's Rz then Rx, and ``flags`` (N,) int32, "this stream has latched its rotations", are continual state:
+      * allocated when the slab is bound, only when the switch is on;
+      * ``clean_state`` clears them; ``reset_streams`` clears the flags of the reset streams in its own launch (the matrices
+        stay: a clear flag makes the next frame a first frame, which overwrites them);
+      * the single-step peek ``forward_step(update_state=False)`` runs the pre-pass with ``update = 0`` (nothing is written);
+      * the snapshot of ``forward_steps(update_state=False)`` holds them."""
 
-    pre_normalization = False
-    _pn_joints = ZAXIS + XAXIS
+    name, what = "prenorm", "pre-normalisation"
+    def __init__(self, shape):
+        super().__init__(shape)
+        self.on, self.joints = False, ZAXIS + XAXIS
+        self.rot = None
 
-    def _set_pre_normalization(self, enabled, joints):
-        self.pre_normalization = bool(enabled)
-        self._pn_joints = joints
+    @property
+    def enabled(self):
+        return self.on
 
-    def _prenorm_clip(self, x):
-        if not self.pre_normalization:
+    @property
+    def settings(self):
+        return self.on, self.joints
+
+    def set(self, settings):
+        self.on, self.joints = settings
+
+    def stepped_with(self):
+        return f"with pre-normalisation {'on' if self.on else 'off'}"
+
+    def clip(self, x):
+        if not self.on:
             return x
         native.require_device_f32(x, "model input")
-        return pre_normalize_clip(x, self._pn_joints[:2], self._pn_joints[2:])
+        return pre_normalize_clip(x, self.joints[:2], self.joints[2:])
 
+    def bind(self, n, device, max_cycle):
+        _, _, v, m = self.shape
+        self.scratch = self.rot = self.flags = None
+        if self.on:
+            self.scratch = torch.empty((max_cycle, n, 3, v, m), device=device, dtype=torch.float32)
+            self.rot = torch.zeros((n, 18), device=device, dtype=torch.float64)
+            self.flags = torch.zeros((n,), device=device, dtype=torch.int32)
 
-class ContinualPreNorm(PreNorm):
-    """Base class of ``CoStGcn``: the step pre-pass and its state.  ``_pn_scratch`` [max_cycle](N, 3, V, M) takes the
-    normalised frames of a cycle (scratch); ``_pn_rot`` (N, 18) fp64, a stream's Rz then Rx, and ``_pn_flags`` (N,) int32,
-    "this stream has latched its rotations", are continual state:
-      * allocated when the slab is bound (``_bind``), only when the switch is on;
-      * ``clean_state`` clears the flags; ``reset_streams`` clears the flags of the reset streams in its own launch;
-      * the single-step peek ``forward_step(update_state=False)`` runs the pre-pass with ``update = 0`` (nothing is written);
-      * the snapshot of ``forward_steps(update_state=False)`` holds them (``_state_tensors``)."""
+    def state(self):
+        return [] if self.flags is None else [("pn_rot", self.rot), ("pn_flags", self.flags)]
 
-    _pn_scratch = _pn_rot = _pn_flags = None
+    def windows(self):
+        return [("pn_rot", 1, 36, 1), ("pn_flags", 1, 1, 1)] if self.on else []       # (18,) fp64 = 36 words
 
-    def _set_pre_normalization(self, enabled, joints):
-        if bool(enabled) == self.pre_normalization and joints == self._pn_joints:
-            return
-        if self._n is not None and self._frames != 0:
-            raise RuntimeError(f"the model has stepped {self._frames} frames with pre-normalisation "
-                               f"{'on' if self.pre_normalization else 'off'}: its rings hold features of that input; call "
-                               "clean_state() before changing the pre-normalisation")
-        super()._set_pre_normalization(enabled, joints)
-        if self._n is not None:
-            self._bind_prenorm(self._n, self._xin0.device)
+    def signature(self):
+        return [("pre_normalization", (int(self.on),) + tuple(self.joints))]
 
-    def _bind_prenorm(self, n, device):
-        _, _, v, m = self.input_shape
-        self._pn_scratch = self._pn_rot = self._pn_flags = None
-        if self.pre_normalization:
-            self._pn_scratch = torch.empty((self.max_cycle, n, 3, v, m), device=device, dtype=torch.float32)
-            self._pn_rot = torch.zeros((n, 18), device=device, dtype=torch.float64)
-            self._pn_flags = torch.zeros((n,), device=device, dtype=torch.int32)
+    def _latch(self, srcs, dsts, r, rot, flags, update, like):
+        n, _, v, m = like.shape
+        rc = native.lib().csk_prenorm_frames_f32(srcs, dsts, r, native.ptr(rot), native.ptr(flags), int(update), n, v, m,
+                                                 *self.joints, native.stream_of(like))
+        native.check(rc, "csk_prenorm_frames_f32")
 
-    def _clean_prenorm(self):
-        if self._pn_flags is not None:
-            self._pn_rot.zero_()
-            self._pn_flags.zero_()
+    def prime(self, x_in, t):
+        """The rotations a stream latches from its first frame, by the step entry itself (the bits of the steps)."""
+        if not self.on:
+            return {}
+        first, dev = x_in[:, :, 0].contiguous(), x_in.device
+        rot = torch.zeros((first.shape[0], 18), device=dev, dtype=torch.float64)
+        flags, sink = torch.zeros((first.shape[0],), device=dev, dtype=torch.int32), torch.empty(first.shape, device=dev)
+        self._latch(*frame_pointers([first], [sink]), 1, rot, flags, True, first)
+        return {"pn_rot": rot, "pn_flags": flags}
 
-    def _prenorm_tensors(self):
-        return [] if self._pn_flags is None else [self._pn_rot, self._pn_flags]
-
-    def _prenorm_state_bytes(self):
-        return sum(t.numel() * t.element_size() for t in self._prenorm_tensors())
-
-    def _prenorm_reset_jobs(self):
-        """Scrub job (co_reset.py) that clears the flags of the streams being reset: the flag array as a ring of one slot and
-        one row in which every stream owns one 4-byte element (the all-zero pattern is int32 0).  The matrices stay: a clear
-        flag makes the next frame a first frame, which overwrites them."""
-        if self._pn_flags is None:
-            return []
-        n = self._pn_flags.shape[0]
-        return [native.ScrubJob(self._pn_flags.data_ptr(), n, 1, 1, 0, 1, 1, native.SCRUB_BLOCK_RING)]
-
-    def _prenorm_frames(self, frames, update=True):
+    def frames(self, frames, update=True):
         """The cycle's raw joint frames -> the normalised frames (the list itself when the switch is off).  ``update=False``:
         the latched rotations and the flags stay as they are."""
-        if not self.pre_normalization:
+        if not self.on:
             return frames
-        r = len(frames)
-        n, _, v, m = frames[0].shape
-        out = [self._pn_scratch[i] for i in range(r)]
-        srcs = (ctypes.c_void_p * r)(*[x_t.data_ptr() for x_t in frames])
-        dsts = (ctypes.c_void_p * r)(*[o.data_ptr() for o in out])
-        rc = native.lib().csk_prenorm_frames_f32(srcs, dsts, r, native.ptr(self._pn_rot), native.ptr(self._pn_flags), int(update),
-                                                 n, v, m, *self._pn_joints, native.stream_of(frames[0]))
-        native.check(rc, "csk_prenorm_frames_f32")
+        out, srcs, dsts = self._into_scratch(frames)
+        self._latch(srcs, dsts, len(frames), self.rot, self.flags, update, frames[0])
         return out
 
 
@@ -149,20 +144,4 @@ def set_pre_normalization(model, enabled: bool = True, zaxis=ZAXIS, xaxis=XAXIS)
     the normalised joints.  ``ValueError`` for a model that does not take C = 3 channels or a joint index outside [0, V);
     a continual model that has stepped (frame counter not 0) raises ``RuntimeError``: ``clean_state()`` first.
     Returns ``model``."""
-    if isinstance(model, parallel.StreamShards):
-        checked = []
-        for shard in model.models:      # all validated before any is switched: the shards step in lock step
-            if not isinstance(shard, PreNorm):
-                raise TypeError(f"{type(shard).__name__} has no pre-normalisation")
-            joints = _check_model_shape(shard, zaxis, xaxis)
-            changes = bool(enabled) != shard.pre_normalization or joints != shard._pn_joints
-            if isinstance(shard, ContinualPreNorm) and changes and shard._n is not None and shard._frames:
-                raise RuntimeError("a shard has stepped: call clean_state() on every shard model before changing the pre-normalisation")
-            checked.append(joints)
-        for shard, joints in zip(model.models, checked):
-            shard._set_pre_normalization(enabled, joints)
-        return model
-    if not isinstance(model, PreNorm):
-        raise TypeError(f"{type(model).__name__} has no pre-normalisation (StGcn, CoStGcn, their siblings, or a StreamShards)")
-    model._set_pre_normalization(enabled, _check_model_shape(model, zaxis, xaxis))
-    return model
+    return switch_stage(model, "prenorm", PreNorm.what, lambda m, stage: (bool(enabled), _check_model_shape(m, zaxis, xaxis)))

@@ -186,7 +186,7 @@ def test_model_clip_as_steps_equals_the_steps(V, variant):
         pkg.set_input_modality(net, "bone_motion")
     if variant == "keypoints":
         pkg.keypoints.set_keypoint_intake(net)
-        x = torch.rand(net._keypoint_shape(2, 96), generator=g).to(DEV)
+        x = torch.rand(net.stage("keypoints").fed_shape(2, 96), generator=g).to(DEV)
     else:
         x = torch.rand(2, 3, 96, V, 2, generator=g).to(DEV)
     for pad_end in (False, True):

@@ -296,7 +296,7 @@ def test_stepping_on_keypoint_frames_equals_the_twin_stepped_on_the_selected_fra
     assert len(mine) == len(theirs) and all(torch.equal(a, b) for a, b in zip(mine, theirs))       # no state of its own
     assert net.state_bytes() == twin.state_bytes() and net.move_signature() == twin.move_signature()
     assert net.scratch_bytes() - twin.scratch_bytes() == 4 * net.max_cycle * N * 3 * 18 * 2
-    assert net._kp_scratch.shape == (net.max_cycle, N, 3, 18, 2) and twin._kp_scratch is None
+    assert net.stage("keypoints").scratch.shape == (net.max_cycle, N, 3, 18, 2) and twin.stage("keypoints").scratch is None
     with pytest.raises(RuntimeError, match=r"clean_state\(\)"):
         keypoints.set_keypoint_intake(net, enabled=False)
     with pytest.raises(RuntimeError, match="does not match"):
@@ -354,7 +354,7 @@ def test_stream_shards_with_the_switch_on():
         if want is not None:
             assert torch.equal(got, want), t
             n_pred += 1
-    assert n_pred == 4 and [m._kp_scratch.shape[1] for m in shards.models] == [3, 2]
+    assert n_pred == 4 and [m.stage("keypoints").scratch.shape[1] for m in shards.models] == [3, 2]
     assert shards.scratch_bytes() - twin.scratch_bytes() == 4 * 8 * N * 3 * 18 * 2
 
 
@@ -400,13 +400,13 @@ def test_the_switch_is_off_by_default_and_then_nothing_is_allocated_or_launched(
     assert keypoints.set_keypoint_intake(net, enabled=False) is net and net.keypoint_intake is False
     _, selected = _sequence(21)
     cyc = [selected[0], selected[1], selected[2], selected[3]]
-    assert _same(_predictions(net, selected, 4, 0, 8), _predictions(plain, selected, 4, 0, 8)) and net._intake_frames(cyc) is cyc
-    assert net._kp_scratch is None and net.scratch_bytes() == plain.scratch_bytes()
+    assert _same(_predictions(net, selected, 4, 0, 8), _predictions(plain, selected, 4, 0, 8)) and net.stage("keypoints").frames(cyc) is cyc
+    assert net.stage("keypoints").scratch is None and net.scratch_bytes() == plain.scratch_bytes()
     x = selected[:20].permute(1, 2, 0, 3, 4).contiguous()
     assert net._intake_clip(x) is x
     before = net.scratch_bytes()
     net.clean_state()
     keypoints.set_keypoint_intake(net)                  # a bound slab that has not stepped takes the switch and binds its scratch
-    assert net._kp_scratch.shape == (net.max_cycle, N, 3, 18, 2) and net.scratch_bytes() - before == 4 * net.max_cycle * N * 3 * 18 * 2
+    assert net.stage("keypoints").scratch.shape == (net.max_cycle, N, 3, 18, 2) and net.scratch_bytes() - before == 4 * net.max_cycle * N * 3 * 18 * 2
     keypoints.set_keypoint_intake(net, enabled=False)
-    assert net._kp_scratch is None and net.scratch_bytes() == before
+    assert net.stage("keypoints").scratch is None and net.scratch_bytes() == before

@@ -276,9 +276,9 @@ def test_stepping_on_joints_equals_the_twin_stepped_on_host_derived_frames(nativ
     got, want = _predictions(net, x.to(DEV), r), _predictions(twin, der[kind].to(DEV), r)
     assert len(want) == 4 and _same(got, want)
     assert (net.__dict__.get("_plan") is not None) == native_plan
-    assert (net._mod_prev is not None) == (kind != "bone") and net._mod_scratch is not None and twin._mod_scratch is None
+    assert (net.stage("modality").prev is not None) == (kind != "bone") and net.stage("modality").scratch is not None and twin.stage("modality").scratch is None
     if kind != "bone":
-        assert torch.equal(net._mod_prev, x[-1].to(DEV)) and bool(net._mod_flags.all())
+        assert torch.equal(net.stage("modality").prev, x[-1].to(DEV)) and bool(net.stage("modality").flags.all())
 
 
 @pytest.mark.parametrize("model,v,native_plan,r", [("CoAGcn", 25, True, 1), ("CoSTr", 25, False, 4)])
@@ -308,13 +308,13 @@ def test_peeks_leave_every_later_prediction_unchanged(native_plan, kind):
     for t in range(T_SEQ):
         p1 = None
         if t in (0, 1, 37, 80, 84, 85):
-            keep = [s.clone() for s in peeker._modality_tensors()] if t else None
+            keep = [s.clone() for s in [t for _, t in peeker.stage("modality").state()]] if t else None
             p1 = peeker.forward_step(frames[t], update_state=False)
             if t in (37, 80):
                 ahead = peeker.forward_steps(frames[t:t + 8].permute(1, 2, 0, 3, 4).contiguous(), update_state=False)
                 assert ahead.shape[2] == (2 if t == 80 else 0)
             if keep:
-                assert all(torch.equal(a, b) for a, b in zip(peeker._modality_tensors(), keep)), t
+                assert all(torch.equal(a, b) for a, b in zip([t for _, t in peeker.stage("modality").state()], keep)), t
         got, want = peeker.forward_step(frames[t]), twin.forward_step(frames[t])
         assert (got is None) == (want is None), t
         if want is not None:
@@ -323,7 +323,7 @@ def test_peeks_leave_every_later_prediction_unchanged(native_plan, kind):
             if t in (80, 84):
                 assert torch.equal(p1, want), t
     assert n_pred == 4 and all(torch.equal(a, b) for a, b in zip(peeker._state_tensors(), twin._state_tensors()))
-    assert sum(s is peeker._mod_prev or s is peeker._mod_flags for s in peeker._state_tensors()) == 2
+    assert sum(s is peeker.stage("modality").prev or s is peeker.stage("modality").flags for s in peeker._state_tensors()) == 2
 
 
 # ---- 8. resets
@@ -343,7 +343,7 @@ def test_reset_stream_is_a_fresh_model_and_its_neighbours_run_on(native_plan, r)
     head, head_plain = _predictions(slab, frames, 4, 0, 80), _predictions(plain, frames, 4, 0, 80)
     assert _same(head, head_plain) and not head
     slab.reset_streams([1])
-    assert slab._mod_flags.tolist() == [1, 0, 1]
+    assert slab.stage("modality").flags.tolist() == [1, 0, 1]
     got, want_plain = _predictions(slab, frames, r, 80), _predictions(plain, frames, r, 80)
     want_fresh = _predictions(fresh, frames, r, 80, rows=[1])
     assert len(got) == len(want_plain) == 24 and len(want_fresh) == 4
@@ -353,7 +353,7 @@ def test_reset_stream_is_a_fresh_model_and_its_neighbours_run_on(native_plan, r)
     assert all(t == tf and torch.equal(a[1], b[0]) for (t, a), (tf, b) in zip(tail, want_fresh))
     assert any(not torch.equal(a[1], b[1]) for (_, a), (_, b) in zip(tail, want_plain[-len(tail):]))
     slab.clean_state()
-    assert not slab._mod_flags.any() and not slab._mod_prev.any()
+    assert not slab.stage("modality").flags.any() and not slab.stage("modality").prev.any()
     second = frames[60:156]
     assert _same(_predictions(slab, second, r), _predictions(fresh2, second, r))
 
@@ -367,23 +367,23 @@ def test_joint_modality_is_the_untouched_model_and_allocates_nothing():
     got, want = _predictions(net, frames, 4), _predictions(plain, frames, 4)
     assert len(want) == 4 and _same(got, want)
     for m in (net, plain):
-        assert m._mod_scratch is None and m._mod_prev is None and m._mod_flags is None and m._modality_tensors() == []
-        assert m._modality_reset_jobs() == []
+        assert m.stage("modality").scratch is None and m.stage("modality").prev is None and m.stage("modality").flags is None and [t for _, t in m.stage("modality").state()] == []
+        assert m.stage("modality").reset_jobs() == []
     cyc = [frames[0], frames[1]]
-    assert net._derive_frames(cyc) is cyc                   # the cycle's own list: no launch
+    assert net.stage("modality").frames(cyc) is cyc                   # the cycle's own list: no launch
     clip, clip_plain = _twins(pkg.StGcn, 25, 2, shape_t=20)
     pkg.set_input_modality(clip, "joint")
     xc = _joints((2, 3, 20, 25, 2), 11).to(DEV)
     with torch.no_grad():
-        assert torch.equal(clip(xc), clip_plain(xc)) and clip._derive_clip(xc) is xc
+        assert torch.equal(clip(xc), clip_plain(xc)) and clip.stage("modality").clip(xc) is xc
     # a bound model that has stepped refuses the change and names the way out; after clean_state() it takes it
     with pytest.raises(RuntimeError, match=r"clean_state\(\)"):
         pkg.set_input_modality(net, "bone")
     net.clean_state()
     pkg.set_input_modality(net, "bone_motion")
-    assert net._mod_prev is not None and net._mod_prev.shape == (N, 3, 25, 2) and net._mod_flags.dtype == torch.int32
+    assert net.stage("modality").prev is not None and net.stage("modality").prev.shape == (N, 3, 25, 2) and net.stage("modality").flags.dtype == torch.int32
     pkg.set_input_modality(net, "bone")
-    assert net._mod_prev is None and net._mod_flags is None and net._mod_scratch is not None
+    assert net.stage("modality").prev is None and net.stage("modality").flags is None and net.stage("modality").scratch is not None
 
 
 # ---- 10. the ensemble

@@ -240,7 +240,7 @@ def test_with_pre_normalisation_the_pre_pass_is_the_references_pipeline(golden, 
     bodies = torch.from_numpy(golden[f"{case}/bodies"])[None].to(DEV)
     padded = net._intake_clip(bodies)
     assert torch.equal(padded[0].cpu(), torch.from_numpy(golden[f"{case}/want_padded"]))
-    got = net._prenorm_clip(padded)
+    got = net.stage("prenorm").clip(padded)
     check_parity(got[0].cpu(), torch.from_numpy(golden[f"{case}/want_final"]), tol=1e-5, ref_cap=8.0, tag=case,
                  what="NTU intake + pre_normalize_clip vs read_xyz + pre_normalization")
 

@@ -292,13 +292,13 @@ def test_stepping_on_raw_frames_equals_the_twin_stepped_on_the_clip_form(native_
     theirs = twin._state_tensors()
     assert all(torch.equal(a, b) for a, b in zip(net._state_tensors()[:len(theirs)], theirs))
     mine = net._state_tensors()[len(theirs):]
-    assert len(mine) == 2 and mine[0] is net._pn_rot and mine[1] is net._pn_flags and bool(net._pn_flags.all())
+    assert len(mine) == 2 and mine[0] is net.stage("prenorm").rot and mine[1] is net.stage("prenorm").flags and bool(net.stage("prenorm").flags.all())
     cyc = [raw[0], raw[1]]
-    assert twin._pn_scratch is None and twin._pn_rot is None and twin._prenorm_reset_jobs() == [] and twin._prenorm_frames(cyc) is cyc
+    assert twin.stage("prenorm").scratch is None and twin.stage("prenorm").rot is None and twin.stage("prenorm").reset_jobs() == [] and twin.stage("prenorm").frames(cyc) is cyc
     assert net.state_bytes() - twin.state_bytes() == N * (18 * 8 + 4)
     assert net.scratch_bytes() - twin.scratch_bytes() == 4 * net.max_cycle * N * 3 * 25 * 2
     if modality != "joint":
-        assert torch.equal(net._mod_prev, normed[-1])
+        assert torch.equal(net.stage("modality").prev, normed[-1])
     with pytest.raises(RuntimeError, match=r"clean_state\(\)"):
         pkg.set_pre_normalization(net, False)
 
@@ -318,7 +318,7 @@ def test_stream_shards_with_the_switch_on():
         if want is not None:
             assert torch.equal(got, want), t
             n_pred += 1
-    assert n_pred == 4 and [m._pn_flags.shape[0] for m in shards.models] == [3, 2]
+    assert n_pred == 4 and [m.stage("prenorm").flags.shape[0] for m in shards.models] == [3, 2]
 
 
 # ---- state contracts
@@ -330,19 +330,19 @@ def test_peeks_do_not_latch_and_snapshots_restore(native_plan):
         pkg.set_pre_normalization(net)
     raw, _ = _sequence(21)
     assert peeker.forward_step(raw[5], update_state=False) is None          # a peek on a fresh slab: binds, does not latch
-    assert not peeker._pn_flags.any() and not peeker._pn_rot.any()
+    assert not peeker.stage("prenorm").flags.any() and not peeker.stage("prenorm").rot.any()
     ahead = peeker.forward_steps(raw[8:16].permute(1, 2, 0, 3, 4).contiguous(), update_state=False)
-    assert ahead.shape[2] == 0 and not peeker._pn_flags.any() and not peeker._pn_rot.any()
+    assert ahead.shape[2] == 0 and not peeker.stage("prenorm").flags.any() and not peeker.stage("prenorm").rot.any()
     n_pred = 0
     for t in range(T_SEQ):
         p1 = None
         if t in (1, 37, 80, 84):
-            keep = [s.clone() for s in peeker._prenorm_tensors()]
+            keep = [s.clone() for s in [t for _, t in peeker.stage("prenorm").state()]]
             p1 = peeker.forward_step(raw[t], update_state=False)
             if t in (37, 80):
                 ahead = peeker.forward_steps(raw[t:t + 8].permute(1, 2, 0, 3, 4).contiguous(), update_state=False)
                 assert ahead.shape[2] == (2 if t == 80 else 0)
-            assert all(torch.equal(a, b) for a, b in zip(peeker._prenorm_tensors(), keep)) and bool(peeker._pn_flags.all()), t
+            assert all(torch.equal(a, b) for a, b in zip([t for _, t in peeker.stage("prenorm").state()], keep)) and bool(peeker.stage("prenorm").flags.all()), t
         got, want = peeker.forward_step(raw[t]), twin.forward_step(raw[t])
         assert (got is None) == (want is None), t
         if want is not None:
@@ -362,9 +362,9 @@ def test_reset_streams_and_clean_state_make_the_next_frame_a_first_frame():
         pkg.set_pre_normalization(net)
     raw, _ = _sequence(22, t=176)
     assert _same(_predictions(slab, raw, 4, 0, 80), _predictions(plain, raw, 4, 0, 80))
-    rot_before = slab._pn_rot.clone()
+    rot_before = slab.stage("prenorm").rot.clone()
     slab.reset_streams([1, 3])
-    assert slab._pn_flags.tolist() == [1, 0, 1, 0, 1] and torch.equal(slab._pn_rot, rot_before)
+    assert slab.stage("prenorm").flags.tolist() == [1, 0, 1, 0, 1] and torch.equal(slab.stage("prenorm").rot, rot_before)
     got, want_plain = _predictions(slab, raw, 4, 80), _predictions(plain, raw, 4, 80)
     want_fresh = _predictions(fresh, raw, 4, 80, rows=[1, 3])
     assert len(got) == len(want_plain) == 24 and len(want_fresh) == 4
@@ -373,9 +373,9 @@ def test_reset_streams_and_clean_state_make_the_next_frame_a_first_frame():
     tail = got[-len(want_fresh):]
     assert all(t == tf and torch.equal(a[[1, 3]], b) for (t, a), (tf, b) in zip(tail, want_fresh))
     assert any(not torch.equal(a[[1, 3]], b[[1, 3]]) for (_, a), (_, b) in zip(tail, want_plain[-len(tail):]))
-    assert torch.equal(slab._pn_rot[[1, 3]], fresh._pn_rot) and torch.equal(slab._pn_rot[[0, 2, 4]], plain._pn_rot[[0, 2, 4]])
+    assert torch.equal(slab.stage("prenorm").rot[[1, 3]], fresh.stage("prenorm").rot) and torch.equal(slab.stage("prenorm").rot[[0, 2, 4]], plain.stage("prenorm").rot[[0, 2, 4]])
     slab.clean_state()
-    assert not slab._pn_flags.any()
+    assert not slab.stage("prenorm").flags.any()
     second = raw[60:156]
     assert _same(_predictions(slab, second, 4), _predictions(fresh2, second, 4))
 
@@ -385,13 +385,13 @@ def test_the_switch_is_off_by_default_and_then_nothing_is_allocated_or_launched(
     assert pkg.set_pre_normalization(net, False) is net
     raw, _ = _sequence(21)
     cyc = [raw[0], raw[1], raw[2], raw[3]]
-    assert _same(_predictions(net, raw, 4, 0, 8), _predictions(plain, raw, 4, 0, 8)) and net._prenorm_frames(cyc) is cyc
-    assert net._pn_scratch is None and net._pn_rot is None and net._pn_flags is None and net._prenorm_tensors() == []
+    assert _same(_predictions(net, raw, 4, 0, 8), _predictions(plain, raw, 4, 0, 8)) and net.stage("prenorm").frames(cyc) is cyc
+    assert net.stage("prenorm").scratch is None and net.stage("prenorm").rot is None and net.stage("prenorm").flags is None and [t for _, t in net.stage("prenorm").state()] == []
     x = raw[:20].permute(1, 2, 0, 3, 4).contiguous()
-    assert net._prenorm_clip(x) is x
+    assert net.stage("prenorm").clip(x) is x
     net.clean_state()
     pkg.set_pre_normalization(net)                      # a bound slab that has not stepped takes the switch and binds its state
-    assert net._pn_rot.shape == (N, 18) and net._pn_rot.dtype == torch.float64 and net._pn_flags.dtype == torch.int32
-    assert net._pn_scratch.shape == (net.max_cycle, N, 3, 25, 2)
+    assert net.stage("prenorm").rot.shape == (N, 18) and net.stage("prenorm").rot.dtype == torch.float64 and net.stage("prenorm").flags.dtype == torch.int32
+    assert net.stage("prenorm").scratch.shape == (net.max_cycle, N, 3, 25, 2)
     pkg.set_pre_normalization(net, False)
-    assert net._pn_rot is None and net._pn_scratch is None
+    assert net.stage("prenorm").rot is None and net.stage("prenorm").scratch is None

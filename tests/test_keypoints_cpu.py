@@ -167,14 +167,14 @@ def test_set_keypoint_intake_host_rules():
     for net in _models():
         assert net.keypoint_intake is False and "keypoint_intake" not in net.__dict__           # the class attribute says so
         assert not [k for k in net.__dict__ if k.startswith("_kp")]
-        assert keypoints.set_keypoint_intake(net) is net and net.keypoint_intake is True and net._kp_people == 5
-        assert keypoints.set_keypoint_intake(net, 8) is net and net._kp_people == 8
-        assert keypoints.set_keypoint_intake(net, people_in=2) is net and net._kp_people == 2
+        assert keypoints.set_keypoint_intake(net) is net and net.keypoint_intake is True and net.stage("keypoints").people == 5
+        assert keypoints.set_keypoint_intake(net, 8) is net and net.stage("keypoints").people == 8
+        assert keypoints.set_keypoint_intake(net, people_in=2) is net and net.stage("keypoints").people == 2
         for bad in (1, 9, 0, -1, 2.0, None, True):
             with pytest.raises(ValueError, match="people_in"):
                 keypoints.set_keypoint_intake(net, bad)
-        assert net._kp_people == 2 and net._keypoint_shape(7) == (7, 2, net.input_shape[2], 3)
-        assert net._keypoint_shape(7, 4) == (7, 4, 2, net.input_shape[2], 3)
+        assert net.stage("keypoints").people == 2 and net.stage("keypoints").fed_shape(7) == (7, 2, net.input_shape[2], 3)
+        assert net.stage("keypoints").fed_shape(7, 4) == (7, 4, 2, net.input_shape[2], 3)
         assert keypoints.set_keypoint_intake(net, enabled=False) is net and net.keypoint_intake is False
     for cls in (pkg.StGcn, pkg.CoStGcn):
         with pytest.raises(ValueError, match="C = 2"):
@@ -198,7 +198,7 @@ def _stepped(frames):
     net = pkg.CoStGcn(pkg.kinetics_graph().A, (3, 300, 18, 2))
     net._ctr = (ctypes.c_int64 * 22)()
     net._n, net._xin0 = 2, types.SimpleNamespace(device="cpu")     # stands for a bound slab (binding needs a device)
-    net._bind_intake = lambda n, device: None
+    net.stage("keypoints").bind = lambda n, device, max_cycle: None
     net._frames = frames
     return net
 
@@ -211,7 +211,7 @@ def test_a_model_that_has_stepped_refuses_the_switch():
     for change in (dict(enabled=False), dict(people_in=6)):
         with pytest.raises(RuntimeError, match=r"clean_state\(\)"):
             keypoints.set_keypoint_intake(net, **change)
-    assert net.keypoint_intake is True and net._kp_people == 5
+    assert net.keypoint_intake is True and net.stage("keypoints").people == 5
 
 
 def test_stream_shards_validate_every_shard_before_switching_any():
@@ -231,7 +231,7 @@ def test_stream_shards_validate_every_shard_before_switching_any():
         keypoints.set_keypoint_intake(shards, 9)
     assert shards.models[0].keypoint_intake is False
     assert keypoints.set_keypoint_intake(shards, 6) is shards
-    assert [(m.keypoint_intake, m._kp_people) for m in shards.models] == [(True, 6)] * 2
+    assert [(m.keypoint_intake, m.stage("keypoints").people) for m in shards.models] == [(True, 6)] * 2
 
 
 def test_cpu_tensors_and_wrong_shapes_are_refused_on_the_host():

@@ -119,7 +119,7 @@ def test_a_model_that_has_stepped_refuses_a_change_of_modality():
     net = pkg.CoStGcn(pkg.ntu_graph().A)
     net._ctr = (ctypes.c_int64 * 22)()
     net._n, net._xin0 = 2, types.SimpleNamespace(device="cpu")     # stands for a bound slab (binding needs a device)
-    net._bind_modality = lambda n, device: None
+    net.stage("modality").bind = lambda n, device, max_cycle: None
     pkg.set_input_modality(net, "bone")                      # frame counter 0: allowed
     net._frames = 8
     pkg.set_input_modality(net, "bone")                      # no change: allowed

@@ -148,13 +148,13 @@ def test_set_ntu_intake_host_rules():
     for net in _clip_models():
         assert net.ntu_intake is False and "ntu_intake" not in net.__dict__            # the class attribute says so
         assert not [k for k in net.__dict__ if k.startswith("_ntu")]
-        assert ntu_intake.set_ntu_intake(net) is net and net.ntu_intake is True and net._ntu_bodies == 4
-        assert ntu_intake.set_ntu_intake(net, bodies_in=8) is net and net._ntu_bodies == 8
-        assert ntu_intake.set_ntu_intake(net, True, 2) is net and net._ntu_bodies == 2
+        assert ntu_intake.set_ntu_intake(net) is net and net.ntu_intake is True and net.stage("ntu").bodies == 4
+        assert ntu_intake.set_ntu_intake(net, bodies_in=8) is net and net.stage("ntu").bodies == 8
+        assert ntu_intake.set_ntu_intake(net, True, 2) is net and net.stage("ntu").bodies == 2
         for bad in (1, 9, 0, -1, 2.0, None, True):
             with pytest.raises(ValueError, match="bodies_in"):
                 ntu_intake.set_ntu_intake(net, bodies_in=bad)
-        assert net._ntu_bodies == 2 and net.ntu_intake is True
+        assert net.stage("ntu").bodies == 2 and net.ntu_intake is True
         assert ntu_intake.set_ntu_intake(net, enabled=False) is net and net.ntu_intake is False
     with pytest.raises(ValueError, match="C = 2"):
         ntu_intake.set_ntu_intake(pkg.StGcn(pkg.ntu_graph().A, (2, 300, 25, 2)))

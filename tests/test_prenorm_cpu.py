@@ -179,12 +179,12 @@ def test_set_pre_normalization_host_rules():
         v = net.input_shape[2]
         assert net.pre_normalization is False and "pre_normalization" not in net.__dict__       # the class attribute says so
         assert not [k for k in net.__dict__ if k.startswith("_pn")]
-        assert pkg.set_pre_normalization(net) is net and net.pre_normalization is True and net._pn_joints == (0, 1, 8, 4)
-        assert pkg.set_pre_normalization(net, True, zaxis=(2, 3), xaxis=[v - 1, 0]) is net and net._pn_joints == (2, 3, v - 1, 0)
+        assert pkg.set_pre_normalization(net) is net and net.pre_normalization is True and net.stage("prenorm").joints == (0, 1, 8, 4)
+        assert pkg.set_pre_normalization(net, True, zaxis=(2, 3), xaxis=[v - 1, 0]) is net and net.stage("prenorm").joints == (2, 3, v - 1, 0)
         for bad in (dict(zaxis=(0, v)), dict(xaxis=(-1, 4)), dict(zaxis=(0,)), dict(xaxis=(1.0, 2)), dict(zaxis=None)):
             with pytest.raises(ValueError):
                 pkg.set_pre_normalization(net, True, **bad)
-        assert net._pn_joints == (2, 3, v - 1, 0)
+        assert net.stage("prenorm").joints == (2, 3, v - 1, 0)
         assert pkg.set_pre_normalization(net, False) is net and net.pre_normalization is False
     for cls in (pkg.StGcn, pkg.CoStGcn):
         with pytest.raises(ValueError, match="C = 2"):
@@ -201,7 +201,7 @@ def _stepped(frames):
     net = pkg.CoStGcn(pkg.ntu_graph().A)
     net._ctr = (ctypes.c_int64 * 22)()
     net._n, net._xin0 = 2, types.SimpleNamespace(device="cpu")     # stands for a bound slab (binding needs a device)
-    net._bind_prenorm = lambda n, device: None
+    net.stage("prenorm").bind = lambda n, device, max_cycle: None
     net._frames = frames
     return net
 
@@ -215,7 +215,7 @@ def test_a_model_that_has_stepped_refuses_the_switch():
     for change in (dict(enabled=False), dict(zaxis=(1, 0))):
         with pytest.raises(RuntimeError, match=r"clean_state\(\)"):
             pkg.set_pre_normalization(net, **change)
-    assert net.pre_normalization is True and net._pn_joints == (0, 1, 8, 4)
+    assert net.pre_normalization is True and net.stage("prenorm").joints == (0, 1, 8, 4)
 
 
 def test_stream_shards_validate_every_shard_before_switching_any():
@@ -235,4 +235,4 @@ def test_stream_shards_validate_every_shard_before_switching_any():
     assert shards.models[0].pre_normalization is False
     shards.models = [_stepped(0), _stepped(0)]
     assert pkg.set_pre_normalization(shards, xaxis=(9, 5)) is shards
-    assert [(m.pre_normalization, m._pn_joints) for m in shards.models] == [(True, (0, 1, 9, 5))] * 2
+    assert [(m.pre_normalization, m.stage("prenorm").joints) for m in shards.models] == [(True, (0, 1, 9, 5))] * 2
