@@ -69,6 +69,22 @@ def _report_path():
     return os.path.join(d, "parity_report.jsonl")
 
 
+def append_report(name, **record):
+    """one JSON line appended to the side file ``name`` beside the parity report; False where no report can be written (a
+    read-only tree) -- evidence for people, never an assertion"""
+    import json
+
+    report = _report_path()
+    if not report:
+        return False
+    try:
+        with open(os.path.join(os.path.dirname(report), name), "a") as f:
+            f.write(json.dumps(record) + "\n")
+    except OSError:
+        return False
+    return True
+
+
 def check_parity(got, want, tol=TOL, ref_cap=REF_CAP, **info):
     """assert max |got - want| <= tol (absolute) and |want| <= ref_cap; record the achieved error."""
     import json

@@ -51,3 +51,30 @@ def test_fusion_errors():
         pkg.fusion.aggregate_preds([a] * 5)
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         pkg.fusion.aggregate_preds([a.cpu()])
+
+
+def _tie_cases():
+    from tests import nan_cone_fixture as fx
+    return fx.TIE_CASES
+
+
+@pytest.mark.parametrize("case", _tie_cases(), ids=lambda c: c.id)
+def test_fusion_rank_with_ties(case):
+    """Integer-valued logits in [-2, 2]: classes tie with the target all the time (tests/test_nan_cone_fixture_cpu.py: in at least
+    half the samples), so "a class outranks the target only when it scores STRICTLY higher" decides the rank.  N no multiple of 4,
+    60 and 400 classes, targets at class 0 and at the last class; fused values, rank and top-1/3/5 exactly the definition's."""
+    from tests import nan_cone_fixture as fx
+    preds, targets = fx.tie_operands(case)
+    fused, rank, accs = fx.tie_reference(case, preds, targets)
+    assert fx.tie_fraction(fused, targets) >= 0.5
+    dev = [torch.from_numpy(p).to(DEV) for p in preds]
+    got_fused, got_rank = pkg.fusion._launch(dev, case.method, targets=targets)
+    assert np.array_equal(got_fused.cpu().numpy(), fused)
+    assert np.array_equal(got_rank.cpu().numpy().astype(np.int64), rank)
+    # hit counts from integer data: the device's ranks give exactly the definition's counts, and the definition's accuracies are
+    # those counts over n (one fp64 division)
+    hits = [int((got_rank.cpu().numpy().astype(np.int64) < k).sum()) for k in (1, 3, 5)]
+    assert hits == [int((rank < k).sum()) for k in (1, 3, 5)] and accs == [h / case.n for h in hits]
+    # the package forms its mean on the device in fp32: the same expression on the definition's ranks, same device, bit for bit
+    want_accs = [float((torch.from_numpy(rank).to(DEV) < k).float().mean()) for k in (1, 3, 5)]
+    assert pkg.fusion.topk_accuracies(dev, targets, (1, 3, 5), case.method) == want_accs
