@@ -3,9 +3,7 @@ launches can still read into a packed, position-independent record, ``import_str
 positions of another slab (other stream count, other ring depths, other frame count), ``resize_streams`` re-binds a slab for
 another stream count and carries the kept streams over.  One launch of csk_co_move_streams_f32 each way (csrc/stream_move.hip).
 
-What a future launch can read of a ring ("window"), from the blocks: the (k-1)/2 newest frames of a block's input ring (the
-residual lag of ``engine_advance``), the k-1 newest frames of its post-GCN ring (the temporal conv's window), nothing of the
-last block's output ring (the head has consumed it) and the whole pooling window.  A frame s lives in slot s % depth of its
+What a future launch can read of a ring is its "window" in the slab's one ring inventory (co_rings.py).  A frame s lives in slot s % depth of its
 ring, so the window of a ring that has received ``count`` frames is the slots of frames count - window .. count - 1: the
 export reads them at the source's (count, depth), the import writes them at the target's.  The summation order of no kernel
 depends on the slab (``_pick_ksplit``, ``_use_split_step``), so the stream's results continue bit for bit."""
@@ -14,20 +12,7 @@ import ctypes
 import torch
 
 from . import native
-
-
-def ring_window(count: int, depth: int, window: int):
-    """(newest, window) as ``csk_move_job`` takes them, for a ring of ``depth`` slots that has received ``count`` frames:
-    the slot of frame count - 1 and how many newest slots move."""
-    if not 0 <= window <= depth:
-        raise ValueError(f"a window of {window} slots in a ring of {depth}")
-    return (count - 1) % depth, window
-
-
-def window_slots(newest: int, depth: int, window: int):
-    """The slots a job (newest, window) covers in a ring of ``depth`` slots, OLDEST first: the order of the packed record
-    (the arithmetic of csk_co_move_streams_f32)."""
-    return [(newest + 1 - window + i) % depth for i in range(window)]
+from .co_rings import array_ring, move_job, ring_window, window_slots  # noqa: F401  (the window arithmetic is read from here too)
 
 
 class StreamState:
@@ -53,18 +38,29 @@ class StreamState:
 torch.serialization.add_safe_globals([StreamState])     # torch.load(weights_only=True) rebuilds it: tensors, tuples, ints, strings
 
 
-def _check_indices(what, indices, n):
-    """The rule and the wording of ``StreamReset._check_reset``."""
+def _index_list(what, indices):
+    """The stream indices ``what`` was handed as a list of ints; anything else is refused."""
     if isinstance(indices, torch.Tensor) or not isinstance(indices, (list, tuple, range)):
         raise ValueError(f"{what} takes a sequence of ints (a list, tuple or range), not a tensor: the indices are "
                          "host-side bookkeeping and reading a device tensor would cost a sync")
     idx = list(indices)
     if any(isinstance(i, bool) or not isinstance(i, int) for i in idx):
         raise ValueError(f"{what} takes ints, got {[type(i).__name__ for i in idx]}")
+    return idx
+
+
+def _distinct_in_range(idx, n):
     if len(set(idx)) != len(idx):
         raise ValueError(f"duplicate stream indices in {idx}")
     if n is not None and any(not 0 <= i < n for i in idx):
         raise ValueError(f"stream indices {idx} outside a slab of {n} streams")
+
+
+def _check_indices(what, indices, n):
+    """THE rule for stream indices: a list, tuple or range of distinct ints inside the slab (``n`` None: no slab yet).
+    ``reset_streams`` makes the two halves around its own refusals (``StreamReset._check_reset``)."""
+    idx = _index_list(what, indices)
+    _distinct_in_range(idx, n)
     return idx
 
 
@@ -98,21 +94,11 @@ class StreamMove:
                 ("step_precision", tuple("bf16x3" if b._use_split_step() else "f32" for b in blks)))
 
     def _move_windows(self):
-        """[(name, rows, seg, window)] in record order, from the blocks alone (no slab needed): block i reads the
-        (k_i - 1) / 2 newest frames of its input ring and the k_i - 1 newest of its post-GCN ring; the last block's output
-        ring is not state; then the pooling window (one row of C_out floats per entry) and the small per-stream states as
-        arrays of 32-bit words with a window of one."""
-        c, _, v, m = self.input_shape
-        mv, blks = m * v, self._blocks
-        out = [("xin0", c, mv, (blks[0].kernel_size - 1) // 2)]
-        for i, blk in enumerate(blks):
-            out.append((f"y{i}", blk.out_channels, mv, blk.kernel_size - 1))
-            if i + 1 < len(blks):
-                out.append((f"out{i}", blk.out_channels, mv, (blks[i + 1].kernel_size - 1) // 2))
-        out.append(("pool", 1, blks[-1].out_channels, self.pool_size))
-        for stage in self._record_stages:               # the input pre-passes (input_stage.py)
-            out += stage.windows()
-        return out
+        """[(name, rows, seg, window)] in record order, from the blocks alone (no slab needed): the rings of the inventory
+        that have a window (co_rings.py: ``_rings``), then the small per-stream states of the input pre-passes as arrays of
+        32-bit words with a window of one (input_stage.py)."""
+        return ([(ring.name, ring.rows, ring.seg, ring.window) for ring in self._record_rings()]
+                + [entry for stage in self._record_stages for entry in stage.windows()])
 
     def record_floats(self):
         """32-bit words of one stream's record: the sum of the windows."""
@@ -120,25 +106,16 @@ class StreamMove:
 
     def _move_jobs(self):
         """The job list of this slab at its present position: the windows above, each with its tensor, the slot of its
-        newest frame (from the counter that owns the ring) and its offset in the record."""
-        rings = {"xin0": (self._xin0, self._frames)}
-        for i, st in enumerate(blk._state for blk in self._blocks):
-            rings[f"y{i}"], rings[f"out{i}"] = (st.y, st.s), (st.out, st.e)
-        arrays = dict(pair for stage in self._record_stages for pair in stage.state())
+        newest frame (from the counter that owns the ring; a per-stream array is one slot that holds its one frame) and its
+        offset in the record."""
+        counters = self._counters()
+        entries = [(ring, counters[ring.counter]) for ring in self._record_rings()]
+        entries += [(array_ring(entry, tensor), 1) for stage in self._record_stages
+                    for entry, (_, tensor) in zip(stage.windows(), stage.state())]
         jobs, offset = [], 0
-        for name, rows, seg, window in self._move_windows():
-            if name == "pool":                          # [pool_size][N][C]: stream n owns row n of every entry
-                t, kind = self._pool_ring, native.SCRUB_POOL_RING
-                (depth, n_rows, row_floats), count = t.shape, self._feats
-            elif name in rings:                         # [depth][C][P]: stream n owns seg floats of every row
-                (t, count), kind = rings[name], native.SCRUB_BLOCK_RING
-                depth, n_rows, row_floats = t.shape
-            else:                                       # a per-stream array: one slot, one row, seg words per stream
-                t, kind, count = arrays[name], native.SCRUB_BLOCK_RING, 1
-                depth, n_rows, row_floats = 1, 1, t.numel() * t.element_size() // 4
-            newest, window = ring_window(count, depth, window)
-            jobs.append(native.MoveJob(t.data_ptr(), row_floats, offset, depth, n_rows, newest, window, seg, kind))
-            offset += rows * seg * window
+        for ring, count in entries:
+            jobs.append(move_job(ring, count, offset))
+            offset += ring.rows * ring.seg * ring.window
         return jobs, offset
 
     def _move(self, packed, dev_idx, count, to_ring):

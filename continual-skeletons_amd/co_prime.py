@@ -14,7 +14,7 @@ import ctypes
 
 import torch
 
-from . import native
+from . import co_rings, native
 from .blocks import SpatioTemporalBlock
 from .co_migrate import StreamState
 
@@ -49,25 +49,13 @@ class StreamPrime:
 
     def prime_table(self, t):
         """[(name, source, count, first, window)] in record order (``_move_windows``) for the rings and the pooling window of
-        a fresh stream of age ``t``: the ring ``name`` has received ``count`` frames, frame j of it is frame j of the clip
-        tensor ``source`` -- "xin0": the input-norm output, "y<i>" / "out<i>": post-GCN tensor / output of block i (0-based)
-        -- and its window is the frames ``first`` .. ``first + window - 1`` (``first`` = count - window < 0: that many
-        leading zero frames).  Host only; from ``delay``, ``stride`` and ``kernel_size`` of the blocks."""
-        e, last = self.prime_counts(t), len(self._blocks) - 1
-        out = []
-        for name, _, _, window in self._move_windows():
-            if name == "xin0":
-                source, count = "xin0", e[0]
-            elif name == "pool":
-                source, count = f"out{last}", e[last + 1]
-            elif name[0] == "y" and name[1:].isdigit():
-                source, count = name, e[int(name[1:])]
-            elif name[:3] == "out" and name[3:].isdigit():
-                source, count = name, e[int(name[3:]) + 1]
-            else:
-                continue                                # the small per-stream states: not frames
-            out.append((name, source, count, count - window, window))
-        return out
+        a fresh stream of age ``t``: the ring ``name`` has received ``count`` = e(L) frames, L the level that feeds it, frame j
+        of it is frame j of the clip tensor ``source`` -- xin0: the input-norm output, y<i> / out<i>: post-GCN tensor /
+        output of block i (0-based) -- and its window is the frames ``first`` .. ``first + window - 1`` (``first`` = count -
+        window < 0: that many leading zero frames).  Host only; from the inventory (co_rings.py: ``_rings``), that is from
+        ``delay``, ``stride`` and ``kernel_size`` of the blocks.  The small per-stream states are not frames: not listed."""
+        e = self.prime_counts(t)
+        return [(ring.name, ring.source, e[ring.level], e[ring.level] - ring.window, ring.window) for ring in self._record_rings()]
 
     def prime_stream_bytes(self, t):
         """Bytes of clip intermediates ONE stream of ``t`` history frames holds while it is primed: the derived input, the
@@ -132,24 +120,23 @@ class StreamPrime:
         rc = native.lib().csk_input_norm_f32(native.ptr(d), native.ptr(ops["scale"]), native.ptr(ops["shift"]), native.ptr(h),
                                              n, c, t, v, m, c * t * v, t * v, native.stream_of(x))
         native.check(rc, "csk_input_norm_f32")
-        clip = {"xin0": h}
-        for i, blk in enumerate(self._blocks):
-            clip[f"y{i}"], h = parts(blk, h)
-            clip[f"out{i}"] = h
+        clip = {co_rings.XIN0: h}                       # the clip tensors under the names the rings' ``source`` asks for
+        for blk, (y_name, out_name) in zip(self._blocks, co_rings.block_ring_names(len(self._blocks))):
+            clip[y_name], h = parts(blk, h)
+            clip[out_name] = h
         small = {}
         for stage in reversed(entered):                 # record order (``_record_stages``)
             small.update(stage.prime(entered[stage], t))
-        table = {name: (source, first) for name, source, _, first, _ in self.prime_table(t)}
-        jobs, offset = [], 0
-        for name, rows, seg, window in self._move_windows():
-            if name in table:
-                src, first = clip[table[name][0]], table[name][1]
-                kind, rows_ = (native.PRIME_POOL, seg) if name == "pool" else (native.PRIME_RING, rows)
-                jobs.append(native.PrimeJob(src.data_ptr(), offset, kind, rows_, src.shape[2], first, window, 0))
-            else:
-                src = small[name]
-                jobs.append(native.PrimeJob(src.data_ptr(), offset, native.PRIME_WORDS, seg, 1, 0, window, 0))
-            offset += rows * seg * window
+        e, jobs, offset = self.prime_counts(t), [], 0
+        for ring in self._record_rings():               # a pooling entry is one row of seg channels, pooled by the launch
+            src = clip[ring.source]
+            kind, rows = (native.PRIME_POOL, ring.seg) if ring.kind == native.SCRUB_POOL_RING else (native.PRIME_RING, ring.rows)
+            jobs.append(native.PrimeJob(src.data_ptr(), offset, kind, rows, src.shape[2], e[ring.level] - ring.window, ring.window, 0))
+            offset += ring.rows * ring.seg * ring.window
+        for stage in self._record_stages:
+            for name, rows, seg, window in stage.windows():
+                jobs.append(native.PrimeJob(small[name].data_ptr(), offset, native.PRIME_WORDS, seg, 1, 0, window, 0))
+                offset += rows * seg * window
         if len(jobs) > native.MOVE_MAX_JOBS:
             raise RuntimeError(f"{len(jobs)} jobs in one pack launch (limit {native.MOVE_MAX_JOBS})")
         arr = (native.PrimeJob * len(jobs))(*jobs)

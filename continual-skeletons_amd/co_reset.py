@@ -11,6 +11,8 @@ import ctypes
 import torch
 
 from . import native
+from .co_migrate import _distinct_in_range, _index_list
+from .co_rings import scrub_job
 
 
 class StreamReset:
@@ -58,19 +60,11 @@ class StreamReset:
 
     def _check_reset(self, indices):
         """Everything ``reset_streams`` refuses, checked on the host before anything is launched; returns the index list."""
-        if isinstance(indices, torch.Tensor) or not isinstance(indices, (list, tuple, range)):
-            raise ValueError("reset_streams takes a sequence of ints (a list, tuple or range), not a tensor: the indices are "
-                             "host-side bookkeeping and reading a device tensor would cost a sync")
-        idx = list(indices)
-        if any(isinstance(i, bool) or not isinstance(i, int) for i in idx):
-            raise ValueError(f"reset_streams takes ints, got {[type(i).__name__ for i in idx]}")
+        idx = _index_list("reset_streams", indices)                # the two halves of ``_check_indices``, the slab's state between
         self._require_bound("reset_streams")
         if self._flushed:
             raise RuntimeError("the state was flushed by forward_steps(pad_end=True); call clean_state() instead")
-        if len(set(idx)) != len(idx):
-            raise ValueError(f"duplicate stream indices in {idx}")
-        if any(not 0 <= i < self._n for i in idx):
-            raise ValueError(f"stream indices {idx} outside a slab of {self._n} streams")
+        _distinct_in_range(idx, self._n)
         if self._frames % self.stride:
             raise RuntimeError(f"streams can be reset when the frame count is a multiple of {self.stride} (it is {self._frames}): "
                                "the stride phase of the strided blocks must match a fresh model's")
@@ -90,15 +84,20 @@ class StreamReset:
                                                    native.stream_of(self._xin0))
         native.check(rc, "csk_co_scrub_streams_f32")
 
-    def _ring_job(self, ring, first, count):
-        """Job for slots ``first .. first + count - 1`` (frame / emission numbers, taken modulo the depth) of a block ring."""
-        depth, rows, p = ring.shape
-        mv = self.input_shape[3] * self.input_shape[2]
-        return native.ScrubJob(ring.data_ptr(), p, depth, rows, first % depth, min(count, depth), mv, native.SCRUB_BLOCK_RING)
+    def _reset_jobs(self):
+        """The job list of a full reset: every slot of every ring of the inventory (``_rings``), then what the input pre-passes
+        with state clear (the streams' next frame is a first frame).  Built, not launched."""
+        jobs = [scrub_job(ring, 0, ring.tensor.shape[0]) for ring in self._rings()]
+        return jobs + [job for stage in self._record_stages for job in stage.reset_jobs()]
 
-    def _pool_job(self, first, count):
-        depth, n, c = self._pool_ring.shape
-        return native.ScrubJob(self._pool_ring.data_ptr(), c, depth, n, first % depth, min(count, depth), c, native.SCRUB_POOL_RING)
+    def _scrub_cycle_jobs(self, ages, before, after):
+        """Per cohort age in ``ages``, the job list of the scrub behind a cycle that moved the counters from ``before`` to
+        ``after``: of the rings the cycle wrote (one job each, the slots it wrote), those that are not live yet for a stream of
+        that age -- age < D(L) of the level L that feeds the ring."""
+        d = self._cum_delays()
+        wrote = [(d[ring.level], scrub_job(ring, before[ring.counter], after[ring.counter] - before[ring.counter]))
+                 for ring in self._rings() if after[ring.counter] > before[ring.counter]]
+        return [[job for live, job in wrote if age < live] for age in ages]
 
     def _leave_cohorts(self, idx):
         """The streams ``idx`` stop warming with whatever cohort they were in (reset again, or replaced by an imported stream)."""
@@ -121,13 +120,7 @@ class StreamReset:
         if not idx:
             return
         dev = self._device_indices(idx)
-        jobs = [self._ring_job(self._xin0, 0, self._xin0.shape[0])]
-        for st in (blk._state for blk in self._blocks):
-            jobs += [self._ring_job(st.y, 0, st.y.shape[0]), self._ring_job(st.out, 0, st.out.shape[0])]
-        jobs.append(self._pool_job(0, self.pool_size))
-        for stage in self._record_stages:          # the input pre-passes with state: the streams' next frame is a first frame
-            jobs += stage.reset_jobs()
-        self._scrub(jobs, dev, len(idx))
+        self._scrub(self._reset_jobs(), dev, len(idx))
         self._leave_cohorts(idx)                                   # a stream reset again leaves its earlier cohort
         at = self._frames
         if at in self._cohorts:                                    # a second call at the same frame: one cohort
@@ -146,17 +139,10 @@ class StreamReset:
         """After the launches of a cycle that moved the counters from ``before`` to their present value: per cohort, zero what
         the blocks that are not live yet for it wrote -- block L's y slots while age < D(L-1), its output slots while
         age < D(L), the pooling-window slots while age < D(10) -- one launch per cohort; cohorts that are ready leave."""
-        after, d, ready = self._counters(), self._cum_delays(), self._ready_age()
-        for at, (idx, dev) in list(self._cohorts.items()):
-            age = before[0] - at
-            if age < d[10] and self._scrub_warming:
-                jobs = []
-                for i, st in enumerate(blk._state for blk in self._blocks):
-                    for ring, c, live in ((st.y, 2 + 2 * i, d[i]), (st.out, 3 + 2 * i, d[i + 1])):     # (received, emitted)
-                        if age < live and after[c] > before[c]:
-                            jobs.append(self._ring_job(ring, before[c], after[c] - before[c]))
-                if after[1] > before[1]:
-                    jobs.append(self._pool_job(before[1], after[1] - before[1]))
-                self._scrub(jobs, dev, len(idx))
+        after, ready, cohorts = self._counters(), self._ready_age(), list(self._cohorts.items())
+        jobs = self._scrub_cycle_jobs([before[0] - at for at, _ in cohorts], before, after)
+        for (at, (idx, dev)), cohort_jobs in zip(cohorts, jobs):
+            if self._scrub_warming:
+                self._scrub(cohort_jobs, dev, len(idx))    # nothing left to scrub (age >= D(10)): no launch
             if after[0] - at >= ready:
                 del self._cohorts[at]

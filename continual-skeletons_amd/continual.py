@@ -34,6 +34,7 @@ from .co_clip import ClipAsSteps
 from .co_plan import NativePlan
 from .co_migrate import StreamMove
 from .co_prime import StreamPrime
+from .co_rings import SlabRings
 from .co_reset import StreamReset
 from .input_stage import InputChain
 from .keypoints import KeypointIntake
@@ -225,13 +226,6 @@ class _BlockState:
         if self.owns_xin:
             self.xin.zero_()
         self.s = self.e = 0
-
-    def nbytes(self):
-        """Persistent state of this block (rings); the split-K scratch is reported by scratch_bytes()."""
-        return 4 * (self.y.numel() + self.out.numel() + (self.xin.numel() if self.owns_xin else 0))
-
-    def scratch_bytes(self):
-        return 4 * self.partial.numel() if self.owns_partial else 0
 
 
 class CoSpatioTemporalBlock(SpatioTemporalBlock):
@@ -565,7 +559,7 @@ def co_geometry(c_in=3, unpadded=False):
     return r, p, s
 
 
-class CoStGcn(NativePlan, StreamReset, StreamMove, StreamPrime, ClipAsSteps, InputChain, _Folded):
+class CoStGcn(NativePlan, SlabRings, StreamReset, StreamMove, StreamPrime, ClipAsSteps, InputChain, _Folded):
     """CoST-GCN: models/cost_gcn/cost_gcn.py:21-41 + CoModelBase (models/base.py:68-227) without the Ride shell.
 
     ``forward_step(x_t: (N, C, V, M))`` -> logits (N, classes) on the steps where the whole stack (10 blocks,
@@ -573,7 +567,7 @@ class CoStGcn(NativePlan, StreamReset, StreamMove, StreamPrime, ClipAsSteps, Inp
     -> (N, classes, n_predictions).  ``forward(x)`` = clip mode of CoModelBase.forward (base.py:166-181).
     state_dict keys equal the reference's (``layers.layerK.0.1.gcn...``); a regular StGcn state_dict loads too
     (what ``map_state_dict`` does in the reference, base.py:200-224).  This class binds the state slab and steps on it; the
-    native plan (co_plan.py: NativePlan), the per-stream reset (co_reset.py: StreamReset), moving streams between slabs
+    native plan (co_plan.py: NativePlan), the one inventory of the slab's rings (co_rings.py: SlabRings), the per-stream reset (co_reset.py: StreamReset), moving streams between slabs
     (co_migrate.py: StreamMove), priming streams from buffered history with one clip pass (co_prime.py: StreamPrime), a stored clip at the
     steps' arithmetic (co_clip.py: ClipAsSteps -- ``forward_clip_as_steps``) are base classes.  The input pre-passes are the
     stage objects of ``STAGES`` (input_stage.py: InputChain), all off by default and run in that order in front of every cycle:
@@ -672,6 +666,7 @@ class CoStGcn(NativePlan, StreamReset, StreamMove, StreamPrime, ClipAsSteps, Inp
                                  counters=(ctypes.c_int64 * 2).from_buffer(self._ctr, 16 * (i + 1))).out
         self._pool_ring = torch.zeros((self.pool_size, n, 256), device=device, dtype=torch.float32)
         self._pooled = torch.empty((n, 256), device=device, dtype=torch.float32)
+        self._bound_rings = self._describe_rings(True)
         self._flushed = False
         self._forget_resets()
         for stage in self._record_stages:
@@ -716,7 +711,7 @@ class CoStGcn(NativePlan, StreamReset, StreamMove, StreamPrime, ClipAsSteps, Inp
     def state_bytes(self):
         """Persistent continual state (input ring, per-block rings, pooling window; the state of the input pre-passes: previous
         frame and flags of a motion modality, latched rotations and flags of the pre-normalisation)."""
-        return (sum(blk._state.nbytes() for blk in self._blocks) + 4 * (self._xin0.numel() + self._pool_ring.numel())
+        return (4 * sum(ring.tensor.numel() for ring in self._rings())
                 + sum(t.numel() * t.element_size() for t in self._stage_tensors()))
 
     def scratch_bytes(self):
@@ -728,10 +723,8 @@ class CoStGcn(NativePlan, StreamReset, StreamMove, StreamPrime, ClipAsSteps, Inp
 
     def clean_state(self):
         if self._n is not None:
-            self._xin0.zero_()
-            for blk in self._blocks:
-                blk.clean_state()
-            self._pool_ring.zero_()
+            for ring in self._rings():
+                ring.tensor.zero_()
             for stage in self._record_stages:
                 stage.clean()
             self._set_counters([0] * 22)
@@ -787,8 +780,7 @@ class CoStGcn(NativePlan, StreamReset, StreamMove, StreamPrime, ClipAsSteps, Inp
         self._ctr[:], self._flushed, self._reset_at, self._cohorts = position
 
     def _state_tensors(self):
-        return ([self._xin0, self._pool_ring, self._pooled] + [t for blk in self._blocks for t in (blk._state.y, blk._state.out)]
-                + self._stage_tensors())
+        return [ring.tensor for ring in self._rings()] + [self._pooled] + self._stage_tensors()
 
     def _stage_tensors(self):
         """The per-stream state of the input pre-passes, in record order."""

@@ -1,21 +1,21 @@
 // stream_move.hip -- copy the live state of SOME streams between the continual slab and a packed buffer
-// (csk_co_move_streams_f32, include/cskel.h): the copying counterpart of stream_reset.hip.  One launch takes a table of jobs
+// (csk_co_move_streams_f32, include/cskel.h).  One launch takes a table of jobs
 // (ring, the slot of its newest live frame, how many newest slots to move, offset inside a stream's packed record) and a
 // device list of stream indices; record j of the packed buffer pairs with stream streams[j].  Export reads the rings and
 // writes the records, import reads the records and writes -- in every row of the window's slots -- the segments of the named
 // streams and nothing else: not the neighbouring streams, not the P-padding, not the slots outside the window.  The words
 // are moved as 32-bit patterns (the flags are int32, the latched rotations fp64 halves).  HBM-bound loads and stores only.
-#include "mfma_core.h"
+// The window's device form, the host checks of a ring job, the grid and the walk over the segments are stream_jobs.h
+// (shared with stream_reset.hip); this file has the entry, the record side and what is done to a segment.
+#include "stream_jobs.h"
 
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-// device form of a job: as ScrubJob (stream_reset.hip), "segment of stream n in row (slot, row) starts at
-// (slot * rows + row) * row_stride + n * seg"; in the record the window's slots go oldest first: (i * rows + row) * seg
+// device form of a job: the window as a slot run, oldest slot first, and where it stands in a record: (i * rows + row) * seg
 struct MoveJob {
-    uint32_t *ring;
-    int64_t row_stride, offset;
-    int32_t depth, rows, slot0, n_slots, seg, pad_;
+    SlotRun run;
+    int64_t offset;
 };
 struct MoveTable {
     MoveJob job[CSK_CO_MOVE_MAX_JOBS];
@@ -56,29 +56,19 @@ __device__ __forceinline__ void copy_segment(uint32_t *dst, const uint32_t *src,
         for (int i = 0; i < tail; ++i) db[4 * nb + i] = sb[4 * nb + i];
 }
 
-// grid: y = job, x strides over the job's segments (slot of the window, row, listed stream -- streams fastest, as the scrub
-// kernel).  An index outside [0, n_total) moves nothing.
+// grid: y = job, x walks the window's segments (walk_segments, stream_jobs.h) and copies each from or to its place in
+// record k.
 __global__ __launch_bounds__(256) void move_streams_kernel(const MoveTable t, uint32_t *__restrict__ packed, int64_t record_words,
                                                            const int32_t *__restrict__ streams, int n_streams, int n_total,
                                                            int to_ring) {
     const MoveJob &j = t.job[blockIdx.y];
-    const int sub = threadIdx.x & 15;
-    const int64_t total = (int64_t)j.n_slots * j.rows * n_streams;
-    for (int64_t g = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 4; g < total; g += (int64_t)gridDim.x * 16) {
-        const int k = (int)(g % n_streams);
-        const int64_t q = g / n_streams;
-        const int row = (int)(q % j.rows), i = (int)(q / j.rows);
-        int slot = j.slot0 + i;
-        if (slot >= j.depth) slot -= j.depth;
-        const int n = streams[k];
-        if (n < 0 || n >= n_total) continue;
-        uint32_t *in_ring = j.ring + ((int64_t)slot * j.rows + row) * j.row_stride + (int64_t)n * j.seg;
-        uint32_t *in_record = packed + (int64_t)k * record_words + j.offset + ((int64_t)i * j.rows + row) * j.seg;
+    walk_segments(j.run, streams, n_streams, n_total, [&](int k, int i, int row, uint32_t *in_ring, int seg, int sub) {
+        uint32_t *in_record = packed + (int64_t)k * record_words + j.offset + ((int64_t)i * j.run.rows + row) * seg;
         if (to_ring)
-            copy_segment(in_ring, in_record, j.seg, sub);
+            copy_segment(in_ring, in_record, seg, sub);
         else
-            copy_segment(in_record, in_ring, j.seg, sub);
-    }
+            copy_segment(in_record, in_ring, seg, sub);
+    });
 }
 
 extern "C" int csk_co_move_streams_f32(const csk_move_job *jobs, int n_jobs, void *packed, int64_t record_floats, const int32_t *streams,
@@ -96,41 +86,28 @@ extern "C" int csk_co_move_streams_f32(const csk_move_job *jobs, int n_jobs, voi
     int64_t most = 0;
     for (int i = 0; i < n_jobs; ++i) {
         const csk_move_job &s = jobs[i];
-        if (!s.ring) CSK_FAIL("co_move_streams: null pointer (ring of job %d)", i);
-        if (reinterpret_cast<uintptr_t>(s.ring) & 3) CSK_FAIL("co_move_streams: ring of job %d is not 4-byte aligned", i);
-        if (s.depth < 1 || s.rows < 1 || s.seg < 1 || s.row_floats < 1) CSK_FAIL("co_move_streams: bad dims in job %d", i);
-        if (s.newest < 0 || s.newest >= s.depth) CSK_FAIL("co_move_streams: newest slot %d of job %d outside a ring of %d slots", s.newest, i, s.depth);
-        if (s.window < 0 || s.window > s.depth)
-            CSK_FAIL("co_move_streams: a window of %d slots in job %d is longer than the ring (%d slots)", s.window, i, s.depth);
-        MoveJob &d = t.job[n];
-        int slot0 = s.newest + 1 - s.window;            // the window's oldest slot; > -depth
-        if (slot0 < 0) slot0 += s.depth;
-        if (s.kind == CSK_SCRUB_BLOCK_RING) {
-            if ((int64_t)n_total * s.seg > s.row_floats)
-                CSK_FAIL("co_move_streams: %d streams of %d floats cannot fit a row of %lld floats (job %d)", n_total, s.seg,
-                         (long long)s.row_floats, i);
-            d = {reinterpret_cast<uint32_t *>(s.ring), s.row_floats, s.offset, s.depth, s.rows, slot0, s.window, s.seg, 0};
-        } else if (s.kind == CSK_SCRUB_POOL_RING) {
-            if (s.rows != n_total || s.seg != s.row_floats)
-                CSK_FAIL("co_move_streams: a pooling ring has one row of seg = row_floats floats per stream (job %d: rows %d, slab %d)", i,
-                         s.rows, n_total);
-            d = {reinterpret_cast<uint32_t *>(s.ring), (int64_t)s.rows * s.row_floats, s.offset, s.depth, 1, slot0, s.window, s.seg, 0};
-        } else {
-            CSK_FAIL("co_move_streams: unknown ring kind %d in job %d", s.kind, i);
-        }
-        if (s.offset < 0 || s.offset + (int64_t)d.n_slots * d.rows * d.seg > record_floats)
+        SlotRun &d = t.job[n].run;
+        const auto run_of_job = [&](SlotRun &run) {     // this entry's own checks: the window, as a run from its oldest slot
+            if (s.newest < 0 || s.newest >= s.depth) CSK_FAIL("co_move_streams: newest slot %d of job %d outside a ring of %d slots", s.newest, i, s.depth);
+            if (s.window < 0 || s.window > s.depth)
+                CSK_FAIL("co_move_streams: a window of %d slots in job %d is longer than the ring (%d slots)", s.window, i, s.depth);
+            run.slot0 = s.newest + 1 - s.window;        // > -depth
+            if (run.slot0 < 0) run.slot0 += s.depth;
+            run.n_slots = s.window;
+            return 0;
+        };
+        if (resolve_ring_job("co_move_streams", i, s.kind, s.ring, s.row_floats, s.depth, s.rows, s.seg, n_total, d, run_of_job)) return -1;
+        const int64_t words = run_segments(d, 1) * d.seg;
+        if (s.offset < 0 || s.offset + words > record_floats)
             CSK_FAIL("co_move_streams: job %d covers floats [%lld, %lld) of a record of %lld", i, (long long)s.offset,
-                     (long long)(s.offset + (int64_t)d.n_slots * d.rows * d.seg), (long long)record_floats);
+                     (long long)(s.offset + words), (long long)record_floats);
+        t.job[n].offset = s.offset;
         if (d.n_slots == 0) continue;                   // an empty window: nothing to launch for it
-        const int64_t segs = (int64_t)d.n_slots * d.rows * n_streams;
-        if (segs > most) most = segs;
+        if (run_segments(d, n_streams) > most) most = run_segments(d, n_streams);
         ++n;
     }
     if (n == 0 || n_streams == 0) return 0;
-    for (int i = n; i < CSK_CO_MOVE_MAX_JOBS; ++i) t.job[i] = t.job[0];    // never indexed (grid y = n); keeps the table defined
-    const int64_t want = (most + 15) / 16;
-    const unsigned blocks = (unsigned)(want < 4096 ? want : 4096);
-    hipLaunchKernelGGL(move_streams_kernel, dim3(blocks, (unsigned)n), dim3(256), 0, (hipStream_t)stream, t, reinterpret_cast<uint32_t *>(packed),
-                       record_floats, streams, n_streams, n_total, to_ring);
+    hipLaunchKernelGGL(move_streams_kernel, table_grid(t.job, n, most, 16, 4096), dim3(256), 0, (hipStream_t)stream, t,
+                       reinterpret_cast<uint32_t *>(packed), record_floats, streams, n_streams, n_total, to_ring);
     return (int)hipGetLastError();
 }

@@ -12,8 +12,9 @@
 //              (float)(M * V).  That loop is interleaved sixteen rows deep with the head's ring store, so it is restated
 //              here and not shared; tests/test_gpu_stream_prime.py holds the two together bit for bit.
 //   words job  a per-stream array [n][words] (flags, latched rotations, the previous raw frame): a plain copy.
-// HBM-bound: source runs are V contiguous floats at stride T_src * V, the stores are contiguous.
-#include "mfma_core.h"
+// HBM-bound: source runs are V contiguous floats at stride T_src * V, the stores are contiguous.  The jobs read clip tensors,
+// not rings, so of stream_jobs.h this file takes the grid of a by-value job table only.
+#include "stream_jobs.h"
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
@@ -144,9 +145,7 @@ extern "C" int csk_co_prime_pack_f32(const csk_prime_job *jobs, int n_jobs, void
         ++n;
     }
     if (n == 0 || n_streams == 0) return 0;
-    for (int i = n; i < CSK_CO_MOVE_MAX_JOBS; ++i) t.job[i] = t.job[0];    // never indexed (grid y = n); keeps the table defined
-    const unsigned blocks = (unsigned)(most < 8192 ? most : 8192);
-    hipLaunchKernelGGL(prime_pack_kernel, dim3(blocks, (unsigned)n), dim3(256), 0, (hipStream_t)stream, t, reinterpret_cast<uint32_t *>(packed),
-                       record_floats, n_streams, M, V);
+    hipLaunchKernelGGL(prime_pack_kernel, table_grid(t.job, n, most, 1, 8192), dim3(256), 0, (hipStream_t)stream, t,
+                       reinterpret_cast<uint32_t *>(packed), record_floats, n_streams, M, V);
     return (int)hipGetLastError();
 }

@@ -3,19 +3,14 @@
 // every slot of each run, the segments of those streams -- nothing else: not the neighbouring streams, not the P-padding
 // behind the last one.  Two uses (co_reset.py): the full reset of a stream (all slots of every ring) and the per-cycle
 // scrub of what the not-yet-live blocks wrote for a warming stream (the slots one cycle wrote).  HBM-bound stores only.
-#include "mfma_core.h"
+// The job's device form, its host checks, the grid and the walk over the segments are stream_jobs.h (shared with
+// stream_move.hip); this file has the entry and what is done to a segment.
+#include "stream_jobs.h"
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-// device form of a job: both layouts of include/cskel.h reduce to "segment of stream n in row (slot, row) starts at
-// (slot * rows + row) * row_stride + n * seg" (pooling ring [slots][N][C]: one row of N * C floats per slot, seg = C)
-struct ScrubJob {
-    float *ring;
-    int64_t row_stride;
-    int32_t depth, rows, slot0, n_slots, seg, pad_;
-};
 struct ScrubTable {
-    ScrubJob job[CSK_CO_SCRUB_MAX_JOBS];
+    SlotRun job[CSK_CO_SCRUB_MAX_JOBS];
 };
 
 // Zero p[0 .. len) with the widest stores its alignment allows; 16 lanes (`sub` = 0..15) share one segment.  p is 4-byte
@@ -42,23 +37,11 @@ __device__ __forceinline__ void zero_segment(float *p, int len, int sub) {
     }
 }
 
-// grid: y = job, x strides over the job's segments (slot of the run, row, listed stream -- streams fastest, so neighbouring
-// 16-lane groups write neighbouring parts of one row).  An index outside [0, n_total) writes nothing.
+// grid: y = job, x walks the job's segments (walk_segments, stream_jobs.h) and zeroes each.
 __global__ __launch_bounds__(256) void scrub_streams_kernel(const ScrubTable t, const int32_t *__restrict__ streams, int n_streams,
                                                             int n_total) {
-    const ScrubJob &j = t.job[blockIdx.y];
-    const int sub = threadIdx.x & 15;
-    const int64_t total = (int64_t)j.n_slots * j.rows * n_streams;
-    for (int64_t g = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 4; g < total; g += (int64_t)gridDim.x * 16) {
-        const int k = (int)(g % n_streams);
-        const int64_t q = g / n_streams;
-        const int row = (int)(q % j.rows);
-        int slot = j.slot0 + (int)(q / j.rows);
-        if (slot >= j.depth) slot -= j.depth;
-        const int n = streams[k];
-        if (n < 0 || n >= n_total) continue;
-        zero_segment(j.ring + ((int64_t)slot * j.rows + row) * j.row_stride + (int64_t)n * j.seg, j.seg, sub);
-    }
+    walk_segments(t.job[blockIdx.y], streams, n_streams, n_total,
+                  [](int, int, int, uint32_t *p, int seg, int sub) { zero_segment(reinterpret_cast<float *>(p), seg, sub); });
 }
 
 extern "C" int csk_co_scrub_streams_f32(const csk_scrub_job *jobs, int n_jobs, const int32_t *streams, int n_streams, int n_total,
@@ -74,35 +57,21 @@ extern "C" int csk_co_scrub_streams_f32(const csk_scrub_job *jobs, int n_jobs, c
     int64_t most = 0;
     for (int i = 0; i < n_jobs; ++i) {
         const csk_scrub_job &s = jobs[i];
-        if (!s.ring) CSK_FAIL("co_scrub_streams: null pointer (ring of job %d)", i);
-        if (reinterpret_cast<uintptr_t>(s.ring) & 3) CSK_FAIL("co_scrub_streams: ring of job %d is not 4-byte aligned", i);
-        if (s.depth < 1 || s.rows < 1 || s.seg < 1 || s.row_floats < 1) CSK_FAIL("co_scrub_streams: bad dims in job %d", i);
-        if (s.slot0 < 0 || s.slot0 >= s.depth) CSK_FAIL("co_scrub_streams: slot0 %d of job %d outside a ring of %d slots", s.slot0, i, s.depth);
-        if (s.n_slots < 0 || s.n_slots > s.depth)
-            CSK_FAIL("co_scrub_streams: a run of %d slots in job %d is longer than the ring (%d slots)", s.n_slots, i, s.depth);
-        ScrubJob &d = t.job[n];
-        if (s.kind == CSK_SCRUB_BLOCK_RING) {
-            if ((int64_t)n_total * s.seg > s.row_floats)
-                CSK_FAIL("co_scrub_streams: %d streams of %d floats cannot fit a row of %lld floats (job %d)", n_total, s.seg,
-                         (long long)s.row_floats, i);
-            d = {s.ring, s.row_floats, s.depth, s.rows, s.slot0, s.n_slots, s.seg, 0};
-        } else if (s.kind == CSK_SCRUB_POOL_RING) {
-            if (s.rows != n_total || s.seg != s.row_floats)
-                CSK_FAIL("co_scrub_streams: a pooling ring has one row of seg = row_floats floats per stream (job %d: rows %d, slab %d)", i,
-                         s.rows, n_total);
-            d = {s.ring, (int64_t)s.rows * s.row_floats, s.depth, 1, s.slot0, s.n_slots, s.seg, 0};
-        } else {
-            CSK_FAIL("co_scrub_streams: unknown ring kind %d in job %d", s.kind, i);
-        }
+        SlotRun &d = t.job[n];
+        const auto run_of_job = [&](SlotRun &run) {     // this entry's own checks: the run as the caller names it
+            if (s.slot0 < 0 || s.slot0 >= s.depth) CSK_FAIL("co_scrub_streams: slot0 %d of job %d outside a ring of %d slots", s.slot0, i, s.depth);
+            if (s.n_slots < 0 || s.n_slots > s.depth)
+                CSK_FAIL("co_scrub_streams: a run of %d slots in job %d is longer than the ring (%d slots)", s.n_slots, i, s.depth);
+            run.slot0 = s.slot0, run.n_slots = s.n_slots;
+            return 0;
+        };
+        if (resolve_ring_job("co_scrub_streams", i, s.kind, s.ring, s.row_floats, s.depth, s.rows, s.seg, n_total, d, run_of_job)) return -1;
         if (d.n_slots == 0) continue;                   // an empty run: nothing to launch for it
-        const int64_t segs = (int64_t)d.n_slots * d.rows * n_streams;
-        if (segs > most) most = segs;
+        if (run_segments(d, n_streams) > most) most = run_segments(d, n_streams);
         ++n;
     }
     if (n == 0 || n_streams == 0) return 0;
-    for (int i = n; i < CSK_CO_SCRUB_MAX_JOBS; ++i) t.job[i] = t.job[0];   // never indexed (grid y = n); keeps the table defined
-    const int64_t want = (most + 15) / 16;
-    const unsigned blocks = (unsigned)(want < 4096 ? want : 4096);
-    hipLaunchKernelGGL(scrub_streams_kernel, dim3(blocks, (unsigned)n), dim3(256), 0, (hipStream_t)stream, t, streams, n_streams, n_total);
+    hipLaunchKernelGGL(scrub_streams_kernel, table_grid(t.job, n, most, 16, 4096), dim3(256), 0, (hipStream_t)stream, t, streams, n_streams,
+                       n_total);
     return (int)hipGetLastError();
 }

@@ -38,16 +38,22 @@ def _pattern(shape, lead=0):
 STREAM_SETS = ([0], [1, 3], [4], [0, 1, 2, 3, 4], [3, 0])
 
 
-@pytest.mark.parametrize("lead", [0, 1])
-@pytest.mark.parametrize("mv", [50, 36, 25])
-@pytest.mark.parametrize("rows", [3, 64, 65])
-@pytest.mark.parametrize("depth", [12, 5])
+def _block_ring_cases():
+    """(depth, rows, mv, lead): the segment lengths of the models at 0 / 4 bytes of lead over three row counts, then -- over
+    rows 3 and 65 -- what they leave out of mv in (50, 36, 25, 2, 1) x lead in (0, 1, 2, 3): the segments shorter than their
+    own head (mv = 2, 1) and the other two base alignments."""
+    cases = [(depth, rows, mv, lead) for lead in (0, 1) for mv in (50, 36, 25) for rows in (3, 64, 65) for depth in (12, 5)]
+    return cases + [(depth, rows, mv, lead) for lead in (0, 1, 2, 3) for mv in (50, 36, 25, 2, 1) for rows in (3, 65) for depth in (12, 5)
+                    if (depth, rows, mv, lead) not in cases]
+
+
+@pytest.mark.parametrize("depth,rows,mv,lead", _block_ring_cases())
 def test_scrub_kernel_block_ring_writes_the_named_segments_only(depth, rows, mv, lead):
     """Ring [depth][rows][P], P = N * mv rounded up to 4 (NTU 250 -> 252 and M = 1 125 -> 128 leave a padding tail): segment
-    starts 8-byte aligned for odd streams at mv = 50, 16-byte at 36, 4-byte at 25 -- and everything 4 bytes further with
-    ``lead``; slot runs that wrap, a single slot, the whole ring, an empty run.  The result equals the CPU-built
-    expectation bit for bit, so every float outside the named segments (neighbours, padding, other slots, the lead) is
-    unchanged."""
+    starts 8-byte aligned for odd streams at mv = 50, 16-byte at 36, 4-byte at 25, and at mv = 2 and 1 a segment can be shorter
+    than the floats in front of its first 16-byte boundary -- and everything 4, 8 or 12 bytes further with ``lead``; slot runs
+    that wrap, a single slot, the whole ring, an empty run.  The result equals the CPU-built expectation bit for bit, so every
+    float outside the named segments (neighbours, padding, other slots, the lead) is unchanged."""
     p = (N * mv + 3) // 4 * 4
     for streams in STREAM_SETS:
         for slot0, n_slots in ((depth - 2, 4), (3, 1), (0, depth), (depth - 1, depth), (1, 0)):
