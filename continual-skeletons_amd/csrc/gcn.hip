@@ -1,8 +1,10 @@
 // gcn.hip -- GCN stage of the ST-GCN / A-GCN forward path (gfx950 / MI355X):
 //   y = ReLU( W' . agg(x) + b' + gcn_residual(x) )      models/base.py:260-270, models/a_gcn/a_gcn.py:48-69
-// Two kernels share GcnParams: gcn_stage_sparse2_kernel (skeleton graphs: the aggregated B operand is formed on the
-// fly from register-resident adjacency entries) and gcn_stage_kernel (general: any / dense / per-sample / per-frame
-// adjacency, ELL tables in LDS, aggregation into an LDS operand tile).  GEMM core: mfma_core.h.
+// Four kernels and a reduction share GcnParams: gcn_stage_sparse2_kernel (skeleton graphs: the aggregated B operand is
+// formed on the fly from register-resident adjacency entries; also the bare 1 x 1 conv and the split-K ranges),
+// gcn_stage_dense_kernel (dense per-segment adjacency on 128-row tiles: aggregation on the matrix pipe), gcn_stage_kernel
+// (general: any / dense / per-sample / per-frame adjacency, ELL tables in LDS, aggregation into an LDS operand tile) and
+// gcn_reduce_kernel (sums the split-K ranges); the fourth, gcn_stage_dense2_kernel, lives in gcn_dense.hip.  GEMM core: mfma_core.h.
 #include <type_traits>
 
 #include "mfma_core.h"
@@ -545,8 +547,7 @@ __global__ __launch_bounds__(NTHREADS, OCC) void gcn_stage_dense_kernel(const Gc
     constexpr int WM = MT / 64;                          // KC2 = channels per chunk, OCC = workgroups per CU
     constexpr int R = CONVRES ? 4 : 3;
     constexpr int M4 = MT / 4;
-    constexpr int WB = R * KC2 * M4 / NTHREADS;         // f32x4 of weights per thread and chunk (6 / 8 or 1.5 -> see below)
-    constexpr int WBU = (R * KC2 * M4 + NTHREADS - 1) / NTHREADS;
+    constexpr int WBU = (R * KC2 * M4 + NTHREADS - 1) / NTHREADS;   // f32x4 of weights per thread and chunk (surplus threads re-stage the last)
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int V = p.V, FT = p.lds_frames, ldbx = p.ldb;  // frames per tile, padded x row length
     float *Wl = smem;                                    // [R][KC2][MT]
@@ -564,7 +565,6 @@ __global__ __launch_bounds__(NTHREADS, OCC) void gcn_stage_dense_kernel(const Gc
     const int ta = qt * FT, q0 = ta * V;
     const int fcnt = min(FT, p.frames - ta);             // frames of this tile
     const int ncol = fcnt * V;                           // valid columns of this tile
-    (void)WB;
 
     {   // this segment's adjacency -> LDS (dense column-wise values, include/cskel.h)
         const float *gv = p.ell_val + (int64_t)seg * p.adj_seg_stride;
@@ -585,7 +585,6 @@ __global__ __launch_bounds__(NTHREADS, OCC) void gcn_stage_dense_kernel(const Gc
     // the same values instead of shifting data)
     f32x4 wv[WBU];
     constexpr int XV = 2;                                // x vectors per thread and chunk: KC2 rows x <= 256 / 4 ... 
-    const int nvec_row = (ncol + 3) / 4;
     const int xrow = tid / 32, xv0 = tid % 32;           // 8 rows x 32 vectors per sweep of 256 threads
     f32x4 xv[XV][2];
     auto issue = [&](int c0) {
@@ -624,7 +623,6 @@ __global__ __launch_bounds__(NTHREADS, OCC) void gcn_stage_dense_kernel(const Gc
             }
         }
     };
-    (void)nvec_row;
     // aggregation units of this wave
     const int RT = (fcnt * KC2 + 31) / 32, CT = (3 * V + 31) / 32, KS2 = (V + 1) / 2;
     const int offA = wm * 64 + l31;
@@ -774,157 +772,186 @@ __global__ __launch_bounds__(256) void gcn_reduce_kernel(const GcnParams p) {
 // ------------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------------
+// The workgroup tile of gcn_stage_kernel and gcn_stage_sparse2_kernel for p's shape: MT x NT outputs (128 rows where Mpad allows),
+// activation rows of whole frames.  Fills p.ldb / p.lds_frames / p.qtiles / p.mtiles.  The two guards of that arithmetic speak
+// under the caller's name; a caller runs each at its own place among its checks (gcn_stage_setup, csk_conv1x1_f32).
+struct GcnTile {
+    int MT, NT;
+    explicit GcnTile(GcnParams &p) : MT((p.Mpad % 128) == 0 ? 128 : 64), NT(16384 / MT) {
+        const int max_dt = (NT + p.V - 2) / p.V;
+        p.lds_frames = max_dt + 1;
+        p.ldb = round_up(p.lds_frames * p.V, 4);
+        p.qtiles = (unsigned)(((int64_t)p.frames * p.V + NT - 1) / NT); p.mtiles = p.Mpad / MT;
+    }
+    static int positions_guard(const GcnParams &p, const char *who) {
+        if ((int64_t)p.frames * p.V >= (1 << 26)) CSK_FAIL("%s: frames*V too large for 32-bit position arithmetic", who);
+        return 0;
+    }
+    static int grid_guard(const GcnParams &p, int n_seg, const char *who) {
+        if ((int64_t)p.qtiles * p.mtiles * n_seg >= (1ll << 31)) CSK_FAIL("%s: grid too large", who);
+        return 0;
+    }
+};
+
 // What every launch of the stage starts from: the argument checks that need no operand (0, or -1 with the message set), the launch
 // parameters with the geometry of the 32x32x2 tiles, *lds_out = the general kernel's LDS tile, *sparse_out = the skeleton-sparse
 // fast path applies.  No pointer but ell_cnt is dereferenced: csk_gcn_stage_f32_tile calls it without operands.
-static int gcn_stage_setup(const float *x, float *y, const float *w, const float *bias, const int32_t *ell_src, const float *ell_val,
-                           const int32_t *ell_cnt, int ell_w, int64_t adj_seg_stride, int adj_per_frame, int n_seg, int c_in, int c_out,
-                           int frames, int V, int64_t x_seg_stride, int64_t x_chan_stride, int64_t y_seg_stride, int64_t y_chan_stride,
-                           int res_mode, int ksplit, float *partial, GcnParams *out, size_t *lds_out, bool *sparse_out) {
-    if (n_seg <= 0 || c_in <= 0 || c_out <= 0 || frames <= 0 || V < 2 || V > 64) CSK_FAIL("gcn_stage: bad dims");
+static int gcn_stage_setup(const GcnCall &c, GcnParams *out, int *MT_out, size_t *lds_out, bool *sparse_out) {
+    const int V = c.V, ell_w = c.ell_w;
+    const int32_t *ell_cnt = c.ell_cnt;
+    if (c.n_seg <= 0 || c.c_in <= 0 || c.c_out <= 0 || c.frames <= 0 || V < 2 || V > 64) CSK_FAIL("gcn_stage: bad dims");
     if (ell_w < 1 || ell_w > V) CSK_FAIL("gcn_stage: ell_w must be in [1, V]");
-    if (res_mode != CSK_RES_IDENTITY && res_mode != CSK_RES_CONV) CSK_FAIL("gcn_stage: res_mode must be identity or conv");
-    if (res_mode == CSK_RES_IDENTITY && c_in != c_out) CSK_FAIL("gcn_stage: identity residual needs c_in == c_out");
+    if (c.res_mode != CSK_RES_IDENTITY && c.res_mode != CSK_RES_CONV) CSK_FAIL("gcn_stage: res_mode must be identity or conv");
+    if (c.res_mode == CSK_RES_IDENTITY && c.c_in != c.c_out) CSK_FAIL("gcn_stage: identity residual needs c_in == c_out");
     for (int i = 0; i < 3; ++i)
         if (ell_cnt[i] < 0 || ell_cnt[i] > ell_w) CSK_FAIL("gcn_stage: ell_cnt[%d] out of range", i);
     GcnParams &p = *out;
-    p = gcn_params(x, y, w, bias, ell_src, ell_val, ell_cnt, ell_w, adj_seg_stride, c_in, c_out, frames, V, x_seg_stride,
-                   x_chan_stride, y_seg_stride, y_chan_stride, res_mode, partial);
+    p = gcn_params(c);
     // per-segment adjacencies are dense by contract (include/cskel.h): ell_w == V, ell_cnt == {V,V,V}, src[e] == e
-    p.dense = adj_seg_stride != 0 && ell_w == V && ell_cnt[0] == V && ell_cnt[1] == V && ell_cnt[2] == V;
-    p.adj_per_frame = adj_per_frame != 0;
+    p.dense = c.adj_seg_stride != 0 && ell_w == V && ell_cnt[0] == V && ell_cnt[1] == V && ell_cnt[2] == V;
+    p.adj_per_frame = c.adj_per_frame != 0;
     if (p.adj_per_frame && !p.dense) CSK_FAIL("gcn_stage: per-frame adjacency must be dense (ell_w == V, ell_cnt == V)");
-    const bool big = (p.Mpad % 128) == 0;
-    const int MT = big ? 128 : 64, NT = 16384 / MT;
-    const int max_dt = (NT + V - 2) / V;
-    p.ldb = round_up((max_dt + 1) * V, 4);
-    p.lds_frames = max_dt + 1;
-    const size_t lds = (size_t)(p.R * KC * MT + p.R * KC * NT + KC * p.ldb + 3 * V * ell_w * (1 + (p.adj_per_frame ? p.lds_frames : 1))) * sizeof(float);
+    const GcnTile tile(p);
+    const bool big = tile.MT == 128;
+    const size_t lds = (size_t)(p.R * KC * tile.MT + p.R * KC * tile.NT + KC * p.ldb + 3 * V * ell_w * (1 + (p.adj_per_frame ? p.lds_frames : 1))) * sizeof(float);
     if (lds > 160 * 1024) CSK_FAIL("gcn_stage: LDS tile %zu B exceeds 160 KiB", lds);
-    const int Q = frames * V;
-    if ((int64_t)frames * V >= (1 << 26)) CSK_FAIL("gcn_stage: frames*V too large for 32-bit position arithmetic");
-    p.qtiles = (Q + NT - 1) / NT; p.mtiles = p.Mpad / MT;
-    if ((int64_t)p.qtiles * p.mtiles * n_seg >= (1ll << 31)) CSK_FAIL("gcn_stage: grid too large");
+    if (const int rc = GcnTile::positions_guard(p, "gcn_stage")) return rc;
+    if (const int rc = GcnTile::grid_guard(p, c.n_seg, "gcn_stage")) return rc;
     // sparse-graph fast path: shared adjacency with <= 1/1/4 non-zeros per column, activation tile <= 320 positions
-    const bool sparse = adj_seg_stride == 0 && ell_cnt[0] <= 1 && ell_cnt[1] <= 1 && ell_cnt[2] <= 4 && p.ldb <= (big ? 192 : 320) &&
+    const bool sparse = c.adj_seg_stride == 0 && ell_cnt[0] <= 1 && ell_cnt[1] <= 1 && ell_cnt[2] <= 4 && p.ldb <= (big ? 192 : 320) &&
                         !csk_diag_flag("CSK_GCN_GENERAL");
     // split-K (latency mode)
-    if (ksplit > 1 && !sparse) CSK_FAIL("gcn_stage_splitk: split-K is built for the skeleton-sparse kernel (shared adjacency, <= 1/1/4 non-zeros per column)");
-    p.ksplit = split_ranges(p.CinPad, c_in, ksplit, 8, &p.cper);
-    *lds_out = lds; *sparse_out = sparse;
+    if (c.ksplit > 1 && !sparse) CSK_FAIL("gcn_stage_splitk: split-K is built for the skeleton-sparse kernel (shared adjacency, <= 1/1/4 non-zeros per column)");
+    p.ksplit = split_ranges(p.CinPad, c.c_in, c.ksplit, 8, &p.cper);
+    *MT_out = tile.MT; *lds_out = lds; *sparse_out = sparse;
     return 0;
 }
 
-// the launch of the slot-balanced 16x16x4 tiles (step16.hip; same sums) is tried for these
-static bool gcn16_candidate(const GcnParams &p, bool sparse) { return sparse && p.ksplit == 1; }
-
-// The kernel a set-up launch runs, family * 1000000 + template arguments (include/cskel.h, csk_gcn_stage_f32_route), or -1 with
-// the message set where no kernel takes the shape.  The ONE copy of the rule: gcn_stage_impl switches on it, the route query
-// reports it.  Host arithmetic: of the operands only the alignment is read (csk_gcn16_tile, csk_gcn_dense2_route).
-enum { ROUTE_UNIT = 1000000, ROUTE_SPARSE2 = 1, ROUTE_TILE16 = 2, ROUTE_DENSE2 = 3, ROUTE_DENSE128 = 4, ROUTE_GENERAL = 5 };
-// a split launch (p.ksplit > 1 ranges; gcn_stage_setup has refused everything but the sparse family): bit fields, csk_gcn_stage_splitk_f32_route
+// The ONE decision of a launch: the kernel it runs and what that launch takes beyond GcnParams.  gcn_stage_route fills it,
+// gcn_stage_impl switches on it, gcn_route_code turns it into the integers the route queries report (include/cskel.h).
+enum { ROUTE_SPARSE2 = 1, ROUTE_TILE16 = 2, ROUTE_DENSE2 = 3, ROUTE_DENSE128 = 4, ROUTE_GENERAL = 5 };
+// the bit fields csk_gcn_stage_splitk_f32_route reports for a split launch
 enum { ROUTE_SPLIT = 1 << 30, ROUTE_SPLIT_MT128 = 1 << 29, ROUTE_SPLIT_CONVRES = 1 << 28, ROUTE_SPLIT_RANGES_SHIFT = 23, ROUTE_SPLIT_CPER_MASK = (1 << 23) - 1 };
-static int gcn_stage_route(const GcnParams &p, bool sparse, int n_seg) {
-    const bool big = (p.Mpad % 128) == 0;
-    const int MT = big ? 128 : 64, NT = 16384 / MT, V = p.V;
-    if (p.ksplit > 1) {
-        if (p.cper / 8 > ROUTE_SPLIT_CPER_MASK) CSK_FAIL("gcn_stage_splitk: %d channels per range exceed the split launch", p.cper);
-        return ROUTE_SPLIT | (big ? ROUTE_SPLIT_MT128 : 0) | (p.R == 4 ? ROUTE_SPLIT_CONVRES : 0) | ((p.ksplit - 1) << ROUTE_SPLIT_RANGES_SHIFT) |
-               (p.cper / 8);
-    }
-    if (gcn16_candidate(p, sparse)) {     // slot-balanced 16x16x4 tiles where they pack the chip better (step16.hip; same sums)
-        if (const int tile = csk_gcn16_tile(p, n_seg)) return ROUTE_TILE16 * ROUTE_UNIT + tile;
-    }
-    if (sparse) return ROUTE_SPARSE2 * ROUTE_UNIT + MT * 10 + (p.R == 4 ? 1 : 0);
-    // dense per-sample / per-frame adjacency at V = 18 / 25: on-the-fly aggregation from register-resident adjacency
-    // columns (gcn_dense.hip); every other dense shape continues below
-    if (p.dense) {
-        if (const int d2 = csk_gcn_dense2_route(p, n_seg)) return ROUTE_DENSE2 * ROUTE_UNIT + d2;
-    }
-    // dense per-segment adjacency (A-GCN clip form): aggregation on the matrix pipe, frame-aligned tiles
-    // (128-row tiles only: on the 64-row tiles of the C_out = 64 layers the VALU aggregation of the general kernel measured
-    // 0.31 ms per launch against 0.34 ms for this form -- profiles/r03a_agcn_clip_layers.md vs r03b)
-    if (big && p.dense && !p.adj_per_frame && V >= 4 && V <= 32 && NT / V >= 1 && p.frames * (int64_t)V >= 4) {
-        const int ft = NT / V;
-        if ((int64_t)((p.frames + ft - 1) / ft) * p.mtiles * n_seg >= (1ll << 31)) CSK_FAIL("gcn_stage: grid too large");
-        return ROUTE_DENSE128 * ROUTE_UNIT + (p.R == 4 ? 1 : 0);
-    }
-    // activation staging sweeps per row: whole frames of the tile only (no temporal halo), i.e. < NT + 2 V positions:
-    // <= 256 for 128-wide and <= 384 for 256-wide tiles at V <= 64 -- 3-4 / 5-6 sweeps of 64 lanes (all spill-free)
-    const int nj = (p.ldb + 63) / 64;
-    if (nj > (big ? 4 : 6)) CSK_FAIL("gcn_stage: activation tile of %d positions per channel exceeds the staged maximum", p.ldb);
-    return ROUTE_GENERAL * ROUTE_UNIT + MT * 10 + (big ? (nj <= 3 ? 3 : 4) : (nj <= 5 ? 5 : 6));
-}
+struct GcnRoute {
+    int family;           // ROUTE_*
+    int MT;               // rows of a workgroup tile, 128 or 64
+    bool convres;         // conv gcn_residual: a fourth operand subset
+    int NJ;               // ROUTE_GENERAL: gcn_stage_kernel<MT, NJ>
+    int tile16;           // ROUTE_TILE16: csk_gcn16_tile's value (0 in every other family)
+    int dense2;           // ROUTE_DENSE2: csk_gcn_dense2_route's value
+    int ranges, cper;     // ROUTE_SPARSE2: channel ranges of cper channels; > 1 range = the split launch and its reduction
+    // what the launch takes that is not in GcnParams (ROUTE_TILE16 / ROUTE_DENSE2: their launchers own it, nothing below is set)
+    unsigned grid;
+    size_t lds;
+    int lds_frames, ldb;  // ROUTE_DENSE128: the frame-aligned tiles, in place of the fields gcn_stage_setup gave p
+    unsigned qtiles;
+};
 
-static int gcn_stage_impl(const float *x, float *y, const float *w, const float *bias, const int32_t *ell_src,
-                          const float *ell_val, const int32_t *ell_cnt, int ell_w, int64_t adj_seg_stride,
-                          int adj_per_frame,
-                          int n_seg, int c_in, int c_out, int frames, int V, int64_t x_seg_stride,
-                          int64_t x_chan_stride, int64_t y_seg_stride, int64_t y_chan_stride, int res_mode,
-                          int ksplit, float *partial, void *stream) {
-    if (!x || !y || !w || !bias || !ell_src || !ell_val || !ell_cnt) CSK_FAIL("gcn_stage: null pointer");
-    GcnParams p;
+// Sets up the launch parameters of a call (gcn_stage_setup) and decides its route: 0, or -1 with the message set where a check
+// fails or no kernel takes the shape.  The one path of the two launch entries and the three queries.  Host arithmetic: of the
+// operands only the alignment is read (csk_gcn16_tile, csk_gcn_dense2_route), each of those rules asked once.
+static int gcn_stage_route(const GcnCall &c, GcnParams *out, GcnRoute *route) {
+    GcnParams &p = *out;
     size_t lds;
     bool sparse;
-    if (const int rc = gcn_stage_setup(x, y, w, bias, ell_src, ell_val, ell_cnt, ell_w, adj_seg_stride, adj_per_frame, n_seg, c_in, c_out, frames,
-                                       V, x_seg_stride, x_chan_stride, y_seg_stride, y_chan_stride, res_mode, ksplit, partial, &p, &lds, &sparse))
-        return rc;
-    const bool big = (p.Mpad % 128) == 0;
-    const int MT = big ? 128 : 64, NT = 16384 / MT;
-    const int Q = frames * V;
-    dim3 grid(p.qtiles * p.mtiles * n_seg);
-    const int route = gcn_stage_route(p, sparse, n_seg);
-    if (route < 0) return route;
-    const bool split = (route & ROUTE_SPLIT) != 0;
-    const int family = split ? ROUTE_SPARSE2 : route / ROUTE_UNIT;
-    if (family == ROUTE_TILE16) return csk_launch_gcn16(p, n_seg, stream);
-    if (family == ROUTE_SPARSE2) {
-        const int R = p.R;
-        size_t lds2;
-        void (*k)(GcnParams);
-        // ping-pong LDS, trickled loads, 3 workgroups / CU
-        lds2 = 2 * (size_t)(R * 8 * MT + 8 * p.ldb) * sizeof(float);
-        if (split) {
-            const bool big2 = (route & ROUTE_SPLIT_MT128) != 0, convres = (route & ROUTE_SPLIT_CONVRES) != 0;
-            const int ranges = ((route >> ROUTE_SPLIT_RANGES_SHIFT) & 31) + 1;
-            if ((int64_t)p.qtiles * p.mtiles * n_seg * ranges >= (1ll << 31)) CSK_FAIL("gcn_stage: grid too large");
-            grid = dim3(p.qtiles * p.mtiles * n_seg * ranges);
-            k = big2 ? (convres ? gcn_stage_sparse2_kernel<128, true, 8, false, true> : gcn_stage_sparse2_kernel<128, false, 8, false, true>)
-                     : (convres ? gcn_stage_sparse2_kernel<64, true, 8, false, true> : gcn_stage_sparse2_kernel<64, false, 8, false, true>);
-        } else {
-            k = big ? (R == 4 ? gcn_stage_sparse2_kernel<128, true, 8> : gcn_stage_sparse2_kernel<128, false, 8>)
-                    : (R == 4 ? gcn_stage_sparse2_kernel<64, true, 8> : gcn_stage_sparse2_kernel<64, false, 8>);
-        }
-        const int e = csk_ensure_lds((const void *)k, lds2);
-        if (e) return e;
-        hipLaunchKernelGGL(k, grid, dim3(NTHREADS), lds2, (hipStream_t)stream, p);
-        if (split) {
-            if (const int e2 = (int)hipGetLastError()) return e2;
-            const int64_t work = (int64_t)c_out * Q;
-            hipLaunchKernelGGL(gcn_reduce_kernel, dim3((unsigned)((work + 255) / 256), n_seg), dim3(256), 0, (hipStream_t)stream, p);
-        }
-        return (int)hipGetLastError();
+    GcnRoute r = {};
+    if (const int rc = gcn_stage_setup(c, &p, &r.MT, &lds, &sparse)) return rc;
+    const bool big = r.MT == 128;
+    const int NT = 16384 / r.MT, V = p.V, n_seg = c.n_seg;
+    r.convres = p.R == 4;
+    r.ranges = p.ksplit; r.cper = p.cper;
+    r.grid = p.qtiles * p.mtiles * n_seg;
+    if (p.ksplit > 1) {   // a split launch: gcn_stage_setup has refused everything but the sparse family
+        if (p.cper / 8 > ROUTE_SPLIT_CPER_MASK) CSK_FAIL("gcn_stage_splitk: %d channels per range exceed the split launch", p.cper);
+        if ((int64_t)r.grid * r.ranges >= (1ll << 31)) CSK_FAIL("gcn_stage: grid too large");
+        r.family = ROUTE_SPARSE2;
+        r.grid *= r.ranges;
+    } else if (sparse && (r.tile16 = csk_gcn16_tile(p, n_seg)) != 0) {
+        r.family = ROUTE_TILE16;   // slot-balanced 16x16x4 tiles where they pack the chip better (step16.hip; same sums)
+    } else if (sparse) {
+        r.family = ROUTE_SPARSE2;
+    } else if (p.dense && (r.dense2 = csk_gcn_dense2_route(p, n_seg)) != 0) {
+        // dense per-sample / per-frame adjacency at V = 18 / 25: on-the-fly aggregation from register-resident adjacency
+        // columns (gcn_dense.hip); every other dense shape continues below
+        r.family = ROUTE_DENSE2;
+    } else if (big && p.dense && !p.adj_per_frame && V >= 4 && V <= 32 && NT / V >= 1 && p.frames * (int64_t)V >= 4) {
+        // dense per-segment adjacency (A-GCN clip form): aggregation on the matrix pipe, frame-aligned tiles
+        // (128-row tiles only: on the 64-row tiles of the C_out = 64 layers the VALU aggregation of the general kernel measured
+        // 0.31 ms per launch against 0.34 ms for this form -- profiles/r03a_agcn_clip_layers.md vs r03b)
+        r.family = ROUTE_DENSE128;
+        r.lds_frames = NT / V;                                  // FT: whole frames per tile
+        r.ldb = round_up(r.lds_frames * V, 4);
+        if ((r.ldb / 4) % 2 == 0) r.ldb += 4;                   // row stride = 4 (mod 8) words: the row-block reads are at most 2-way conflicted
+        r.qtiles = (p.frames + r.lds_frames - 1) / r.lds_frames;
+        if ((int64_t)r.qtiles * p.mtiles * n_seg >= (1ll << 31)) CSK_FAIL("gcn_stage: grid too large");
+        r.grid = r.qtiles * p.mtiles * n_seg;
+        r.lds = (size_t)(p.R * 8 * r.MT + 3 * 8 * NT + 8 * r.ldb + 3 * V * V) * sizeof(float);
+    } else {
+        // activation staging sweeps per row: whole frames of the tile only (no temporal halo), i.e. < NT + 2 V positions:
+        // <= 256 for 128-wide and <= 384 for 256-wide tiles at V <= 64 -- 3-4 / 5-6 sweeps of 64 lanes (all spill-free)
+        const int nj = (p.ldb + 63) / 64;
+        if (nj > (big ? 4 : 6)) CSK_FAIL("gcn_stage: activation tile of %d positions per channel exceeds the staged maximum", p.ldb);
+        r.family = ROUTE_GENERAL;
+        r.NJ = big ? (nj <= 3 ? 3 : 4) : (nj <= 5 ? 5 : 6);
+        r.lds = lds;
     }
-    if (family == ROUTE_DENSE2) return csk_launch_gcn_dense2(p, n_seg, stream);
-    if (family == ROUTE_DENSE128) {
-        const int KC2 = 8;
-        p.lds_frames = NT / V;                                  // FT: whole frames per tile
-        int ldbx = round_up(p.lds_frames * V, 4);
-        if ((ldbx / 4) % 2 == 0) ldbx += 4;                     // row stride = 4 (mod 8) words: the row-block reads are at most 2-way conflicted
-        p.ldb = ldbx;
-        p.qtiles = (frames + p.lds_frames - 1) / p.lds_frames;
-        const size_t ldsd = (size_t)(p.R * KC2 * MT + 3 * KC2 * NT + KC2 * ldbx + 3 * V * V) * sizeof(float);
-        void (*kd)(GcnParams) = p.R == 4 ? gcn_stage_dense_kernel<128, true, 8, 3> : gcn_stage_dense_kernel<128, false, 8, 3>;
-        if (const int e = csk_ensure_lds((const void *)kd, ldsd)) return e;
-        hipLaunchKernelGGL(kd, dim3(p.qtiles * p.mtiles * n_seg), dim3(NTHREADS), ldsd, (hipStream_t)stream, p);
-        return (int)hipGetLastError();
+    // ping-pong LDS, trickled loads, 3 workgroups / CU
+    if (r.family == ROUTE_SPARSE2) r.lds = 2 * (size_t)(p.R * 8 * r.MT + 8 * p.ldb) * sizeof(float);
+    *route = r;
+    return 0;
+}
+
+// What the queries report for a route (include/cskel.h): family * 1000000 + template arguments (csk_gcn_stage_f32_route), the bit
+// fields of a split launch (csk_gcn_stage_splitk_f32_route).  Nothing in the library reads these integers back.
+static int gcn_route_code(const GcnRoute &r) {
+    if (r.ranges > 1)
+        return ROUTE_SPLIT | (r.MT == 128 ? ROUTE_SPLIT_MT128 : 0) | (r.convres ? ROUTE_SPLIT_CONVRES : 0) | ((r.ranges - 1) << ROUTE_SPLIT_RANGES_SHIFT) |
+               (r.cper / 8);
+    const int args = r.family == ROUTE_TILE16 ? r.tile16 : r.family == ROUTE_DENSE2 ? r.dense2 : r.family == ROUTE_DENSE128 ? (int)r.convres :
+                     r.MT * 10 + (r.family == ROUTE_GENERAL ? r.NJ : (int)r.convres);
+    return r.family * 1000000 + args;
+}
+
+template <bool SPLIT>
+static auto gcn_sparse2_kernel_of(const GcnRoute &r) -> void (*)(GcnParams) {
+    if (r.MT == 128) return r.convres ? gcn_stage_sparse2_kernel<128, true, 8, false, SPLIT> : gcn_stage_sparse2_kernel<128, false, 8, false, SPLIT>;
+    return r.convres ? gcn_stage_sparse2_kernel<64, true, 8, false, SPLIT> : gcn_stage_sparse2_kernel<64, false, 8, false, SPLIT>;
+}
+
+static int gcn_stage_impl(const GcnCall &c, void *stream) {
+    if (!c.x || !c.y || !c.w || !c.bias || !c.ell_src || !c.ell_val || !c.ell_cnt) CSK_FAIL("gcn_stage: null pointer");
+    GcnParams p;
+    GcnRoute r;
+    if (const int rc = gcn_stage_route(c, &p, &r)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    void (*kern)(GcnParams);
+    switch (r.family) {
+        case ROUTE_TILE16: return csk_launch_gcn16(p, c.n_seg, r.tile16, stream);
+        case ROUTE_DENSE2: return csk_launch_gcn_dense2(p, c.n_seg, r.dense2, stream);
+        case ROUTE_SPARSE2: kern = r.ranges > 1 ? gcn_sparse2_kernel_of<true>(r) : gcn_sparse2_kernel_of<false>(r); break;
+        case ROUTE_DENSE128:
+            p.lds_frames = r.lds_frames; p.ldb = r.ldb; p.qtiles = r.qtiles;
+            kern = r.convres ? gcn_stage_dense_kernel<128, true, 8, 3> : gcn_stage_dense_kernel<128, false, 8, 3>;
+            break;
+        default:
+            kern = r.MT == 128 ? (r.NJ == 3 ? gcn_stage_kernel<128, 3> : gcn_stage_kernel<128, 4>)
+                               : (r.NJ == 5 ? gcn_stage_kernel<64, 5> : gcn_stage_kernel<64, 6>);
     }
-    const int nj = route % 10;
-    void (*kern)(GcnParams) = big ? (nj == 3 ? gcn_stage_kernel<128, 3> : gcn_stage_kernel<128, 4>)
-                                  : (nj == 5 ? gcn_stage_kernel<64, 5> : gcn_stage_kernel<64, 6>);
-    if (const int e = csk_ensure_lds((const void *)kern, lds)) return e;
-    hipLaunchKernelGGL(kern, grid, dim3(NTHREADS), lds, (hipStream_t)stream, p);
+    if (const int e = csk_ensure_lds((const void *)kern, r.lds)) return e;
+    hipLaunchKernelGGL(kern, dim3(r.grid), dim3(NTHREADS), r.lds, s, p);
+    if (r.ranges > 1) {
+        if (const int e = (int)hipGetLastError()) return e;
+        const int64_t work = (int64_t)c.c_out * c.frames * c.V;
+        hipLaunchKernelGGL(gcn_reduce_kernel, dim3((unsigned)((work + 255) / 256), c.n_seg), dim3(256), 0, s, p);
+    }
     return (int)hipGetLastError();
+}
+
+// the three queries: no operand but ell_cnt is dereferenced, so only that one is refused when null
+static int gcn_stage_query(const GcnCall &c, GcnRoute *r) {
+    if (!c.ell_cnt) CSK_FAIL("gcn_stage: null pointer");
+    GcnParams p;
+    return gcn_stage_route(c, &p, r);
 }
 
 extern "C" int csk_gcn_stage_f32(const float *x, float *y, const float *w, const float *bias, const int32_t *ell_src,
@@ -933,37 +960,30 @@ extern "C" int csk_gcn_stage_f32(const float *x, float *y, const float *w, const
                                  int n_seg, int c_in, int c_out, int frames, int V, int64_t x_seg_stride,
                                  int64_t x_chan_stride, int64_t y_seg_stride, int64_t y_chan_stride, int res_mode,
                                  void *stream) {
-    return gcn_stage_impl(x, y, w, bias, ell_src, ell_val, ell_cnt, ell_w, adj_seg_stride, adj_per_frame, n_seg, c_in, c_out, frames,
-                          V, x_seg_stride, x_chan_stride, y_seg_stride, y_chan_stride, res_mode, 1, nullptr, stream);
+    const GcnCall c = {x, y, w, bias, ell_src, ell_val, ell_cnt, ell_w, adj_seg_stride, adj_per_frame, n_seg, c_in, c_out, frames, V,
+                       x_seg_stride, x_chan_stride, y_seg_stride, y_chan_stride, res_mode, 1, nullptr};
+    return gcn_stage_impl(c, stream);
 }
 
 extern "C" int csk_gcn_stage_f32_tile(const float *x, const float *y, const int32_t *ell_cnt, int ell_w, int64_t adj_seg_stride,
                                       int adj_per_frame, int n_seg, int c_in, int c_out, int frames, int V, int64_t x_seg_stride,
                                       int64_t x_chan_stride, int64_t y_seg_stride, int64_t y_chan_stride, int res_mode) {
-    if (!ell_cnt) CSK_FAIL("gcn_stage: null pointer");
-    GcnParams p;
-    size_t lds;
-    bool sparse;
-    if (const int rc = gcn_stage_setup(x, const_cast<float *>(y), nullptr, nullptr, nullptr, nullptr, ell_cnt, ell_w, adj_seg_stride, adj_per_frame,
-                                       n_seg, c_in, c_out, frames, V, x_seg_stride, x_chan_stride, y_seg_stride, y_chan_stride, res_mode, 1,
-                                       nullptr, &p, &lds, &sparse))
-        return rc;
-    return gcn16_candidate(p, sparse) ? csk_gcn16_tile(p, n_seg) : 0;
+    const GcnCall c = {x, const_cast<float *>(y), nullptr, nullptr, nullptr, nullptr, ell_cnt, ell_w, adj_seg_stride, adj_per_frame, n_seg, c_in,
+                       c_out, frames, V, x_seg_stride, x_chan_stride, y_seg_stride, y_chan_stride, res_mode, 1, nullptr};
+    GcnRoute r;
+    if (const int rc = gcn_stage_query(c, &r)) return rc;
+    return r.tile16;
 }
 
 extern "C" int csk_gcn_stage_f32_route(const float *x, const float *y, const float *ell_val, const int32_t *ell_cnt, int ell_w,
                                        int64_t adj_seg_stride, int adj_per_frame, int n_seg, int c_in, int c_out, int frames, int V,
                                        int64_t x_seg_stride, int64_t x_chan_stride, int64_t y_seg_stride, int64_t y_chan_stride,
                                        int res_mode) {
-    if (!ell_cnt) CSK_FAIL("gcn_stage: null pointer");
-    GcnParams p;
-    size_t lds;
-    bool sparse;
-    if (const int rc = gcn_stage_setup(x, const_cast<float *>(y), nullptr, nullptr, nullptr, ell_val, ell_cnt, ell_w, adj_seg_stride, adj_per_frame,
-                                       n_seg, c_in, c_out, frames, V, x_seg_stride, x_chan_stride, y_seg_stride, y_chan_stride, res_mode, 1,
-                                       nullptr, &p, &lds, &sparse))
-        return rc;
-    return gcn_stage_route(p, sparse, n_seg);
+    const GcnCall c = {x, const_cast<float *>(y), nullptr, nullptr, nullptr, ell_val, ell_cnt, ell_w, adj_seg_stride, adj_per_frame, n_seg, c_in,
+                       c_out, frames, V, x_seg_stride, x_chan_stride, y_seg_stride, y_chan_stride, res_mode, 1, nullptr};
+    GcnRoute r;
+    if (const int rc = gcn_stage_query(c, &r)) return rc;
+    return gcn_route_code(r);
 }
 
 // what the split entry and its route query refuse before anything else
@@ -976,15 +996,11 @@ extern "C" int csk_gcn_stage_splitk_f32_route(const float *x, const float *y, co
                                               int c_in, int c_out, int frames, int V, int64_t x_seg_stride, int64_t x_chan_stride,
                                               int64_t y_seg_stride, int64_t y_chan_stride, int res_mode, int ksplit, const float *partial) {
     if (const int rc = gcn_splitk_args(ksplit, partial)) return rc;
-    if (!ell_cnt) CSK_FAIL("gcn_stage: null pointer");
-    GcnParams p;
-    size_t lds;
-    bool sparse;
-    if (const int rc = gcn_stage_setup(x, const_cast<float *>(y), nullptr, nullptr, nullptr, ell_val, ell_cnt, ell_w, 0, 0, n_seg, c_in, c_out, frames,
-                                       V, x_seg_stride, x_chan_stride, y_seg_stride, y_chan_stride, res_mode, ksplit, const_cast<float *>(partial),
-                                       &p, &lds, &sparse))
-        return rc;
-    return gcn_stage_route(p, sparse, n_seg);
+    const GcnCall c = {x, const_cast<float *>(y), nullptr, nullptr, nullptr, ell_val, ell_cnt, ell_w, 0, 0, n_seg, c_in, c_out, frames, V,
+                       x_seg_stride, x_chan_stride, y_seg_stride, y_chan_stride, res_mode, ksplit, const_cast<float *>(partial)};
+    GcnRoute r;
+    if (const int rc = gcn_stage_query(c, &r)) return rc;
+    return gcn_route_code(r);
 }
 
 extern "C" int csk_gcn_stage_splitk_f32(const float *x, float *y, const float *w, const float *bias, const int32_t *ell_src,
@@ -992,8 +1008,9 @@ extern "C" int csk_gcn_stage_splitk_f32(const float *x, float *y, const float *w
                                         int frames, int V, int64_t x_seg_stride, int64_t x_chan_stride, int64_t y_seg_stride,
                                         int64_t y_chan_stride, int res_mode, int ksplit, float *partial, void *stream) {
     if (const int rc = gcn_splitk_args(ksplit, partial)) return rc;
-    return gcn_stage_impl(x, y, w, bias, ell_src, ell_val, ell_cnt, ell_w, 0, 0, n_seg, c_in, c_out, frames, V, x_seg_stride,
-                          x_chan_stride, y_seg_stride, y_chan_stride, res_mode, ksplit, partial, stream);
+    const GcnCall c = {x, y, w, bias, ell_src, ell_val, ell_cnt, ell_w, 0, 0, n_seg, c_in, c_out, frames, V,
+                       x_seg_stride, x_chan_stride, y_seg_stride, y_chan_stride, res_mode, ksplit, partial};
+    return gcn_stage_impl(c, stream);
 }
 
 
@@ -1006,21 +1023,18 @@ extern "C" int csk_conv1x1_f32(const float *x, float *y, const float *w, const f
                                int64_t y_chan_stride, void *stream) {
     if (!x || !y || !w || !bias) CSK_FAIL("conv1x1: null pointer");
     if (n_seg <= 0 || c_in <= 0 || c_out <= 0 || frames <= 0 || V < 2 || V > 64) CSK_FAIL("conv1x1: bad dims");
-    if ((int64_t)frames * V >= (1 << 26)) CSK_FAIL("conv1x1: frames*V too large for 32-bit position arithmetic");
     const int32_t no_adjacency[3] = {0, 0, 0};
-    GcnParams p = gcn_params(x, y, w, bias, nullptr, nullptr, no_adjacency, 1, 0, c_in, c_out, frames, V, x_seg_stride, x_chan_stride,
-                             y_seg_stride, y_chan_stride, CSK_RES_NONE, nullptr);
+    const GcnCall c = {x, y, w, bias, nullptr, nullptr, no_adjacency, 1, 0, 0, n_seg, c_in, c_out, frames, V,
+                       x_seg_stride, x_chan_stride, y_seg_stride, y_chan_stride, CSK_RES_NONE, 1, nullptr};
+    GcnParams p = gcn_params(c);
     p.R = 1;                                               // one operand subset: the conv itself
-    const bool big = (p.Mpad % 128) == 0;
-    const int MT = big ? 128 : 64, NT = 16384 / MT;
-    const int max_dt = (NT + V - 2) / V;
-    p.ldb = round_up((max_dt + 1) * V, 4);
+    if (const int rc = GcnTile::positions_guard(p, "conv1x1")) return rc;
+    const GcnTile tile(p);
+    const bool big = tile.MT == 128;
     if (p.ldb > (big ? 192 : 320)) CSK_FAIL("conv1x1: activation tile of %d positions exceeds the staged maximum", p.ldb);
-    const int Q = frames * V;
-    p.qtiles = (Q + NT - 1) / NT; p.mtiles = p.Mpad / MT;
-    if ((int64_t)p.qtiles * p.mtiles * n_seg >= (1ll << 31)) CSK_FAIL("conv1x1: grid too large");
+    if (const int rc = GcnTile::grid_guard(p, n_seg, "conv1x1")) return rc;
     constexpr int KCP = 16;                                // channels per chunk: 32 MFMAs per wave and barrier
-    const size_t lds = 2 * (size_t)(KCP * MT + KCP * p.ldb) * sizeof(float);
+    const size_t lds = 2 * (size_t)(KCP * tile.MT + KCP * p.ldb) * sizeof(float);
     void (*k)(GcnParams) = big ? gcn_stage_sparse2_kernel<128, false, KCP, true> : gcn_stage_sparse2_kernel<64, false, KCP, true>;
     if (const int e = csk_ensure_lds((const void *)k, lds)) return e;
     hipLaunchKernelGGL(k, dim3(p.qtiles * p.mtiles * n_seg), dim3(NTHREADS), lds, (hipStream_t)stream, p);

@@ -303,8 +303,8 @@ static int launch_dense2(const GcnParams &p, int n_seg, hipStream_t stream) {
 }
 
 // The instantiation gcn_stage_dense2_kernel<MT, CONVRES, V, 8> a launch runs, as MT * 1000 + V * 10 + CONVRES; 0: not a shape
-// this file is built for.  The ONE copy of the rule: the launcher below switches on it, csk_gcn_stage_f32_route reports it.  Host
-// arithmetic: of p.x / p.ell_val only the alignment is read.
+// this file is built for.  The ONE copy of the rule, asked once per launch (gcn_stage_route, gcn.hip): the launcher below is handed
+// the value, csk_gcn_stage_f32_route reports it.  Host arithmetic: of p.x / p.ell_val only the alignment is read.
 int csk_gcn_dense2_route(const GcnParams &p, int n_seg) {
     // built for the two skeleton layouts of the reference's datasets: V = 18 (Kinetics / OpenPose) and V = 25 (NTU RGB+D)
     if (!p.dense || (p.V != 18 && p.V != 25) || p.frames < 1) return 0;
@@ -320,9 +320,7 @@ int csk_gcn_dense2_route(const GcnParams &p, int n_seg) {
     return MT * 1000 + p.V * 10 + (p.R == 4 ? 1 : 0);
 }
 
-int csk_launch_gcn_dense2(GcnParams p, int n_seg, void *stream) {
-    const int route = csk_gcn_dense2_route(p, n_seg);
-    if (!route) return -2;
+int csk_launch_gcn_dense2(GcnParams p, int n_seg, int route, void *stream) {
     const int MT = route / 1000, V = route / 10 % 100, FT = 128 / V;
     const bool convres = route % 10 != 0;
     p.lds_frames = FT;

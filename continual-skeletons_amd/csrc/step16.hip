@@ -454,7 +454,8 @@ int csk_launch_tcn_step16(StepParams p, int n_emit, void *stream) {
 // Graph conv: bitwise the sums of gcn_stage_sparse2_kernel, so the choice IS a throughput policy of the launch shape: taken
 // where the cost model says the launch packs the chip better (CSK_GCN16=2 under CSK_DIAG=1: whenever the shape is supported).
 // The instantiation gcn16_kernel<NB, F, CONVRES, 8> as NB * 1000 + F * 100 + CONVRES * 10, 0: the launch keeps the 32x32x2 tiles.
-// The ONE copy of the rule: the launcher below switches on it, csk_gcn_stage_f32_tile reports it.
+// The ONE copy of the rule, asked once per launch (gcn_stage_route, gcn.hip): the launcher below is handed the value,
+// csk_gcn_stage_f32_tile reports it.
 int csk_gcn16_tile(const GcnParams &p, int n_seg) {
     const int mode = csk_diag_int("CSK_GCN16");
     if (mode == 1) return 0;
@@ -477,9 +478,7 @@ int csk_gcn16_tile(const GcnParams &p, int n_seg) {
     return best_nb * 1000 + F * 100 + (p.R == 4 ? 10 : 0);
 }
 
-int csk_launch_gcn16(GcnParams p, int n_seg, void *stream) {
-    const int tile = csk_gcn16_tile(p, n_seg);
-    if (!tile) return -2;
+int csk_launch_gcn16(GcnParams p, int n_seg, int tile, void *stream) {
     const int best_nb = tile / 1000, F = tile / 100 % 10;
     hipStream_t s = (hipStream_t)stream;
 #define CSK_G16(NB_) (F == 4 ? launch_gcn16<NB_, 4>(p, n_seg, s) : F == 2 ? launch_gcn16<NB_, 2>(p, n_seg, s) : launch_gcn16<NB_, 1>(p, n_seg, s))
@@ -523,8 +522,9 @@ int csk_launch_co_stack16(int n_blocks, const csk_co_block_args *b, int n_skel, 
         const csk_co_block_args &a = b[i];
         // what co_block_cycle hands the two stage entries, but ring slots for slot runs and (no residual) the input ring as xres
         GcnParams &g = sp.b[i].g;
-        g = gcn_params(a.xin, a.y_ring, a.gcn_w, a.gcn_bias, a.ell_src, a.ell_val, a.ell_cnt, a.ell_w, 0, a.c_in, a.c_out, n_skel, V,
-                       (int64_t)a.c_in * P, P, (int64_t)a.c_out * P, P, a.gcn_res_mode, nullptr);
+        const GcnCall call = {a.xin, a.y_ring, a.gcn_w, a.gcn_bias, a.ell_src, a.ell_val, a.ell_cnt, a.ell_w, 0, 0, 1, a.c_in, a.c_out, n_skel, V,
+                              (int64_t)a.c_in * P, P, (int64_t)a.c_out * P, P, a.gcn_res_mode, 1, nullptr};
+        g = gcn_params(call);
         g.mtiles = 1; g.qtiles = (unsigned)((Q + NP - 1) / NP);
         g.x_ring_slots = a.xin_slots; g.x_ring_slot0 = a.xin_slot0; g.y_ring_slots = a.y_slots; g.y_ring_slot0 = a.y_slot0;
         StepParams &t = sp.b[i].t;

@@ -389,6 +389,102 @@ def test_gcn_route_query_and_dense_guards_without_a_gpu():
     assert b"V <= 32" in lib.csk_last_error()
 
 
+def _gcn_route_tables(lib):
+    """The answers of the three graph-conv route queries over a shape grid, in grid order: {query: [int or refusal text, ...]}.
+    Grid: V x c_out x residual x adjacency x ell_cnt x operand alignment x n_seg x frames (x ksplit for the split query, which
+    takes shared adjacencies only); ell_w = max(ell_cnt), contiguous channel-major layouts, conv residual from c_in = 40."""
+    import ctypes as C
+    import itertools
+    out = {"route": [], "tile": [], "split": []}
+
+    def said(rc):
+        return rc if rc >= 0 else lib.csk_last_error().decode()
+    for V, c_out, res, cnt, off, n_seg, frames in itertools.product((18, 25, 20, 4, 32, 41, 64), (40, 64, 100, 128, 192, 256), (1, 2),
+                                                                    ((1, 1, 4), (2, 1, 4), (1, 1, 5), None), (0, 4), (1, 2, 4, 1024),
+                                                                    (1, 7, 8, 300)):
+        cnt = cnt or (V, V, V)
+        ell_w, c_in, q = max(cnt), (c_out if res == 1 else 40), frames * V
+        cp = C.cast((C.c_int32 * 3)(*cnt), C.c_void_p)
+        x, y, ell = C.c_void_p(0x10000 + off), C.c_void_p(0x10000), C.c_void_p(0x20000 + off)
+        geom = (n_seg, c_in, c_out, frames, V, c_in * q, q, c_out * q, q, res)
+        for stride, per_frame in ((0, 0), (3 * V * ell_w, 0), (3 * V * ell_w, 1)):          # shared, per segment, per frame
+            out["route"].append(said(lib.csk_gcn_stage_f32_route(x, y, ell, cp, ell_w, stride, per_frame, *geom)))
+            out["tile"].append(said(lib.csk_gcn_stage_f32_tile(x, y, cp, ell_w, stride, per_frame, *geom)))
+        for ksplit in (1, 4, 32, 33):
+            out["split"].append(said(lib.csk_gcn_stage_splitk_f32_route(x, y, ell, cp, ell_w, *geom, ksplit, y)))
+    return out
+
+
+# What the library of the commit before GcnCall / GcnRoute answered over _gcn_route_tables' grid: per query the number of cases behind
+# every distinct answer (route integers as include/cskel.h defines them, refusals by their full text) and the SHA-256 of the answers
+# in grid order, one per line.  Recorded from that library, not from the one under test.
+_LDS = "gcn_stage: LDS tile %d B exceeds 160 KiB"
+_REFUSED = {**{_LDS % b: 96 for b in (173056, 222764, 227328, 233004, 235520, 335872, 346112)},
+            "gcn_stage: ell_w must be in [1, V]": 1152,
+            "gcn_stage: per-frame adjacency must be dense (ell_w == V, ell_cnt == V)": 7680}
+_GCN_ROUTE_TABLE = {
+    "route": ({1000640: 543, 1000641: 543, 1001280: 548, 1001281: 548,
+               2018400: 28, 2018410: 28, 2025400: 33, 2025410: 33,
+               3064180: 96, 3064181: 96, 3064250: 192, 3064251: 192, 3128180: 96, 3128181: 96, 3128250: 192, 3128251: 192,
+               4000000: 336, 4000001: 336,
+               5000645: 7968, 5000646: 1536, 5001283: 7392, 5001284: 1728, **_REFUSED},
+              "6d35b974c4d933111a63f9e3083e1397e463878c6cf9326bd10a4a34f3f112af"),
+    "tile": ({0: 22630, 18400: 28, 18410: 28, 25400: 33, 25410: 33, **_REFUSED},
+             "38b1554c77e0049dbe494f29da766a83cd82c1b1395c4046927704ac1a1e9137"),
+    "split": ({1000640: 543, 1000641: 543, 1001280: 548, 1001281: 548,
+               2018400: 28, 2018410: 28, 2025400: 33, 2025410: 33,
+               5000645: 3264, 5000646: 768, 5001283: 3264, 5001284: 768,
+               # (1 << 30) | MT128 << 29 | CONVRES << 28 | (ranges - 1) << 23 | cper / 8
+               1090519042: 192, 1098907650: 192, 1098907654: 192, 1107296257: 192, 1132462081: 192, 1266679809: 192,
+               1358954498: 576, 1375731713: 576, 1635778564: 384, 1635778568: 192, 1711276033: 192, 1736441857: 192,
+               1870659585: 192, 1895825410: 576, 1912602625: 576,
+               "gcn_stage: ell_w must be in [1, V]": 1152,
+               "gcn_stage_splitk: ksplit must be in [1, 32] and needs a partial-sum buffer": 10752,
+               "gcn_stage_splitk: split-K is built for the skeleton-sparse kernel (shared adjacency, <= 1/1/4 non-zeros per column)": 16128},
+              "2654cfef03c10b2f1f6b47e285e1cc457cdf5ed642c75f3eff95fa195dc4e438"),
+}
+
+
+def test_gcn_route_queries_keep_every_answer_and_refusal_text_over_the_shape_grid():
+    """csk_gcn_stage_f32_route, csk_gcn_stage_f32_tile and csk_gcn_stage_splitk_f32_route answer every shape of the grid -- the joint
+    counts of every family, ragged and full c_out, both residuals, shared / per-segment / per-frame adjacencies, sparse and dense
+    entry counts, misaligned operands, 1 to 1024 segments, 1 to 300 frames, splits in and out of range -- with the literal integers
+    and the literal refusal texts recorded before the host path was restructured: the same count of cases behind every answer and
+    the same answer for every case (digest of the grid-ordered list)."""
+    import collections
+    import hashlib
+    got = _gcn_route_tables(pkg.native.lib())
+    assert set(got) == set(_GCN_ROUTE_TABLE)
+    for query, (counts, digest) in _GCN_ROUTE_TABLE.items():
+        tally = dict(collections.Counter(got[query]))
+        assert tally == counts, (query, sorted(set(tally.items()) ^ set(counts.items()), key=str))
+        assert hashlib.sha256("\n".join(map(str, got[query])).encode()).hexdigest() == digest, query
+
+
+def test_conv1x1_refusals_keep_their_text():
+    """csk_conv1x1_f32 shares its tile geometry and guards with the graph-conv stage but speaks under its own name: every refusal
+    with its full text, in the order of the checks, nothing launched."""
+    import ctypes as C
+    lib = pkg.native.lib()
+    fake = C.c_void_p(0x1000)
+
+    def conv(x=fake, y=fake, w=fake, b=fake, n_seg=2, c_in=16, c_out=128, frames=8, V=25):
+        q = frames * V
+        rc = lib.csk_conv1x1_f32(x, y, w, b, n_seg, c_in, c_out, frames, V, c_in * q, q, c_out * q, q, None)
+        return rc, lib.csk_last_error()
+    for null in "xywb":
+        assert conv(**{null: None}) == (-1, b"conv1x1: null pointer"), null
+    for bad in (dict(n_seg=0), dict(c_in=0), dict(c_out=0), dict(frames=0), dict(V=1), dict(V=65)):
+        assert conv(**bad) == (-1, b"conv1x1: bad dims"), bad
+    assert conv(frames=1 << 20, V=64) == (-1, b"conv1x1: frames*V too large for 32-bit position arithmetic")
+    # an activation row holds the whole frames a tile touches: 4 x 63 = 252 positions on 128-row tiles, over the 192 staged there
+    # (V = 64 fits exactly: 3 x 64 = 192, and would launch); this check comes before the grid's
+    assert conv(V=63) == (-1, b"conv1x1: activation tile of 252 positions exceeds the staged maximum")
+    assert conv(V=63, n_seg=1 << 30, frames=1 << 10) == (-1, b"conv1x1: activation tile of 252 positions exceeds the staged maximum")
+    assert conv(V=25, n_seg=1 << 30, frames=1 << 10) == (-1, b"conv1x1: grid too large")
+    assert conv(V=25, c_out=64, n_seg=1 << 30, frames=1 << 10) == (-1, b"conv1x1: grid too large")
+
+
 def test_set_precision_marks_blocks_and_refolds():
     m = pkg.StGcn(pkg.ntu_graph().A)
     assert all(b.precision == "f32" for b in m.layers.values())
