@@ -3,11 +3,14 @@
 Counterpart of ``AdaptiveGraphConvolution`` (models/a_gcn/a_gcn.py:12-69), ``AGcn`` (a_gcn.py:72-145) and
 ``CoAGcn`` (models/coa_gcn/coa_gcn.py).  The graph conv aggregates with a PER-SAMPLE dense adjacency
     adj_i = softmax_{dim=-2}( a_i(x)^T b_i(x) / (inter*T) ) + (A + graph_attn)_i        (a_gcn.py:50-63)
-Three launches: (1) the six 1x1 embedding convs as ONE fused 1x1 conv (tcn stage / step kernel), (2)
-``csk_agcn_attention_f32`` -> dense column-wise adjacency values per sample, (3) the general GCN stage kernel
-with ``adj_seg_stride`` (aggregation on VALU from LDS-staged tables, channel mixing on MFMA).
-Clip mode: one V x V matrix per sample over all T; continual mode (CoAGCN): T = 1, i.e. per-frame attention --
-clip != step by design (a_gcn.py:60-61, coa_gcn.py:31).
+``AdaptiveGraphConvolution._adjacency`` forms the dense column-wise adjacency values and owns the choice between its two routes:
+the two-launch one -- the six 1x1 embedding convs as ONE ``csk_conv1x1_f32``, then ``csk_agcn_attention_f32`` -- and the fused
+``csk_agcn_embed_attention_f32`` (embedding convs and logits in one launch) at the shapes it is built for.  ``_graph_conv`` applies
+them: the general GCN stage kernel with ``adj_seg_stride`` (aggregation on VALU from LDS-staged tables, channel mixing on MFMA).
+Three callers state a geometry each.  ``forward``, clip mode: one V x V matrix per sample over all T.  ``stage``, continual mode
+(CoAGCN): T = 1, i.e. per-frame attention -- clip != step by design (a_gcn.py:60-61, coa_gcn.py:31).  ``forward_framewise``: a
+whole clip at the steps' arithmetic, one matrix per (sample, frame) -- the frame-wise kernel ``csk_agcn_stage_framewise_f32``
+(adjacencies never reach memory) where it is built and measured faster, else the per-frame launches on chunks of frames.
 """
 import torch
 import torch.nn as nn
@@ -58,36 +61,54 @@ class AdaptiveGraphConvolution(GraphConvolution):
         native.check(rc, "csk_agcn_attention_f32")
         return adj
 
+    def _adjacency(self, x, ops, n_seg, frames, x_strides, per_frame, fuse=True, row=None):
+        """The dense adjacencies of ``n_seg`` segments of ``frames`` frames of ``x`` (segment and channel stride ``x_strides``):
+        one (3, V, V) per segment over all its frames -- the clip form -- or with ``per_frame`` one per (segment, frame),
+        segment-major.  THE place that picks the launches: csk_agcn_embed_attention_f32 (embedding convs + logits in one launch)
+        where ``fuse``, the caller's own gate, and ``_fused_ok`` allow it, else the embeddings E through csk_conv1x1_f32 (the six
+        1x1 convs as one) and csk_agcn_attention_f32.  ``row``: floats of a segment's embedding row in E (default frames * V;
+        ``stage``: the padded row of its rings)."""
+        v, c, e_ch = ops["V"], self.in_channels, 6 * self.inter_c
+        n_adj = n_seg * frames if per_frame else n_seg
+        if fuse and self._fused_ok(v, x.data_ptr(), *x_strides):
+            adj = torch.empty((n_adj, 3, v, v), device=x.device, dtype=torch.float32)
+            ft = 128 // v                              # frames per tile of the kernel: the clip form sums a partial logit of each
+            scratch = None if per_frame else torch.empty((n_seg, 3, (frames + ft - 1) // ft, v, v), device=x.device, dtype=torch.float32)
+            rc = native.lib().csk_agcn_embed_attention_f32(
+                native.ptr(x), native.ptr(ops["w_embed_pairs"]), native.ptr(ops["b_embed_pairs"]), native.ptr(ops["a_sum"]),
+                native.ptr(adj), native.ptr(scratch), n_seg, c, self.inter_c, frames, v, int(per_frame), x_strides[0], x_strides[1],
+                native.stream_of(x))
+            native.check(rc, "csk_agcn_embed_attention_f32")
+            return adj
+        row = frames * v if row is None else row
+        if per_frame:
+            E = torch.empty((n_seg, e_ch, row), device=x.device, dtype=torch.float32)
+        else:       # (N, 6*inter, T, V), + 4 floats of slack behind it (the clip form of csk_agcn_attention_f32 reads whole 16-byte vectors)
+            E = torch.empty((n_seg * e_ch * row + 4,), device=x.device, dtype=torch.float32)[: n_seg * e_ch * row].view(n_seg, e_ch, frames, v)
+        rc = native.lib().csk_conv1x1_f32(native.ptr(x), native.ptr(E), native.ptr(ops["w_embed"]), native.ptr(ops["b_embed"]), n_seg, c,
+                                          e_ch, frames, v, x_strides[0], x_strides[1], e_ch * row, row, native.stream_of(x))
+        native.check(rc, "csk_conv1x1_f32")
+        if per_frame:   # every (segment, frame) its own "sample" of T = 1: V floats apart in a row, a segment's rows e_ch * row apart
+            return self._attention(E, ops, n_adj, 1, v, v, row, seg_per_group=frames, e_group_stride=e_ch * row)
+        return self._attention(E, ops, n_seg, frames, v, e_ch * row, row)
+
+    @staticmethod
+    def _graph_conv(x, y, ops, adj, n_seg, frames, x_strides, y_strides, per_frame):
+        """The general GCN stage kernel on ``x`` into ``y`` with the adjacencies ``adj`` of ``_adjacency`` as the ELL values."""
+        blocks.gcn_stage(x, y, dict(ops, ell_val=adj), n_seg=n_seg, frames=frames, x_strides=x_strides, y_strides=y_strides,
+                         adj_seg_stride=3 * ops["V"] * ops["V"], adj_per_frame=int(per_frame))
+
     def forward(self, x):
         self._require_eval()
         _check_input(x, self.in_channels, "AdaptiveGraphConvolution input")
         ops = self._packed_ops(x.device)
         n, c, t, v = x.shape
-        e_ch = 6 * self.inter_c
+        xs, ys = (c * t * v, t * v), (self.out_channels * t * v, t * v)
         y = torch.empty((n, self.out_channels, t, v), device=x.device, dtype=torch.float32)
         # (V = 25: the fused clip form measured SLOWER than GEMM + logits kernels -- 28.0 vs 24.2 ms per NTU batch-64 forward: five
         # frames per tile, joints staged one by one -- so it is used at V = 18 only; the step form gains 4 % at V = 25 too)
-        if v == 18 and self._fused_ok(v, x.data_ptr(), c * t * v, t * v):
-            # embedding convs + partial logits in one launch, softmax in a second (csk_agcn_embed_attention_f32, per-segment form)
-            adj = torch.empty((n, 3, v, v), device=x.device, dtype=torch.float32)
-            ft = 128 // v                              # frames per tile of the kernel
-            scratch = torch.empty((n, 3, (t + ft - 1) // ft, v, v), device=x.device, dtype=torch.float32)
-            rc = native.lib().csk_agcn_embed_attention_f32(
-                native.ptr(x), native.ptr(ops["w_embed_pairs"]), native.ptr(ops["b_embed_pairs"]), native.ptr(ops["a_sum"]),
-                native.ptr(adj), native.ptr(scratch), n, c, self.inter_c, t, v, 0, c * t * v, t * v, native.stream_of(x))
-            native.check(rc, "csk_agcn_embed_attention_f32")
-            blocks.gcn_stage(x, y, dict(ops, ell_val=adj), n_seg=n, frames=t, x_strides=(c * t * v, t * v),
-                             y_strides=(self.out_channels * t * v, t * v), adj_seg_stride=3 * v * v)
-            return y
-        # (N, 6*inter, T, V), + 4 floats of slack behind it (csk_agcn_attention_f32 reads whole 16-byte vectors)
-        E = torch.empty((n * e_ch * t * v + 4,), device=x.device, dtype=torch.float32)[: n * e_ch * t * v].view(n, e_ch, t, v)
-        rc = native.lib().csk_conv1x1_f32(native.ptr(x), native.ptr(E), native.ptr(ops["w_embed"]), native.ptr(ops["b_embed"]), n, c,
-                                          e_ch, t, v, c * t * v, t * v, e_ch * t * v, t * v, native.stream_of(x))
-        native.check(rc, "csk_conv1x1_f32")
-        adj = self._attention(E, ops, n, t, v, e_ch * t * v, t * v)
-        o = dict(ops, ell_val=adj)
-        blocks.gcn_stage(x, y, o, n_seg=n, frames=t, x_strides=(c * t * v, t * v),
-                         y_strides=(self.out_channels * t * v, t * v), adj_seg_stride=3 * v * v)
+        adj = self._adjacency(x, ops, n, t, xs, per_frame=False, fuse=v == 18)
+        self._graph_conv(x, y, ops, adj, n, t, xs, ys, per_frame=False)
         return y
 
     fuse_embed_attention = True     # False: two launches (csk_conv1x1_f32 + csk_agcn_attention_f32) -- for A/B measurements
@@ -136,71 +157,41 @@ class AdaptiveGraphConvolution(GraphConvolution):
                 self.out_channels * t * v, t * v, ops["res_mode"], native.stream_of(x))
             native.check(rc, "csk_agcn_stage_framewise_f32")
             return y
-        e_ch = 6 * self.inter_c
         xs, ys = (c * t * v, t * v), (self.out_channels * t * v, t * v)
         fused = self._fused_ok(v, x.data_ptr(), *xs)    # (a chunk starts t0 * V floats into a row: even for even V)
-        chunk = max(1, int(self.framewise_budget_bytes // (4 * n * (3 * v * v + (0 if fused else e_ch * v)))))
+        chunk = max(1, int(self.framewise_budget_bytes // (4 * n * (3 * v * v + (0 if fused else 6 * self.inter_c * v)))))
         for t0 in range(0, t, chunk):
             f = min(chunk, t - t0)
             xc, yc = x[:, :, t0:], y[:, :, t0:]         # frames t0 .. of every channel: same strides, f frames taken
-            if fused:
-                adj = torch.empty((n * f, 3, v, v), device=x.device, dtype=torch.float32)
-                rc = native.lib().csk_agcn_embed_attention_f32(
-                    native.ptr(xc), native.ptr(ops["w_embed_pairs"]), native.ptr(ops["b_embed_pairs"]), native.ptr(ops["a_sum"]),
-                    native.ptr(adj), None, n, c, self.inter_c, f, v, 1, xs[0], xs[1], native.stream_of(x))
-                native.check(rc, "csk_agcn_embed_attention_f32")
-            else:
-                E = torch.empty((n, e_ch, f * v), device=x.device, dtype=torch.float32)
-                rc = native.lib().csk_conv1x1_f32(native.ptr(xc), native.ptr(E), native.ptr(ops["w_embed"]), native.ptr(ops["b_embed"]), n, c,
-                                                  e_ch, f, v, xs[0], xs[1], e_ch * f * v, f * v, native.stream_of(x))
-                native.check(rc, "csk_conv1x1_f32")
-                adj = self._attention(E, ops, n * f, 1, v, v, f * v, seg_per_group=f, e_group_stride=e_ch * f * v)
-            blocks.gcn_stage(xc, yc, dict(ops, ell_val=adj), n_seg=n, frames=f, x_strides=xs, y_strides=ys,
-                             adj_seg_stride=3 * v * v, adj_per_frame=1)
+            adj = self._adjacency(xc, ops, n, f, xs, per_frame=True, fuse=fused)
+            self._graph_conv(xc, yc, ops, adj, n, f, xs, ys, per_frame=True)
         return y
 
+    def _fused_shape(self, v):
+        """Shapes csk_agcn_embed_attention_f32 is built for (and the A/B switch)."""
+        return self.fuse_embed_attention and v in (18, 25) and self.inter_c in (16, 32, 64)
+
     def _fused_ok(self, v, data_ptr, seg_stride, chan_stride):
-        """Shapes csk_agcn_embed_attention_f32 is built for (even V: 8-byte aligned activation rows)."""
-        if not self.fuse_embed_attention or v not in (18, 25) or self.inter_c not in (16, 32, 64):
-            return False
-        return v % 2 == 1 or (data_ptr % 8 == 0 and seg_stride % 2 == 0 and chan_stride % 2 == 0)
+        """``_fused_shape`` and what the entry asks of the operand (even V: 8-byte aligned activation rows)."""
+        return self._fused_shape(v) and (v % 2 == 1 or (data_ptr % 8 == 0 and seg_stride % 2 == 0 and chan_stride % 2 == 0))
 
     def plan_operands(self, device):
         """Operands of the native step executor (csk_co_layer.agcn_*: the per-frame form of csk_agcn_embed_attention_f32), or
         None where that entry is not built (V not in {18, 25}, inter not in {16, 32, 64}): such stacks keep the Python engine."""
         ops = self._packed_ops(device)
-        if not self.fuse_embed_attention or ops["V"] not in (18, 25) or self.inter_c not in (16, 32, 64):
+        if not self._fused_shape(ops["V"]):
             return None
         return dict(inter=self.inter_c, w_pairs=ops["w_embed_pairs"], b_pairs=ops["b_embed_pairs"], a_sum=ops["a_sum"])
 
     def stage(self, x, y, n_seg, frames, x_strides, y_strides):
         """Continual use on channel-major frames (C, P): every skeleton is its own 'sample' with T = 1, so the
         attention is computed per skeleton and frame (coa_gcn.py: forward_stepping of the module) and the graph
-        conv runs with a per-frame adjacency.  The n_seg consecutive ring slots of a launch cycle go through three
-        launches together: embedding conv (one emission per slot), attention, graph conv (one segment per slot)."""
+        conv runs with a per-frame adjacency.  The n_seg consecutive ring slots of a launch cycle go through the launches of
+        ``_adjacency`` together (segment = ring slot, frames = skeletons, one embedding row of P floats per slot), then the graph
+        conv: adjacency per "frame" of a segment (= skeleton), index seg * frames + skeleton."""
         ops = self._packed_ops(x.device)
-        v, p = ops["V"], x_strides[1]
-        e_ch = 6 * self.inter_c
-        if self._fused_ok(v, x.data_ptr(), x_strides[0], p):
-            # embedding convs + attention in one launch (csk_agcn_embed_attention_f32, per-frame form), then the graph conv
-            adj = torch.empty((n_seg * frames, 3, v, v), device=x.device, dtype=torch.float32)
-            rc = native.lib().csk_agcn_embed_attention_f32(
-                native.ptr(x), native.ptr(ops["w_embed_pairs"]), native.ptr(ops["b_embed_pairs"]), native.ptr(ops["a_sum"]),
-                native.ptr(adj), None, n_seg, self.in_channels, self.inter_c, frames, v, 1, x_strides[0], p, native.stream_of(x))
-            native.check(rc, "csk_agcn_embed_attention_f32")
-            blocks.gcn_stage(x, y, dict(ops, ell_val=adj), n_seg=n_seg, frames=frames, x_strides=x_strides, y_strides=y_strides,
-                             adj_seg_stride=3 * v * v, adj_per_frame=1)
-            return
-        E = torch.empty((n_seg, e_ch, p), device=x.device, dtype=torch.float32)
-        # the fused 1x1 embedding conv on the channel-major slots: segment = ring slot, frames = skeletons
-        rc = native.lib().csk_conv1x1_f32(native.ptr(x), native.ptr(E), native.ptr(ops["w_embed"]), native.ptr(ops["b_embed"]), n_seg,
-                                          self.in_channels, e_ch, frames, v, x_strides[0], p, e_ch * p, p, native.stream_of(x))
-        native.check(rc, "csk_conv1x1_f32")
-        adj = self._attention(E, ops, n_seg * frames, 1, v, v, p, seg_per_group=frames, e_group_stride=e_ch * p)
-        o = dict(ops, ell_val=adj)
-        # segment = one channel-major frame, adjacency per "frame" of it (= skeleton): index seg * frames + skeleton
-        blocks.gcn_stage(x, y, o, n_seg=n_seg, frames=frames, x_strides=x_strides, y_strides=y_strides,
-                         adj_seg_stride=3 * v * v, adj_per_frame=1)
+        adj = self._adjacency(x, ops, n_seg, frames, x_strides, per_frame=True, row=x_strides[1])
+        self._graph_conv(x, y, ops, adj, n_seg, frames, x_strides, y_strides, per_frame=True)
 
 
 class AdaptiveGraphConvolutionMod(GraphConvolution):
@@ -287,16 +278,7 @@ class CoAGcn(CoStGcn):
         x = self._intake_clip(x)
         native.require_device_f32(x, "CoAGcn input")
         _, d = self._prepare_clip_as_stepped(x)
-        n, c, t, v, m = d.shape
-        ops = self._packed_ops(x.device)
-        h = torch.empty((n * m, c, t, v), device=x.device, dtype=torch.float32)
-        rc = native.lib().csk_input_norm_f32(native.ptr(d), native.ptr(ops["scale"]), native.ptr(ops["shift"]), native.ptr(h),
-                                             n, c, t, v, m, c * t * v, t * v, native.stream_of(x))
-        native.check(rc, "csk_input_norm_f32")
-        for blk in self._blocks:
-            # the two stages of SpatioTemporalBlock.forward_parts, the first one frame-wise
-            h = blocks.SpatioTemporalBlock._tail(blk, h, blk.gcn.forward_framewise(h), None)
-        return h
+        return self._through_blocks(self.input_norm(d), lambda blk, h: self._framewise_parts(blk, h)[1])
 
     def forward_clip_as_steps(self, x, pad_end=False):
         """(N, C, T, V, M) -> (N, classes, n_predictions): what ``clean_state(); forward_steps(x, pad_end)`` returns (within the
@@ -325,15 +307,13 @@ class CoAGcn(CoStGcn):
             # window slots first .. first + w - 1 of the array; the `count` newest end at entry `last`
             native.check(lib.csk_co_window_mean_f32(native.ptr(ring[first]), native.ptr(pooled[k]), n * 256, w, last - first,
                                                     last - first + 1, stream), "csk_co_window_mean_f32")
-        logits = torch.empty((len(entries), n, self.num_classes), device=x.device, dtype=torch.float32)
-        native.check(lib.csk_fc_f32(native.ptr(pooled), native.ptr(self.fc.weight.detach()), native.ptr(self.fc.bias.detach()),
-                                    native.ptr(logits), len(entries) * n, 256, self.num_classes, stream), "csk_fc_f32")
-        return logits.permute(1, 2, 0).contiguous()
+        return self._fc(pooled).permute(1, 2, 0).contiguous()
 
     # ---- priming from buffered history at the steps' arithmetic (DESIGN.md sections 3e, 3h) ------------------------------
     @staticmethod
     def _framewise_parts(blk, h):
-        """``(y, out)`` of a block with the attention formed per frame: the two stages ``features_clip_as_steps`` composes."""
+        """``(y, out)`` of a block with the attention formed per frame: the two stages of ``SpatioTemporalBlock.forward_parts``,
+        the first one frame-wise.  What ``features_clip_as_steps`` walks the stack with and ``prime_state_as_steps`` keeps."""
         y = blk.gcn.forward_framewise(h)
         return y, blocks.SpatioTemporalBlock._tail(blk, h, y, None)
 

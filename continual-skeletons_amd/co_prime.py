@@ -114,16 +114,15 @@ class StreamPrime:
         two clip stages, or a caller's form of them whose tensors are the steps' (agcn.py: the frame-wise graph conv)."""
         x = self._intake_clip(x)
         n, c, t, v, m = x.shape
-        ops = self._packed_ops(x.device)
         entered, d = self._prepare_clip_as_stepped(x)
-        h = torch.empty((n * m, c, t, v), device=x.device, dtype=torch.float32)
-        rc = native.lib().csk_input_norm_f32(native.ptr(d), native.ptr(ops["scale"]), native.ptr(ops["shift"]), native.ptr(h),
-                                             n, c, t, v, m, c * t * v, t * v, native.stream_of(x))
-        native.check(rc, "csk_input_norm_f32")
-        clip = {co_rings.XIN0: h}                       # the clip tensors under the names the rings' ``source`` asks for
-        for blk, (y_name, out_name) in zip(self._blocks, co_rings.block_ring_names(len(self._blocks))):
-            clip[y_name], h = parts(blk, h)
-            clip[out_name] = h
+        clip = {co_rings.XIN0: self.input_norm(d)}      # the clip tensors under the names the rings' ``source`` asks for
+        names = iter(co_rings.block_ring_names(len(self._blocks)))
+
+        def keep_parts(blk, h):
+            y_name, out_name = next(names)
+            clip[y_name], clip[out_name] = parts(blk, h)
+            return clip[out_name]
+        self._through_blocks(clip[co_rings.XIN0], keep_parts)
         small = {}
         for stage in reversed(entered):                 # record order (``_record_stages``)
             small.update(stage.prime(entered[stage], t))

@@ -924,10 +924,14 @@ class CoStGcn(NativePlan, SlabRings, StreamReset, StreamMove, StreamPrime, ClipA
         rc = native.lib().csk_pool_scaled_f32(native.ptr(hs), native.ptr(feat), n, m, 256, take * v,
                                               take / self.pool_size, native.stream_of(x))
         native.check(rc, "csk_pool_scaled_f32")
-        logits = torch.empty((n, self.num_classes), device=x.device, dtype=torch.float32)
-        native.check(native.lib().csk_fc_f32(native.ptr(feat), native.ptr(self.fc.weight.detach()),
-                                             native.ptr(self.fc.bias.detach()), native.ptr(logits), n, 256,
-                                             self.num_classes, native.stream_of(x)), "csk_fc_f32")
+        return self._fc(feat)
+
+    def _fc(self, feat):
+        """co.Linear on pooled features, (..., 256) -> (..., classes): the last launch of every clip-side continual head."""
+        logits = torch.empty(feat.shape[:-1] + (self.num_classes,), device=feat.device, dtype=torch.float32)
+        rc = native.lib().csk_fc_f32(native.ptr(feat), native.ptr(self.fc.weight.detach()), native.ptr(self.fc.bias.detach()),
+                                     native.ptr(logits), feat.numel() // 256, 256, self.num_classes, native.stream_of(feat))
+        native.check(rc, "csk_fc_f32")
         return logits
 
     def _clip_features(self, x):
@@ -936,15 +940,8 @@ class CoStGcn(NativePlan, SlabRings, StreamReset, StreamMove, StreamPrime, ClipA
 
     def _clip_stack(self, x):
         """Input norm and the ten clip blocks on the derived frames ``x`` (N, C, T, V, M) -> (N*M, 256, T', V)."""
-        n, c, t, v, m = x.shape
-        ops = self._packed_ops(x.device)
-        h = torch.empty((n * m, c, t, v), device=x.device, dtype=torch.float32)
-        rc = native.lib().csk_input_norm_f32(native.ptr(x), native.ptr(ops["scale"]), native.ptr(ops["shift"]),
-                                             native.ptr(h), n, c, t, v, m, c * t * v, t * v, native.stream_of(x))
-        native.check(rc, "csk_input_norm_f32")
-        for blk in self._blocks:
-            h = SpatioTemporalBlock.forward(blk, h)
-        return h
+        # SpatioTemporalBlock.forward by name: the clip computation, whatever a continual block's own ``forward`` is
+        return self._through_blocks(self.input_norm(x), SpatioTemporalBlock.forward)
 
     def warm_up(self, n, device, frames=None):
         """Feed ``receptive_field - padding - 1`` random frames (models/base.py:144-159) so that the next

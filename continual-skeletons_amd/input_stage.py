@@ -196,6 +196,27 @@ class InputChain:
                 x = stage.clip_as_stepped(x)
         return entered, x
 
+    # ---- behind the pre-passes: the head of every clip pass (a model: ``_Folded`` with scale / shift, ``layers``) ----
+    def input_norm(self, x):
+        """(N, C, T, V, M) -> (N*M, C, T, V): permute + data_bn (models/st_gcn/st_gcn.py:49-57) of the clip the blocks run on."""
+        native.require_device_f32(x, f"{type(self).__name__} input")
+        n, c, t, v, m = x.shape
+        ops = self._packed_ops(x.device)
+        if ops["scale"].numel() != m * v * c:
+            raise RuntimeError(f"input (C,V,M)=({c},{v},{m}) does not match data_bn with {ops['scale'].numel()} channels")
+        h = torch.empty((n * m, c, t, v), device=x.device, dtype=torch.float32)
+        rc = native.lib().csk_input_norm_f32(native.ptr(x), native.ptr(ops["scale"]), native.ptr(ops["shift"]),
+                                             native.ptr(h), n, c, t, v, m, c * t * v, t * v, native.stream_of(x))
+        native.check(rc, "csk_input_norm_f32")
+        return h
+
+    def _through_blocks(self, h, block):
+        """``h`` through the blocks in stack order; ``block(blk, h)`` is one block's output and the next one's input.  The
+        caller names the per-block call: ``__call__``, the clip ``forward`` of a continual block, a form that keeps parts."""
+        for blk in self.layers.values():
+            h = block(blk, h)
+        return h
+
     def _stage_frames(self, frames, update=True):
         """A cycle's frames through the whole chain (all off: the list itself)."""
         for stage in self.stages:

@@ -84,24 +84,9 @@ class StGcn(InputChain, _Folded):
     def _watched(self):       # only the driver's own folded tensors; blocks keep their own caches
         return [self.data_bn]
 
-    def input_norm(self, x):
-        """(N, C, T, V, M) -> (N*M, C, T, V): permute + data_bn (models/st_gcn/st_gcn.py:49-57)."""
-        native.require_device_f32(x, "StGcn input")
-        n, c, t, v, m = x.shape
-        ops = self._packed_ops(x.device)
-        if ops["scale"].numel() != m * v * c:
-            raise RuntimeError(f"input (C,V,M)=({c},{v},{m}) does not match data_bn with {ops['scale'].numel()} channels")
-        h = torch.empty((n * m, c, t, v), device=x.device, dtype=torch.float32)
-        rc = native.lib().csk_input_norm_f32(native.ptr(x), native.ptr(ops["scale"]), native.ptr(ops["shift"]),
-                                             native.ptr(h), n, c, t, v, m, c * t * v, t * v, native.stream_of(x))
-        native.check(rc, "csk_input_norm_f32")
-        return h
-
     def features(self, x):
         h = self.input_norm(self._prepare_clip(x))      # the pre-passes on channel-first input; all off: x itself
-        for i in range(len(self.layers)):
-            h = self.layers[f"layer{i + 1}"](h)
-        return h
+        return self._through_blocks(h, lambda blk, h: blk(h))       # through __call__: hooks and a subclass's forward hold
 
     def head(self, h, n, m):
         """mean over (T, V), mean over M, fc (models/st_gcn/st_gcn.py:60-64)."""

@@ -97,4 +97,4 @@ for i, blk in enumerate(net._blocks):
     flop = 2.0 * n * t * v * (6 * inter * ci + 3 * inter * v + r * co * ci)
     print(f"AGCN_FRAMEWISE_AB {shape} layer {i + 1} ({ci} -> {co}, T {t}, route {route}, shipped: {'kernel' if g.framewise_route(h) else 'composed'}): composed {b:.3f} ms, kernel {c:.3f} ms, "
           f"{b / c:.3f}x; kernel at {flop / (c * 1e-3) / PEAK:.3f} of the fp32 MFMA peak", flush=True)
-    h = pkg.blocks.SpatioTemporalBlock._tail(blk, h, g.forward_framewise(h), None)
+    h = net._framewise_parts(blk, h)[1]
