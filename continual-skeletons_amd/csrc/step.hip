@@ -13,7 +13,7 @@
 // positions, so the GEMM is  D[co, p] = sum_r sum_c W[r][c][co] * ring[(head - 8 + r) % slots][c][p].
 // Zero-initialised slots reproduce the zero left-padding of the clip conv (models/base.py:307-334 semantics).
 // (A bare CoTemporalConvolution uses the same kernel on a ring of exactly k slots.)
-// The kernels here are the 32x32x2 tiles, for the launches csk_launch_tcn_step16 does not take: split-K (latency mode), k != 9,
+// The kernels here are the 32x32x2 tiles, for the launches csk_tcn_step16_tile does not take: split-K (latency mode), k != 9,
 // P < 8, rings >= 4 GB.  Every other temporal step, and the fused block / stack step (csk_co_block_step_f32,
 // csk_co_stack_step_f32), runs on the tiles of step16.hip.
 #include <type_traits>
@@ -367,20 +367,52 @@ __global__ void co_window_mean_kernel(const float *__restrict__ ring, float *__r
 // ------------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------------
-// What csk_tcn_step_f32 requires of the launch SHAPE (no pointer, no slot index): 0, or -1 with the message set.  x_res_slots is
-// read for a launch with a residual only.  Shared with csk_tcn_step_f32_tile.
-static int check_step_shape(int slots, int head_step, int n_emit, int x_res_slots, int out_slots, int c, int c_out, int64_t P, int k,
-                            int res_mode, int c_res, int ksplit) {
-    if (ksplit < 1 || ksplit > 32) CSK_FAIL("tcn_step: ksplit must be in [1, 32] and needs a partial-sum buffer");
-    if (c <= 0 || c_out <= 0 || P < 4 || (P & 3)) CSK_FAIL("tcn_step: bad dims (P must be a positive multiple of 4)");
-    if (k < 1 || k > 9 || slots < k) CSK_FAIL("tcn_step: bad k/slots/head");
-    if (n_emit < 1 || n_emit > 64 || head_step < 0 || out_slots < n_emit) CSK_FAIL("tcn_step: bad emission geometry");
-    if (slots < k - 1 + (n_emit - 1) * head_step + 1) CSK_FAIL("tcn_step: ring too shallow for %d emissions", n_emit);
-    if (P >= (1ll << 31) - 256) CSK_FAIL("tcn_step: P too large");
-    if (res_mode != CSK_RES_NONE) {
-        if (x_res_slots < 1) CSK_FAIL("tcn_step: bad residual ring geometry");
-        if (res_mode == CSK_RES_IDENTITY && c_res != c_out) CSK_FAIL("tcn_step: identity residual needs c_res == c_out");
+// The ONE decision of a launch, asked once: step_route makes it, csk_tcn_step_f32 launches from it, csk_tcn_step_f32_route reports it.
+enum { STEP_TILE16 = 1, STEP_TILE32 = 2 };      // family: tcn_step16_kernel (step16.hip), code = csk_tcn_step16_tile's value | tcn_step_kernel, code = step_code
+struct StepRoute { int family, code; unsigned gx, gy, gz; int64_t grid; };     // STEP_TILE32: position tiles, m-tiles, emission groups * ranges; their product
+constexpr int step_code(int MT, int E, int HS, bool SPLIT, bool K9, int OCC) { return MT * 100000 + E * 10000 + HS * 1000 + SPLIT * 100 + K9 * 10 + OCC; }
+
+// Every k = 9, unsplit launch whose rings fit 32-bit byte offsets runs on the slot-balanced 16x16x4 tiles (step16.hip), whatever its size: that
+// family has its own fp32 summation order.  The others run tcn_step_kernel<MT, E, HS, SPLIT, K9, OCC>: the ONE copy of that rule.  Host arithmetic.
+static StepRoute step_route(const StepParams &p, int n_emit) {
+    if (const int tile = csk_tcn_step16_tile(p, n_emit)) return {STEP_TILE16, tile};
+    const bool big = (p.Mpad % 128) == 0, split = p.ksplit > 1, k9 = p.K == 9;
+    const int MT = big ? 128 : 64;
+    // emissions folded into a workgroup tile: the largest E in {4, 2, 1} that divides n_emit and leaves >= 64 positions
+    // per emission (a wave's 64 columns must belong to one emission); stride-2 launches only as 128-row tiles of two
+    // emissions (the only stride-2 shapes of the ST-GCN stack); k != 9, and split-K on the 64-row tiles, use the plain tile.
+    int E = 1;
+    if (k9 && !big && p.head_step == 1 && !split) E = (n_emit % 4 == 0) ? 4 : (n_emit % 2 == 0) ? 2 : 1;
+    if (k9 && big && p.head_step >= 1 && p.head_step <= 2) E = (n_emit % 2 == 0) ? 2 : 1;      // also with split-K
+    const int HS = big && E == 2 ? p.head_step : 1, NP = 16384 / MT / E;
+    const unsigned gx = (unsigned)((p.P + NP - 1) / NP), gy = (unsigned)(p.Mpad / MT), gz = (unsigned)((n_emit / E) * p.ksplit);
+    const int64_t g = (int64_t)gx * gy * gz;
+    // The 64-row, four-emission form also exists within 168 registers (three workgroups per CU, 43 KB of LDS each): taken when
+    // the launch needs fewer rounds of 768 resident workgroups than of 512 (256 CUs) -- CoAGCN at the Kinetics shape is 576
+    // tiles per 64-channel block: one round instead of a full one plus an eighth.  A function of the launch size only.
+    const int OCC = !big && E == 4 && (g + 767) / 768 < (g + 511) / 512 ? 3 : 2;       // (E == 4: unsplit, k == 9)
+    return {STEP_TILE32, step_code(MT, E, HS, split, k9, OCC), gx, gy, gz, g};
+}
+
+struct StepKernel { void (*kern)(StepParams); size_t lds; };        // code -> kernel and LDS bytes of the 15 instantiations step_route can name
+static StepKernel step_kernel_of(int code) {
+    switch (code) {
+#define CSK_STEP32(MT, E, HS, ...) case step_code(MT, E, HS, __VA_ARGS__): return {tcn_step_kernel<MT, E, HS, __VA_ARGS__>, (9 * KC * MT + RingStage<16384 / MT / E, 8 + (E - 1) * HS + 1>::LDS_FLOATS) * sizeof(float)};
+        CSK_STEP32(128, 2, 2, true, true, 2) CSK_STEP32(128, 2, 1, true, true, 2) CSK_STEP32(128, 1, 1, true, true, 2) CSK_STEP32(128, 1, 1, true, false, 2)
+        CSK_STEP32(64, 1, 1, true, true, 2) CSK_STEP32(64, 1, 1, true, false, 2) CSK_STEP32(128, 2, 2, false, true, 2) CSK_STEP32(128, 2, 1, false, true, 2)
+        CSK_STEP32(128, 1, 1, false, true, 2) CSK_STEP32(128, 1, 1, false, false, 2) CSK_STEP32(64, 4, 1, false, true, 2) CSK_STEP32(64, 2, 1, false, true, 2)
+        CSK_STEP32(64, 1, 1, false, true, 2) CSK_STEP32(64, 1, 1, false, false, 2) CSK_STEP32(64, 4, 1, false, true, 3)
+#undef CSK_STEP32
     }
+    return {nullptr, 0};
+}
+
+// what only csk_tcn_step_f32 requires: the limits of its step_check (step_params.h)
+static int step_limits_f32(const StepCall &c, bool operands) {
+    if (c.ksplit < 1 || c.ksplit > 32 || (operands && c.ksplit > 1 && !c.partial)) CSK_FAIL("tcn_step: ksplit must be in [1, 32] and needs a partial-sum buffer");
+    if (c.k < 1 || c.k > 9) CSK_FAIL("tcn_step: bad k/slots/head");
+    if (c.head_step < 0) CSK_FAIL("tcn_step: bad emission geometry");
+    if (c.P >= (1ll << 31) - 256) CSK_FAIL("tcn_step: P too large");
     return 0;
 }
 
@@ -389,64 +421,19 @@ extern "C" int csk_tcn_step_f32(const float *ring, int slots, int head, int head
                                 const float *w_res, const float *bias, float *out, int out_slots, int out_slot0,
                                 int c, int c_out, int64_t P, int k, int res_mode, int c_res, int relu, int ksplit,
                                 float *partial, void *stream) {
-    if (!ring || !w || !bias || !out) CSK_FAIL("tcn_step: null pointer");
-    if (res_mode != CSK_RES_NONE && !x_res) CSK_FAIL("tcn_step: residual requested without x_res");
-    if (const int rc = check_step_shape(slots, head_step, n_emit, x_res_slots, out_slots, c, c_out, P, k, res_mode, c_res, ksplit)) return rc;
-    if (ksplit > 1 && !partial) CSK_FAIL("tcn_step: ksplit must be in [1, 32] and needs a partial-sum buffer");
-    if (head < 0 || head >= slots) CSK_FAIL("tcn_step: bad k/slots/head");
-    if (out_slot0 < 0 || out_slot0 >= out_slots) CSK_FAIL("tcn_step: bad emission geometry");
-    if (res_mode != CSK_RES_NONE) {
-        if (x_res_slot0 < 0 || x_res_slot0 >= x_res_slots || x_res_step < 0) CSK_FAIL("tcn_step: bad residual ring geometry");
-        if (res_mode == CSK_RES_CONV && !w_res) CSK_FAIL("tcn_step: conv residual without w_res");
-    }
-    if (((uintptr_t)ring | (uintptr_t)(x_res ? x_res : ring)) & 15) CSK_FAIL("tcn_step: state pointers must be 16-byte aligned");
-    // without x_res: the post-GCN ring as a one-slot stand-in
-    StepParams p = step_params(ring, slots, head, head_step, w, x_res ? x_res : ring, x_res ? x_res_slots : 1, x_res ? x_res_slot0 : 0,
-                               x_res_step, w_res, bias, out, out_slots, out_slot0, c, c_out, P, k, res_mode, c_res, relu);
-    p.ksplit = split_ranges(p.Cpad, c, ksplit, KC, &p.cper);
-    p.part = partial;
+    const StepCall call = {ring, slots, head, head_step, n_emit, w, x_res, x_res_slots, x_res_slot0, x_res_step, w_res, bias, out,
+                           out_slots, out_slot0, c, c_out, P, k, res_mode, c_res, relu, ksplit, partial};
+    if (const int rc = step_check("tcn_step", "k/slots/head", call, true, [&] { return step_limits_f32(call, true); })) return rc;
+    StepParams p = step_params(call);
+    const StepRoute r = step_route(p, n_emit);
     if (p.ksplit > 1 && ((uintptr_t)partial & 15)) CSK_FAIL("tcn_step: partial-sum buffer must be 16-byte aligned");
-    // every k = 9, unsplit launch whose rings fit 32-bit byte offsets runs on the slot-balanced 16x16x4 tiles (step16.hip),
-    // whatever its size: that family has its own fp32 summation order (-2: not one of those launches)
-    if (p.ksplit == 1) {
-        const int rc = csk_launch_tcn_step16(p, n_emit, stream);
-        if (rc != -2) return rc;
-    }
-    const bool big = (p.Mpad % 128) == 0;
-    const int MT = big ? 128 : 64, NT = 16384 / MT;
-    // emissions folded into a workgroup tile: the largest E in {4, 2, 1} that divides n_emit and leaves >= 64 positions
-    // per emission (a wave's 64 columns must belong to one emission); stride-2 launches only as 128-row tiles of two
-    // emissions (the only stride-2 shapes of the ST-GCN stack); split-K and the E = 1 form use the plain tile.
-    int E = 1;
-    if (k == 9) {
-        if (!big && head_step == 1 && p.ksplit == 1) E = (n_emit % 4 == 0) ? 4 : (n_emit % 2 == 0) ? 2 : 1;
-        if (big && head_step <= 2 && head_step >= 1) E = (n_emit % 2 == 0) ? 2 : 1;      // also with split-K
-    }
-    const int NP = NT / E;
-    void (*kern)(StepParams);
-    size_t stage_floats;
-    const bool k9 = k == 9;     // E > 1 implies k == 9 (folding condition above)
-#define CSK_PICK(MT_, E_, HS_, SP_) (kern = (E_ > 1 || k9) ? tcn_step_kernel<MT_, E_, HS_, SP_, true> : tcn_step_kernel<MT_, E_, HS_, SP_, (E_ > 1)>, stage_floats = RingStage<16384 / MT_ / E_, 8 + (E_ - 1) * HS_ + 1>::LDS_FLOATS)
-    if (p.ksplit > 1) {
-        if (big) E == 2 ? (head_step == 2 ? CSK_PICK(128, 2, 2, true) : CSK_PICK(128, 2, 1, true)) : CSK_PICK(128, 1, 1, true);
-        else CSK_PICK(64, 1, 1, true);
-    } else if (big) E == 2 ? (head_step == 2 ? CSK_PICK(128, 2, 2, false) : CSK_PICK(128, 2, 1, false)) : CSK_PICK(128, 1, 1, false);
-    else E == 4 ? CSK_PICK(64, 4, 1, false) : E == 2 ? CSK_PICK(64, 2, 1, false) : CSK_PICK(64, 1, 1, false);
-#undef CSK_PICK
-    const size_t lds = (size_t)(9 * KC * MT + stage_floats) * sizeof(float);
-    p.gx = (unsigned)((P + NP - 1) / NP); p.gy = (unsigned)(p.Mpad / MT); p.gz = (unsigned)((n_emit / E) * p.ksplit);
-    if ((int64_t)p.gx * p.gy * p.gz >= (1ll << 31)) CSK_FAIL("tcn_step: grid too large");
-    dim3 grid(p.gx * p.gy * p.gz);
-    // The 64-row, four-emission form also exists within 168 registers (three workgroups per CU, 43 KB of LDS each): taken when
-    // the launch needs fewer rounds of 768 resident workgroups than of 512 (256 CUs) -- CoAGCN at the Kinetics shape is 576
-    // tiles per 64-channel block: one round instead of a full one plus an eighth.  A function of the launch size only.
-    if (!big && E == 4 && p.ksplit == 1 && k9) {
-        const unsigned g = grid.x;
-        if ((g + 767) / 768 < (g + 511) / 512) kern = tcn_step_kernel<64, 4, 1, false, true, 3>;
-    }
+    if (r.family == STEP_TILE16) return csk_launch_tcn_step16(p, n_emit, r.code, stream);
+    if (r.grid >= (1ll << 31)) CSK_FAIL("tcn_step: grid too large");
+    p.gx = r.gx; p.gy = r.gy; p.gz = r.gz;
+    const StepKernel sk = step_kernel_of(r.code);
     hipStream_t s = (hipStream_t)stream;
-    if (const int e = csk_ensure_lds((const void *)kern, lds)) return e;
-    hipLaunchKernelGGL(kern, grid, dim3(NTHREADS), lds, s, p);
+    if (const int e = csk_ensure_lds((const void *)sk.kern, sk.lds)) return e;
+    hipLaunchKernelGGL(sk.kern, dim3((unsigned)r.grid), dim3(NTHREADS), sk.lds, s, p);
     if (p.ksplit > 1) {
         if (const int e = (int)hipGetLastError()) return e;
         const int64_t work = (int64_t)c_out * (P / 4);
@@ -455,15 +442,25 @@ extern "C" int csk_tcn_step_f32(const float *ring, int slots, int head, int head
     return (int)hipGetLastError();
 }
 
+// The query: the shape arguments of the entry as a call without operands (x_res_slots <= 0: no x_res; otherwise an x_res that is
+// there and never read), checked at the shape level and routed as the entry routes it
+extern "C" int csk_tcn_step_f32_route(int slots, int head_step, int n_emit, int x_res_slots, int out_slots, int c, int c_out, int64_t P,
+                                      int k, int res_mode, int c_res, int ksplit, int32_t *route) {
+    if (!route) CSK_FAIL("tcn_step_route: null route");
+    static const float there = 0.f;
+    const StepCall call = {nullptr, slots, 0, head_step, n_emit, nullptr, x_res_slots > 0 ? &there : nullptr, x_res_slots, 0, 0,
+                           nullptr, nullptr, nullptr, out_slots, 0, c, c_out, P, k, res_mode, c_res, 1, ksplit, nullptr};
+    if (const int rc = step_check("tcn_step", "k/slots/head", call, false, [&] { return step_limits_f32(call, false); })) return rc;
+    const StepRoute r = step_route(step_params(call), n_emit);
+    route[0] = r.family; route[1] = r.code; route[2] = r.grid < (1ll << 31) ? (int32_t)r.grid : -1;
+    return 0;
+}
+
 extern "C" int csk_tcn_step_f32_tile(int slots, int head_step, int n_emit, int x_res_slots, int out_slots, int c, int c_out, int64_t P,
                                      int k, int res_mode, int c_res, int ksplit) {
-    if (const int rc = check_step_shape(slots, head_step, n_emit, x_res_slots, out_slots, c, c_out, P, k, res_mode, c_res, ksplit)) return rc;
-    // the launch parameters of csk_tcn_step_f32 without their pointers and slot indices, which the choice does not read
-    // (x_res_slots <= 0: no x_res, the one-slot stand-in)
-    StepParams p = step_params(nullptr, slots, 0, head_step, nullptr, nullptr, x_res_slots > 0 ? x_res_slots : 1, 0, head_step, nullptr,
-                               nullptr, nullptr, out_slots, 0, c, c_out, P, k, res_mode, c_res, 1);
-    p.ksplit = split_ranges(p.Cpad, c, ksplit, KC, &p.cper);
-    return csk_tcn_step16_tile(p, n_emit);
+    int32_t route[CSK_STEP_ROUTE_WORDS];
+    if (const int rc = csk_tcn_step_f32_route(slots, head_step, n_emit, x_res_slots, out_slots, c, c_out, P, k, res_mode, c_res, ksplit, route)) return rc;
+    return route[0] == STEP_TILE16 ? route[1] : 0;
 }
 
 extern "C" int csk_co_spatial_pool_f32(const float *h, float *feat, int N, int C, int MV, int64_t P, void *stream) {

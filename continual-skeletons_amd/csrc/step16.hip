@@ -421,8 +421,8 @@ int launch16(StepParams p, int n_emit, bool tail, hipStream_t s) {
 // a different fp32 summation order -- so WHICH family runs must not depend on the launch size (a stream's results must not
 // depend on how many streams share the slab, nor on how many frames a launch carries): every k = 9, unsplit launch whose
 // rings fit 32-bit byte offsets takes this family; only the tile WIDTH (NB) follows the launch shape.
-// The instantiation tcn_step16_kernel<NB, E, HS, TAIL> of a launch as NB * 1000 + E * 100 + HS * 10 + TAIL, 0: not a launch of
-// this family.  The ONE copy of the rule: the launcher below switches on it, csk_tcn_step_f32_tile reports it.
+// The instantiation tcn_step16_kernel<NB, E, HS, TAIL> of a launch as NB * 1000 + E * 100 + HS * 10 + TAIL, 0: not a launch of this family.
+// The ONE copy of the rule, asked once per launch (step_route, step.hip): the launcher below is handed the value, the queries report it.
 int csk_tcn_step16_tile(const StepParams &p, int n_emit) {
     if (p.K != 9 || p.ksplit != 1 || p.head_step < 1 || p.head_step > 2) return 0;
     // 32-bit byte offsets inside the rings
@@ -440,11 +440,8 @@ int csk_tcn_step16_tile(const StepParams &p, int n_emit) {
     return best_nb * 1000 + E * 100 + HS * 10 + (tail ? 1 : 0);
 }
 
-int csk_launch_tcn_step16(StepParams p, int n_emit, void *stream) {
-    const int tile = csk_tcn_step16_tile(p, n_emit);
-    if (!tile) return -2;
-    const int best_nb = tile / 1000, E = tile / 100 % 10, HS = tile / 10 % 10;
-    const bool tail = tile % 10 != 0;
+int csk_launch_tcn_step16(StepParams p, int n_emit, int tile, void *stream) {
+    const int best_nb = tile / 1000, E = tile / 100 % 10, HS = tile / 10 % 10, tail = tile % 10;
     hipStream_t s = (hipStream_t)stream;
 #define CSK_L16(NB_) (E == 4 ? launch16<NB_, 4, 1>(p, n_emit, tail, s) : E == 2 ? (HS == 2 ? launch16<NB_, 2, 2>(p, n_emit, tail, s) : launch16<NB_, 2, 1>(p, n_emit, tail, s)) : launch16<NB_, 1, 1>(p, n_emit, tail, s))
     return best_nb == 25 ? CSK_L16(25) : CSK_L16(18);
@@ -528,8 +525,8 @@ int csk_launch_co_stack16(int n_blocks, const csk_co_block_args *b, int n_skel, 
         g.mtiles = 1; g.qtiles = (unsigned)((Q + NP - 1) / NP);
         g.x_ring_slots = a.xin_slots; g.x_ring_slot0 = a.xin_slot0; g.y_ring_slots = a.y_slots; g.y_ring_slot0 = a.y_slot0;
         StepParams &t = sp.b[i].t;
-        t = step_params(a.y_ring, a.y_slots, a.y_slot0, 1, a.tcn_w, a.xin, a.xin_slots, a.x_res_slot0, 1, nullptr, a.tcn_bias, a.out,
-                        a.out_slots, a.out_slot0, a.c_out, a.c_out, P, 9, a.res_mode, a.res_mode ? a.c_in : 0, 1);
+        t = step_params(StepCall{a.y_ring, a.y_slots, a.y_slot0, 1, 4, a.tcn_w, a.xin, a.xin_slots, a.x_res_slot0, 1, nullptr, a.tcn_bias, a.out,
+                                 a.out_slots, a.out_slot0, a.c_out, a.c_out, P, 9, a.res_mode, a.res_mode ? a.c_in : 0, 1, 1, nullptr});
         t.gx = (unsigned)((P + NP - 1) / NP); t.gy = 1; t.gz = 1;
     }
     void (*kern)(CoStackParams) = best_nb == 25 ? co_stack16_kernel<25> : co_stack16_kernel<18>;

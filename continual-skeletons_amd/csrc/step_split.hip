@@ -26,6 +26,7 @@
 // Two barriers per stage (the activation tile is single-buffered: two tiles of 400 positions do not fit twice per CU); the
 // next stage's ring loads are in flight in registers under the stage's MFMAs.
 #include "split_core.h"
+#include "step_params.h"
 #include "tile16.h"
 
 namespace {
@@ -192,16 +193,17 @@ int launch_split(StepSplitParams p, int n_emit, hipStream_t s) {
     return (int)hipGetLastError();
 }
 
-// emissions per tile: 2 when the launch carries an even number (a staged ring slot then serves two taps), else 1; the tile
-// width in 16-position column blocks (NTU: 25 / 13, Kinetics: 18 / 9) follows the launch shape by the cost model of the exact
-// step kernels.  Neither changes an output's summation order.
-int pick_blocks(int n_emit, int Mpad, int64_t P) {
+// The tile of a launch -- the ONE copy of the rule.  E, emissions per tile: 2 when the launch carries an even number (a staged ring
+// slot then serves two taps), else 1; NBE, the tile width in 16-position column blocks (NTU: 25 / 13, Kinetics: 18 / 9), follows the
+// launch shape by the cost model of the exact step kernels.  Neither changes an output's summation order.
+struct SplitTile { int NBE, E; };
+SplitTile split_tile(int n_emit, int Mpad, int64_t P) {
     const int E = n_emit % 2 == 0 ? 2 : 1;
     const int64_t mt = Mpad / 64;
     const int wide = E == 2 ? 13 : 25, narrow = E == 2 ? 9 : 18;
     const double cw = cost_model(((P + 16 * wide - 1) / (16 * wide)) * mt * (n_emit / E), 16.0 * wide * E);
     const double cn = cost_model(((P + 16 * narrow - 1) / (16 * narrow)) * mt * (n_emit / E), 16.0 * narrow * E);
-    return cw <= cn ? wide : narrow;
+    return {cw <= cn ? wide : narrow, E};
 }
 
 }  // namespace
@@ -210,44 +212,36 @@ extern "C" int csk_tcn_step_bf16x3(const float *ring, int slots, int head, int h
                                    const float *x_res, int x_res_slots, int x_res_slot0, int x_res_step,
                                    const void *w_res_split, const float *bias, float *out, int out_slots, int out_slot0,
                                    int c, int c_out, int64_t P, int k, int res_mode, int c_res, int relu, void *stream) {
-    if (!ring || !w_split || !bias || !out) CSK_FAIL("tcn_step_bf16x3: null pointer");
-    if (c <= 0 || c_out <= 0 || P < 4 || (P & 3)) CSK_FAIL("tcn_step_bf16x3: bad dims (P must be a positive multiple of 4)");
-    if (k != 9) CSK_FAIL("tcn_step_bf16x3: the split kernel is built for the 9 x 1 temporal conv (k = %d); use csk_tcn_step_f32", k);
-    if (head_step < 1 || head_step > 2) CSK_FAIL("tcn_step_bf16x3: head_step must be 1 or 2 (the stride the weight image was packed for)");
-    if (slots < k || head < 0 || head >= slots) CSK_FAIL("tcn_step_bf16x3: bad slots/head");
-    if (n_emit < 1 || n_emit > 64 || out_slots < n_emit || out_slot0 < 0 || out_slot0 >= out_slots)
-        CSK_FAIL("tcn_step_bf16x3: bad emission geometry");
-    if (slots < k - 1 + (n_emit - 1) * head_step + 1) CSK_FAIL("tcn_step_bf16x3: ring too shallow for %d emissions", n_emit);
-    if (res_mode != CSK_RES_NONE && res_mode != CSK_RES_IDENTITY && res_mode != CSK_RES_CONV) CSK_FAIL("tcn_step_bf16x3: bad res_mode");
-    if (res_mode != CSK_RES_NONE) {
-        if (!x_res) CSK_FAIL("tcn_step_bf16x3: residual requested without x_res");
-        if (c_res <= 0 || x_res_slots < 1 || x_res_slot0 < 0 || x_res_slot0 >= x_res_slots || x_res_step < 0)
-            CSK_FAIL("tcn_step_bf16x3: bad residual ring geometry");
-        if (res_mode == CSK_RES_IDENTITY && c_res != c_out) CSK_FAIL("tcn_step_bf16x3: identity residual needs c_res == c_out");
-        if (res_mode == CSK_RES_CONV && !w_res_split) CSK_FAIL("tcn_step_bf16x3: conv residual without w_res");
-    }
-    if (((uintptr_t)ring | (uintptr_t)(x_res ? x_res : ring) | (uintptr_t)out) & 15) CSK_FAIL("tcn_step_bf16x3: state pointers must be 16-byte aligned");
-    if (((uintptr_t)w_split | (uintptr_t)(w_res_split ? w_res_split : w_split)) & 15) CSK_FAIL("tcn_step_bf16x3: packed weights must be 16-byte aligned");
+    const StepCall call = {ring, slots, head, head_step, n_emit, w_split, x_res, x_res_slots, x_res_slot0, x_res_step, w_res_split, bias, out,
+                           out_slots, out_slot0, c, c_out, P, k, res_mode, c_res, relu, 1, nullptr};
+    const StepParams q = step_params(call);         // for Mpad and the residual ring, stood in for where the call has no x_res
+    const int Cres = res_mode != CSK_RES_NONE ? c_res : 1;
+    const int rc = step_check("tcn_step_bf16x3", "slots/head", call, true, [&]() -> int {      // (step_params.h) with what only this entry requires
+        if (k != 9) CSK_FAIL("tcn_step_bf16x3: the split kernel is built for the 9 x 1 temporal conv (k = %d); use csk_tcn_step_f32", k);
+        if (head_step < 1 || head_step > 2) CSK_FAIL("tcn_step_bf16x3: head_step must be 1 or 2 (the stride the weight image was packed for)");
+        if (res_mode != CSK_RES_NONE && res_mode != CSK_RES_IDENTITY && res_mode != CSK_RES_CONV) CSK_FAIL("tcn_step_bf16x3: bad res_mode");
+        if ((uintptr_t)out & 15) CSK_FAIL("tcn_step_bf16x3: state pointers must be 16-byte aligned");
+        if (((uintptr_t)w_split | (uintptr_t)w_res_split) & 15) CSK_FAIL("tcn_step_bf16x3: packed weights must be 16-byte aligned");
+        if ((int64_t)slots * c * P * 4 >= (1ll << 32) || (int64_t)q.xres_slots * Cres * P * 4 >= (1ll << 32) || (int64_t)out_slots * c_out * P * 4 >= (1ll << 32))
+            CSK_FAIL("tcn_step_bf16x3: a ring of 4 GB or more (32-bit byte offsets inside the rings)");
+        return 0;
+    });
+    if (rc) return rc;
+    if (res_mode != CSK_RES_NONE && c_res <= 0) CSK_FAIL("tcn_step_bf16x3: bad residual ring geometry");
     StepSplitParams p;
-    p.ring = ring; p.w = (const u32x4 *)w_split; p.xres = x_res ? x_res : ring; p.wres = (const u32x4 *)w_res_split; p.bias = bias; p.out = out;
-    p.C = c; p.nch16 = round_up(c, KS) / KS; p.Cout = c_out; p.Mpad = round_up(c_out, CSK_MT);
+    p.ring = ring; p.w = (const u32x4 *)w_split; p.xres = q.xres; p.wres = (const u32x4 *)w_res_split; p.bias = bias; p.out = out;
+    p.C = c; p.nch16 = round_up(c, KS) / KS; p.Cout = c_out; p.Mpad = q.Mpad;
     p.slots = slots; p.head = head; p.head_step = head_step; p.res_mode = res_mode;
-    p.Cres = res_mode != CSK_RES_NONE ? c_res : 1; p.nch16_res = round_up(p.Cres, KS) / KS; p.relu = relu; p.P = P;
-    p.xres_slots = x_res ? x_res_slots : 1; p.xres_slot0 = x_res ? x_res_slot0 : 0; p.xres_step = x_res_step;
-    p.out_slots = out_slots; p.out_slot0 = out_slot0;
-    // 32-bit byte offsets inside the rings
-    if ((int64_t)slots * c * P * 4 >= (1ll << 32) || (int64_t)p.xres_slots * p.Cres * P * 4 >= (1ll << 32) ||
-        (int64_t)out_slots * c_out * P * 4 >= (1ll << 32))
-        CSK_FAIL("tcn_step_bf16x3: a ring of 4 GB or more (32-bit byte offsets inside the rings)");
-    const int E = n_emit % 2 == 0 ? 2 : 1, nbe = pick_blocks(n_emit, p.Mpad, P);
-    const bool w = nbe == (E == 2 ? 13 : 25);
+    p.Cres = Cres; p.nch16_res = round_up(p.Cres, KS) / KS; p.relu = relu; p.P = P;
+    p.xres_slots = q.xres_slots; p.xres_slot0 = q.xres_slot0; p.xres_step = x_res_step; p.out_slots = out_slots; p.out_slot0 = out_slot0;
+    const SplitTile t = split_tile(n_emit, p.Mpad, P);
     hipStream_t s = (hipStream_t)stream;
-    if (E == 1) return w ? launch_split<25, 1, 1>(p, n_emit, s) : launch_split<18, 1, 1>(p, n_emit, s);
-    if (head_step == 2) return w ? launch_split<13, 2, 2>(p, n_emit, s) : launch_split<9, 2, 2>(p, n_emit, s);
-    return w ? launch_split<13, 2, 1>(p, n_emit, s) : launch_split<9, 2, 1>(p, n_emit, s);
+    if (t.E == 1) return t.NBE == 25 ? launch_split<25, 1, 1>(p, n_emit, s) : launch_split<18, 1, 1>(p, n_emit, s);
+    if (head_step == 2) return t.NBE == 13 ? launch_split<13, 2, 2>(p, n_emit, s) : launch_split<9, 2, 2>(p, n_emit, s);
+    return t.NBE == 13 ? launch_split<13, 2, 1>(p, n_emit, s) : launch_split<9, 2, 1>(p, n_emit, s);
 }
 
 extern "C" int csk_tcn_step_bf16x3_tile(int n_emit, int c_out, int64_t P) {
     if (n_emit < 1 || n_emit > 64 || c_out <= 0 || P < 4 || (P & 3)) CSK_FAIL("tcn_step_bf16x3_tile: bad dims");
-    return pick_blocks(n_emit, round_up(c_out, CSK_MT), P);
+    return split_tile(n_emit, round_up(c_out, CSK_MT), P).NBE;
 }

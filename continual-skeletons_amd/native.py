@@ -42,6 +42,7 @@ SIGNATURES = {
     "csk_agcn_stage_framewise_f32_route": [_p, _i, _i, _i, _i, _i, _i, _l, _l, _i],
     "csk_tcn_step_f32": [_p, _i, _i, _i, _i, _p, _p, _i, _i, _i, _p, _p, _p, _i, _i, _i, _i, _l, _i, _i, _i, _i, _i, _p, _p],
     "csk_tcn_step_f32_tile": [_i, _i, _i, _i, _i, _i, _i, _l, _i, _i, _i, _i],
+    "csk_tcn_step_f32_route": [_i, _i, _i, _i, _i, _i, _i, _l, _i, _i, _i, _i, C.POINTER(C.c_int32)],
     "csk_tcn_step_bf16x3": [_p, _i, _i, _i, _i, _p, _p, _i, _i, _i, _p, _p, _p, _i, _i, _i, _i, _l, _i, _i, _i, _i, _p],
     "csk_tcn_step_bf16x3_tile": [_i, _i, _l],
     "csk_co_stack_step_f32": [_i, _p, _i, _i, _l, _p],

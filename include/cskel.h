@@ -29,7 +29,7 @@ extern "C" {
 
 /* Stays 16 while entries are only added: csk_derive_modality_f32 / _frames_f32, csk_prenorm_f32 / _frames_f32,
  * csk_tcn_stage_wino_valid_f32, csk_tcn_stage_wino_valid_res_f32, csk_co_plan_set_delays, csk_gcn_stage_f32_route, csk_gcn_stage_splitk_f32_route, csk_co_prime_pack_f32, csk_co_head_clip_f32, csk_str_unit_f32_route,
- * csk_co_stack_step_f32_route and
+ * csk_co_stack_step_f32_route, csk_tcn_step_f32_route and
  * csk_select_people_f32 / _frames_f32 and csk_ntu_intake_f32 are additive (no existing entry, struct
  * or constant changed). */
 #define CSK_ABI_VERSION 16
@@ -445,6 +445,23 @@ int csk_tcn_step_f32(const float *ring, int slots, int head, int head_step, int 
  */
 int csk_tcn_step_f32_tile(int slots, int head_step, int n_emit, int x_res_slots, int out_slots, int c, int c_out, int64_t P,
                           int k, int res_mode, int c_res, int ksplit);
+
+/*
+ * The kernel csk_tcn_step_f32 launches for a launch shape -- the function the launcher switches on.  Arguments and argument checks
+ * as csk_tcn_step_f32_tile's (-1 with the same message).
+ *  route[0]  the family: 1 = the slot-balanced 16x16x4 step (csrc/step16.hip), 2 = the 32x32x2 step (csrc/step.hip)
+ *  route[1]  the instantiation: family 1, csk_tcn_step_f32_tile's value (never 0 here); family 2,
+ *            MT * 100000 + E * 10000 + HS * 1000 + SPLIT * 100 + K9 * 10 + OCC of tcn_step_kernel<MT, E, HS, SPLIT, K9, OCC> -- MT rows
+ *            of a workgroup tile (128 when c_out_pad is a multiple of 128, else 64), E emissions folded into a tile (4, 2 or 1), HS
+ *            the head_step the tile is built for, SPLIT 1 when the request leaves more than one channel range (followed by
+ *            step_reduce_kernel), K9 1 for k == 9, OCC workgroups per CU (2; 3 = the 168-register twin of <64, 4, 1>)
+ *  route[2]  family 2: the workgroups of that launch (-1: 2^31 or more, the entry refuses it as "grid too large"); family 1: 0
+ * Host arithmetic only (no GPU).  For tests and tools: within family 2, E, HS and OCC follow the launch size and do not change an
+ * output's summation order.
+ */
+#define CSK_STEP_ROUTE_WORDS 3
+int csk_tcn_step_f32_route(int slots, int head_step, int n_emit, int x_res_slots, int out_slots, int c, int c_out, int64_t P,
+                           int k, int res_mode, int c_res, int ksplit, int32_t *route);
 
 /*
  * OPT-IN step precision "bf16x3" of csk_tcn_step_f32 (same reference method, models/base.py:307-334, 390-446; same rings,

@@ -99,7 +99,7 @@ ENTRIES = {
     # ---- plan, ABI, probe and pure host queries
     "csk_abi_version": Entry(NO_POINTER),
     "csk_stream_overlap_probe": Entry(NO_POINTER, note="its buffers are the probe's own scratch"),
-    "csk_tcn_step_f32_tile": Entry(NO_POINTER), "csk_tcn_step_bf16x3_tile": Entry(NO_POINTER),
+    "csk_tcn_step_f32_tile": Entry(NO_POINTER), "csk_tcn_step_f32_route": Entry(NO_POINTER), "csk_tcn_step_bf16x3_tile": Entry(NO_POINTER),
     "csk_co_stack_step_f32_route": Entry(NO_POINTER, note="reads the blocks' scalar fields only"),
     "csk_str_unit_f32_route": Entry(NO_POINTER),
     "csk_co_plan_create": Entry(NO_POINTER), "csk_co_plan_destroy": Entry(NO_POINTER), "csk_co_plan_update_weights": Entry(NO_POINTER),
